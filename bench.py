@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — throughput of the mel->waveform hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the HiFi-GAN V1 generator over one batch of synthetic mels already resident
 in HBM: per GPU ``--batch`` utterances x ``--frames`` mel frames (defaults 64 x 1024 = BASELINE.json
@@ -14,6 +14,9 @@ no data-path collective.  Rank 0 prints ONE JSON line with:
   parity_bf16  max-abs / SNR of the bf16 engine against the reference generator's fp64 output (tests/golden)
   cpu_baseline the REFERENCE's own torch generator (oracle/_ref, built by oracle/build_ref.py) on this box's host cores;
                the numpy port of the oracle when that archive is absent (kind says which)
+A plain run prints the headline only (value, ms_per_step, the run's shape and its FLOP arithmetic): set up, warm up, time the K steps.
+Everything from ``rtf_b1`` down, and the long-form and pipeline legs, takes runs of its own and comes with ``--full`` (``full_report``).
+``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``); the inputs are seeded, so two builds compare.
 
 With ``--gpus N`` (N > 1) and no WORLD_SIZE in the environment the script re-executes itself under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1``: one rank per GPU, backend
@@ -337,6 +340,10 @@ def main():
     ap.add_argument("--stage", type=int, default=-1, help="engine option 'stage' (bf16: the whole last stage in one launch; 0 / 1; -1 = engine default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rtf", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement and check (roofline, pipeline, long-form, parity, RTF, fp32 / bf16x3 paths, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's waveforms (rank 0; a fixed sample of rows when larger than 32 MiB) to DIR/waveform.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -403,6 +410,83 @@ def main():
         per_rank_ms = [float(x.item()) / args.steps * 1e3 for x in allt]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and info.rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    # the last timed step's waveforms are sane (every rank checks its own shard)
+    assert bool(torch.isfinite(out).all()), "non-finite output"
+    assert float(out.abs().max()) <= 1.0, "waveform outside tanh's range"
+
+    side = full_report(args, gen, mel, out, info, dev, barrier) if args.full else None
+
+    if info.rank == 0:
+        samples_per_step = n_gpus * B * 256 * T
+        value = samples_per_step * args.steps / elapsed
+        res = {
+            "metric": "audio samples/sec whole-node, HiFi-GAN V1 mel2wave",
+            "value": value,
+            "unit": "samples/s",
+            "n_gpus": n_gpus,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic (seeded random weights of the V1 architecture, seeded log-mel-like inputs)",
+            "config": {
+                "workload": f"HiFi-GAN V1 generator, {B} utterances x {T} mel frames per GPU per step (BASELINE configs[2] shape), {args.dtype}",
+                "batch_per_gpu": B,
+                "frames": T,
+                "samples_per_step": samples_per_step,
+                "parallelism": f"dp{n_gpus} utterance-sharded, weights broadcast once, no data-path collective",
+                "microbatch": gen.get_option("microbatch"),
+                "streams": gen.get_option("streams"),
+                "schedule": "engine default: micro-batches of <= 32768 frames on two HIP streams" if not (args.microbatch or args.streams) else "as given by --microbatch / --streams",
+            },
+            "weights_broadcast": {"backend": bstats.get("backend"), "ranks_in_group": bstats.get("world"), "bytes": bstats.get("bytes"),
+                                  "ms_rank0": bstats.get("broadcast_ms"),
+                                  # after the broadcast every rank checksums its blob, MIN / MAX all-reduced: the job stops if they differ (null at N = 1)
+                                  "blob_checksum": bstats.get("blob_checksum"), "blob_checksum_equal": bstats.get("blob_checksum_equal")},
+            "ms_per_step_per_rank": per_rank_ms,
+            "tflops_whole_job": value * FLOP_PER_SAMPLE / 1e12,
+            "frac_of_mfma_peak_whole_forward": value * FLOP_PER_SAMPLE / 1e12 / (PEAK_TFLOPS[args.dtype] * n_gpus),
+        }
+        if side:
+            res.update(side)
+        print(json.dumps(res), flush=True)
+
+    barrier()
+    gen.close()
+    if n_gpus > 1 and dist.is_initialized():
+        dist.destroy_process_group()
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs budget
+
+
+def dump_outputs(dirname: str, out: torch.Tensor) -> None:
+    """--dump-outputs: the waveforms the timed path returned in its last step, [rows, 256 x frames] float32, as DIR/waveform.npy.
+    A batch larger than DUMP_BYTES keeps a fixed, seeded, sorted choice of whole rows (and of positions when one row alone is larger), so
+    that two builds run with the same arguments write the same elements."""
+    B, L = out.shape
+    rows = np.sort(np.random.default_rng(0).choice(B, max(1, min(B, DUMP_BYTES // (4 * L))), replace=False))
+    y = out[torch.from_numpy(rows).to(out.device)]
+    if y.numel() * 4 > DUMP_BYTES:
+        cols = np.sort(np.random.default_rng(1).choice(L, DUMP_BYTES // 4, replace=False))
+        y = y[:, torch.from_numpy(cols).to(out.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "waveform.npy"), y.float().cpu().numpy())
+
+
+def full_report(args, gen, mel, out, info, dev, barrier):
+    """--full: every measurement and check beyond the headline, run after the timed steps on the same generator and inputs (the
+    roofline calibration pass, the text -> waveform pipeline and the long-form utterance with their parity-grade peers, the bf16 parity,
+    batch-1 RTF, the fp32 and split-operand paths, the CPU baseline).  Every rank takes part (the sharded legs); returns the keys rank 0
+    adds to the result line, None on the other ranks."""
+    n_gpus = info.world
+    B, T = args.batch, args.frames
 
     # ---- roofline calibration pass (rank 0's kernel timing) ----
     # The product schedule runs a large batch as two half-size passes side by side on two streams (engine.hip: auto_streams), so a kernel shares
@@ -573,43 +657,9 @@ def main():
         longform["vocoder"] = f"{args.dtype} engine"
         del m10
 
-    assert bool(torch.isfinite(out).all()), "non-finite output"
-    assert float(out.abs().max()) <= 1.0, "waveform outside tanh's range"
-
+    res = None
     if info.rank == 0:
-        samples_per_step = n_gpus * B * 256 * T
-        value = samples_per_step * args.steps / elapsed
-        res = {
-            "metric": "audio samples/sec whole-node, HiFi-GAN V1 mel2wave",
-            "value": value,
-            "unit": "samples/s",
-            "n_gpus": n_gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic (seeded random weights of the V1 architecture, seeded log-mel-like inputs)",
-            "config": {
-                "workload": f"HiFi-GAN V1 generator, {B} utterances x {T} mel frames per GPU per step (BASELINE configs[2] shape), {args.dtype}",
-                "batch_per_gpu": B,
-                "frames": T,
-                "samples_per_step": samples_per_step,
-                "parallelism": f"dp{n_gpus} utterance-sharded, weights broadcast once, no data-path collective",
-                "microbatch": gen.get_option("microbatch"),
-                "streams": gen.get_option("streams"),
-                "schedule": "engine default: micro-batches of <= 32768 frames on two HIP streams" if not (args.microbatch or args.streams) else "as given by --microbatch / --streams",
-            },
-            "weights_broadcast": {"backend": bstats.get("backend"), "ranks_in_group": bstats.get("world"), "bytes": bstats.get("bytes"),
-                                  "ms_rank0": bstats.get("broadcast_ms"),
-                                  # after the broadcast every rank checksums its blob, MIN / MAX all-reduced: the job stops if they differ (null at N = 1)
-                                  "blob_checksum": bstats.get("blob_checksum"), "blob_checksum_equal": bstats.get("blob_checksum_equal")},
-            "ms_per_step_per_rank": per_rank_ms,
-            "tflops_whole_job": value * FLOP_PER_SAMPLE / 1e12,
-            "frac_of_mfma_peak_whole_forward": value * FLOP_PER_SAMPLE / 1e12 / (PEAK_TFLOPS[args.dtype] * n_gpus),
-        }
+        res = {}
         # ---- roofline of the dominant kernel, HIP events on the launch stream, timed region only ----
         if prof["launches"] > 0 and prof["ms"] > 0:
             ach = prof["flops"] / (prof["ms"] * 1e-3) / 1e12
@@ -814,14 +864,9 @@ def main():
         else:  # the key is always there: the CPU baseline is timed on rank 0 of the N = 1 run only (it would otherwise compete with the ranks' host threads)
             res["cpu_baseline"] = None
             res["cpu_baseline_skipped"] = "--no-cpu-baseline" if n_gpus == 1 else f"N = {n_gpus} > 1: the reference's CPU path is timed in the N = 1 run only"
-        print(json.dumps(res), flush=True)
-
-    barrier()
-    gen.close()
     if gx_side is not None:
         gx_side.close()
-    if n_gpus > 1 and dist.is_initialized():
-        dist.destroy_process_group()
+    return res
 
 
 if __name__ == "__main__":

@@ -48,8 +48,16 @@ def load_reference_archive(state_dict=None):
     return ts
 
 
+def _present(path: Path) -> bool:
+    """``path.exists()``, with a location this user may not read counted as absent (``exists()`` raises there)."""
+    try:
+        return path.exists()
+    except OSError:
+        return False
+
+
 def main() -> int:
-    if not (REF / "vietTTS/hifigan/torch_model.py").exists():
+    if not _present(REF / "vietTTS/hifigan/torch_model.py"):
         print("oracle/build_ref.py: /root/reference not present — keeping whatever oracle/_ref/ holds")
         return 0
     import warnings

@@ -441,6 +441,36 @@ def test_bf16_benchmark_shape_B64_T1024(golden_dir, dev, capsys):
         gen.close()
 
 
+def test_plain_bench_line_and_dumped_outputs(dev, tmp_path):
+    """bench.py without --full prints the headline alone, and --dump-outputs writes what its last timed step computed: the bf16 engine's
+    waveforms for the benchmark's own seeded weights and mels, bit for bit what the engine returns for them in this process."""
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from viettts_amd.hifigan.generator import Generator
+
+    repo = Path(__file__).resolve().parents[1]
+    cmd = [sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3", "--frames", "96",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 2 and d["dtype"] == "bf16" and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(3 * 256 * 96 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    for k in ("roofline", "rtf_b1", "parity_bf16", "fp32_path", "bf16x3_path", "longform_10min", "pipeline_256", "cpu_baseline"):
+        assert k not in d, k  # --full only
+    y = np.load(tmp_path / "waveform.npy")
+    assert y.dtype == np.float32 and y.shape == (3, 256 * 96)
+    gen = Generator(V1, device=dev, dtype="bf16")
+    gen.load_params(synthetic_params(V1, 4321, "scaled"))
+    try:
+        want = gen(torch.from_numpy(synthetic_mel(3, 96, 1234)).to(dev)).cpu().numpy()
+    finally:
+        gen.close()
+    assert np.array_equal(y, want)
+
+
 def test_parallel_resblocks_schedule_is_bit_identical_bf16():
     """bf16 engine, small launches: the three ResBlocks of a stage on parallel streams with scratch of their own; only a ResBlock's
     last kernel touches the shared bf16 accumulator and those kernels are chained by events in the sequential order, so every sample

@@ -22,7 +22,7 @@ def test_two_ranks_share_one_gpu_and_shard_both_legs():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY"):
         env.pop(k, None)
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2", "--frames", "128",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
@@ -58,7 +58,7 @@ def test_eight_ranks_share_one_gpu_at_the_world_size_the_driver_uses():
     env = dict(os.environ, VTTS_DIST_BACKEND="gloo", VTTS_SHARE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY"):
         env.pop(k, None)
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--batch", "1", "--frames", "64", "--no-cpu-baseline"]
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--batch", "1", "--frames", "64", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -90,7 +90,7 @@ def test_two_gpus_real_rccl_broadcast_and_sharded_legs():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "VTTS_DIST_BACKEND", "VTTS_SHARE_GPU", "HSA_ENABLE_IPC_MODE_LEGACY"):
         env.pop(k, None)
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "4", "--frames", "256", "--no-cpu-baseline"]
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "4", "--frames", "256", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])

@@ -240,23 +240,6 @@ def test_oracle_equals_the_reference_code_executed():
         assert np.abs(mel - g[p + "mel_full"]).max() < 1e-11
 
 
-@pytest.mark.skipif(not Path("/root/reference/vietTTS/nat/model.py").exists(), reason="needs /root/reference (build container only)")
-def test_reference_nat_code_reproduces_the_committed_fixture(tmp_path):
-    """Re-mint the fixture from the reference's files and compare with the committed one (where the reference exists)."""
-    import os
-    import subprocess
-    import sys
-
-    out = tmp_path / "again.npz"
-    env = dict(os.environ, VTTS_NAT_GOLDEN_OUT=str(out))
-    r = subprocess.run([sys.executable, str(Path(__file__).parents[1] / "oracle" / "make_nat_golden.py")], env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout + r.stderr
-    a, b = np.load(NAT_GOLDEN), np.load(out)
-    assert sorted(a.files) == sorted(b.files)
-    for k in a.files:
-        assert np.array_equal(a[k], b[k]), k
-
-
 def test_checkpoint_with_haiku_and_jax_objects_loads_without_those_libraries(tmp_path):
     """A checkpoint pickled the way the reference pickles it (vietTTS/nat/utils.py:18-26: Haiku mappings of jax arrays, an optax state)
     read where none of those libraries exists.  The classes are EMULATED here under their real module paths (pickling hooks restated

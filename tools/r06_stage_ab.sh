@@ -3,7 +3,7 @@
 # per-kernel durations of a one-stream pass with the option on (rocprofv3 --kernel-trace --stats).   gpurun -- 'bash tools/r06_stage_ab.sh [tag]'
 T=${1:-r06_stage}; R=$PWD; O=$R/gpurun_out/$T; mkdir -p $O
 for rep in 1 2 3; do for t in 1 0; do
-  python bench.py --stage $t --no-cpu-baseline --no-f32 --no-rtf --steps 20 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('stage', $t, 'ms_per_step', round(d['ms_per_step'],3), 'calib', round(d['roofline']['calibration_ms_per_step'],3))"
+  python bench.py --full --stage $t --no-cpu-baseline --no-f32 --no-rtf --steps 20 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('stage', $t, 'ms_per_step', round(d['ms_per_step'],3), 'calib', round(d['roofline']['calibration_ms_per_step'],3))"
 done; done | tee $O/ab.txt
 cd /tmp && export TMPDIR=/tmp
 for t in 1 0; do

@@ -7,5 +7,5 @@ timeout 1700 python -m pytest tests -m gpu -q -x --timeout 900 > $O/pytest_gpu.l
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1
 bash tools/profile_final.sh $TAG > $O/profile_final.log 2>&1; tail -4 $O/profile_final.log
 cp gpurun_out/$TAG/counters_bf16.json gpurun_out/$TAG/counters_f32.json gpurun_out/$TAG/counters_bf16x3.json profiles/ 2>/dev/null
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-700 $O/bench.json; tail -2 $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-700 $O/bench.json; tail -2 $O/bench.err
 bash tools/r05_pipeline_stats.sh $TAG 2>&1 | tail -4
