@@ -167,19 +167,31 @@ def test_built_library_has_no_packed_f32_valu():
     assert all(pk == 0 for pk, _ in counts.values()), counts
 
 
-def test_experiment_includes_still_compile(tmp_path):
-    """Development-only code lives OUT of the product sources (round 6: `tools/kbench/experiments/nat_*.inc`, included by `nat.hip` only under
-    `-DVTTS_NAT_PERSIST` / `-DVTTS_NAT_PKFMA` / `-DVTTS_NAT_PP_EXP`; the timeline stamps of the stage / whole-ResBlock kernels under `-DVTTS_TIMELINE`).
-    The findings under profiles/ cite those builds as provenance, so they must not rot: the three files that carry them compile with every switch on."""
+def test_timeline_builds_still_compile(tmp_path):
+    """The timeline stamps of the whole-ResBlock kernels (`-DVTTS_TIMELINE=1`, tools/rx_timeline.py) are compiled out of the product library.
+    The findings under profiles/ cite those builds as provenance, so they must not rot: the two files that carry them compile with the switch on."""
     import subprocess
 
     from viettts_amd.csrc import build
 
-    defs = ["-DVTTS_NAT_PERSIST=1", "-DVTTS_NAT_PKFMA=7", "-DVTTS_NAT_PP_EXP=1", "-DVTTS_TIMELINE=1"]
     procs = []
-    for src in ("nat.hip", "kernels_bf16_stage.hip", "kernels_x3_rb.hip"):
-        cmd = [build._hipcc(), *build.FLAGS, *build.FILE_FLAGS[src], *defs, "-c", str(build.CSRC / src), "-o", str(tmp_path / (src + ".o"))]
+    for src in ("kernels_bf16_rbg.hip", "kernels_x3_rb.hip"):
+        cmd = [build._hipcc(), *build.FLAGS, *build.FILE_FLAGS[src], "-DVTTS_TIMELINE=1", "-c", str(build.CSRC / src), "-o", str(tmp_path / (src + ".o"))]
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
     for src, p in procs:
         _, err = p.communicate(timeout=900)
         assert p.returncode == 0, (src, err[-2000:])
+
+
+def test_sources_include_only_listed_files():
+    """build._digest() hashes SOURCES and HEADERS only, so every quoted #include of those files must resolve to one of them: anything else
+    could change without the library being rebuilt."""
+    from viettts_amd.csrc import build
+
+    listed = {(build.CSRC / name).resolve() for name in build.SOURCES + build.HEADERS}
+    stray = []
+    for path in sorted(listed):
+        for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', path.read_text(), re.M):
+            if (path.parent / inc).resolve() not in listed:
+                stray.append(f"{path.name}: {inc}")
+    assert not stray, stray

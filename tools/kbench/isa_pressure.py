@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPR liveness of a straight-line stretch of a kernel's ISA (tools/kbench/cc_one.sh writes /tmp/<stem>.s): backward liveness over lines [a, b) taken as a
 loop body (two passes, so loop-carried values count), printing the live-register count every `step` lines and the maximum.
-    python tools/kbench/isa_pressure.py /tmp/kernels_bf16_stage.s 7142 9612 [step]"""
+    python tools/kbench/isa_pressure.py /tmp/kernels_bf16_rbk.s <first_line> <end_line> [step]"""
 import re, sys
 L = open(sys.argv[1]).read().split('\n')
 a, b = int(sys.argv[2]), int(sys.argv[3])

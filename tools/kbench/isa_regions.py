@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-region instruction counts of a kernel's ISA (tools/kbench/cc_one.sh writes /tmp/<stem>.s): regions end at barriers, branches and labels.
-    python tools/kbench/isa_regions.py /tmp/kernels_bf16_stage.s [min_instructions]"""
+    python tools/kbench/isa_regions.py /tmp/kernels_bf16_rbk.s [min_instructions]"""
 import re, sys
 lines = open(sys.argv[1]).read().split('\n')
 minv = int(sys.argv[2]) if len(sys.argv) > 2 else 20

@@ -33,9 +33,6 @@ __device__ __forceinline__ float vadd_raw(float a, float b) { return a + b; }
 // engine divides (it answers to the 1e-4 bar); here the value is rounded to bf16 right afterwards, a product and a quotient differ by at
 // most one fp32 ulp (2^-16 of a bf16 ulp), and an IEEE division is 8 VALU instructions per element (v_div_scale x 2, v_rcp, 3 fma,
 // v_div_fmas, v_div_fixup: ~1000 per tile and wave on the four launches per pass that end a stage — they ran 10-13 % behind their siblings).
-#ifndef VTTS_MRF_DIV  // A/B switch: 1 = round 2's IEEE division per element
-#define VTTS_MRF_DIV 0
-#endif
 __device__ __forceinline__ float mrf_recip(float div) { return 1.0f / div; }
 // LeakyReLU with a slope in (0, 1] (the model's: 0.1, 0.01, model.py:5,122; the engine rejects others): max(v, s v) — the same value as the
 // compare-and-select form for every finite v (v >= 0: s v <= v; v < 0: s v > v), two VALU instructions instead of three
@@ -60,18 +57,9 @@ __device__ __forceinline__ float lrelu01(float v) { return vmax_raw(v, vmul_raw(
 // issue at all while the OTHER wave of the SIMD streams MFMAs — overlap 0.01 against 0.8 for every plain VALU instruction
 // (tools/kbench/coissue.hip, profiles/r03_a_coissue_findings.md) — and the staging / epilogue phases that use this run beside the
 // co-resident workgroup's MFMA loops by design.  The file is built with -fno-slp-vectorize so that hipcc cannot re-pack them.
-#ifndef VTTS_PK_F32  // A/B switch: 1 = round 2's packed multiply
-#define VTTS_PK_F32 0
-#endif
 __device__ __forceinline__ unsigned lrelu01_pack(float lo, float hi) {
-#if VTTS_PK_F32
-    const f32x2 v = {lo, hi};
-    const f32x2 m = v * 0.1f;  // v_pk_mul_f32
-    return pack_bf16x2(vmax_raw(v.x, m.x), vmax_raw(v.y, m.y));
-#else
     const float k = 0.1f;
     return pack_bf16x2(vmax_raw(lo, vmul_raw(lo, k)), vmax_raw(hi, vmul_raw(hi, k)));
-#endif
 }
 __device__ __forceinline__ unsigned lrelu_bf16x2(unsigned u, float s) {
     return pack_bf16x2(lrelu_f(bf16_lo(u), s), lrelu_f(bf16_hi(u), s));
@@ -134,12 +122,9 @@ __device__ __forceinline__ int swz_of(int row) {
 //     profiles/r02_b_pmc_bf16.md).  These tiles are stored in blocks of 16 rows, slot-major inside a block: a block's 16 rows
 //     of one slot are one 256-byte LDS line, so any 16 rows that are distinct mod 16 (a read group) and any 8 consecutive rows
 //     (a write group) hit distinct banks.  Tile rows are allocated in multiples of 16.
-#ifndef VTTS_TILE_BLOCKED  // A/B switch (tools/ab_bench.sh): 0 = round 2's XOR swizzle at every pitch
-#define VTTS_TILE_BLOCKED 1
-#endif
 template <int SPR>
 __device__ __forceinline__ int tile_off(int row, int slot) {
-    if constexpr (SPR >= 16 || !VTTS_TILE_BLOCKED) return row * (SPR * 16) + ((slot ^ swz_of<SPR>(row)) << 4);
+    if constexpr (SPR >= 16) return row * (SPR * 16) + ((slot ^ swz_of<SPR>(row)) << 4);
     else return (row >> 4) * (SPR * 256) + (slot << 8) + ((row & 15) << 4);
 }
 constexpr int tile_rows16(int rows) { return (rows + 15) / 16 * 16; }

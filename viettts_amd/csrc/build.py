@@ -19,7 +19,7 @@ CSRC = Path(__file__).resolve().parent
 ROOT = CSRC.parents[1]
 LIBDIR = CSRC.parent / "lib"
 OBJDIR = CSRC / "build"
-SOURCES = ["engine.hip", "kernels_generic.hip", "kernels_f32_mfma.hip", "kernels_f32_pair.hip", "kernels_x3.hip", "kernels_x3_rb.hip", "kernels_bf16.hip", "kernels_bf16_rbg.hip", "kernels_bf16_rbk.hip", "kernels_bf16_stage.hip", "kernels_bf16_up.hip", "nat.hip"]
+SOURCES = ["engine.hip", "kernels_generic.hip", "kernels_f32_mfma.hip", "kernels_f32_pair.hip", "kernels_x3.hip", "kernels_x3_rb.hip", "kernels_bf16.hip", "kernels_bf16_rbg.hip", "kernels_bf16_rbk.hip", "kernels_bf16_up.hip", "nat.hip"]
 HEADERS = ["vtts_internal.h", "device_common.h", "bf16_common.h", str(ROOT / "include" / "vtts_hifigan.h"), str(ROOT / "include" / "vtts_nat.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # No kernel of this library may contain packed-f32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32); hipcc's SLP vectoriser is
@@ -79,10 +79,7 @@ def _build(force, verbose, stamp, out, libname) -> Path:
 
     def compile_one(src: str) -> Path:
         obj = OBJDIR / (Path(src).stem + "." + libname + ".o")
-        per_file = [] if os.environ.get("VTTS_BUILD_NO_FILE_FLAGS") else FILE_FLAGS.get(src, [])  # experiment builds only (A/B of the flag itself)
-        if src in os.environ.get("VTTS_BUILD_NOSLP_FILES", "").split(","):
-            per_file = ["-fno-slp-vectorize"]
-        cmd = [hipcc, *FLAGS, *per_file, "-c", str(CSRC / src), "-o", str(obj)]
+        cmd = [hipcc, *FLAGS, *FILE_FLAGS.get(src, []), "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -23,7 +23,7 @@
 // (emulated: +1.5 %), the raw residual rows kept in LDS at C = 32 (-29 % HBM bytes, 0.8 % slower).  What did help late in the
 // round: one look-ahead load after each MFMA instead of grouped issue (+2.1 %), LeakyReLU as packed multiply + raw v_max
 // and the bias block as the first MFMA's C operand (-30 % VALU instructions per tile, +0.7 %).
-// Round 2: lean loop addressing (VTTS_LEAN: weight fragments by buffer loads with the k-step in an SGPR offset, one row
+// Round 2: lean loop addressing (weight fragments by buffer loads with the k-step in an SGPR offset, one row
 // address + swizzle term per tap and v_xad_u32 per k-step for the LDS fragments: 43 -> 21 VALU per 64 MFMAs, 2-5 % per pair
 // launch, profiles/r02_a_pair_kernel_findings.md).  The same treatment of the staging loads and of epilogue 2's row accesses
 // (buffer loads / stores with SGPR row offsets, -200 VALU per tile) measured no faster.  A persistent, software-pipelined
@@ -39,20 +39,6 @@
 #include <type_traits>
 
 #include "bf16_common.h"
-
-#ifndef VTTS_XCD_MAP  // XCD-aware tile order (A/B switch, tools/kbench): see resblock_pair_g_bf16_k
-#define VTTS_XCD_MAP 1
-#endif
-
-#ifndef VTTS_RAWRES  // C = 32: the tile's raw rows kept in LDS as the residual (A/B switch)
-#define VTTS_RAWRES 1
-#endif
-#ifndef VTTS_WREG  // C = 32: the convolution's weights register-resident for the whole phase (A/B switch, tools/kbench)
-#define VTTS_WREG 1
-#endif
-#ifndef VTTS_LEAN  // lean loop addressing (buffer loads with SGPR offsets, per-tap swizzle terms): A/B switch, tools/kbench
-#define VTTS_LEAN 1
-#endif
 
 namespace vtts {
 
@@ -79,7 +65,7 @@ struct GTile {
     static constexpr bool UNROLL_ALL = (KSX % RA) != 0;  // else: loop over taps, one tap's k-steps per iteration
     // C = 32: a convolution's whole A operand is NQT * MR fragments = at most 88 VGPRs per lane (k = 11), so it is loaded ONCE per phase,
     // ahead of it, and the MFMA loop carries no vector-memory instruction at all (see conv_phase_wreg)
-    static constexpr bool WREG = VTTS_WREG && UNROLL_ALL && NXC == 1 && NQT * MR * 4 <= 96;
+    static constexpr bool WREG = UNROLL_ALL && NXC == 1 && NQT * MR * 4 <= 96;
     static constexpr int XPT = (ROWSX_MAX * SPR1 + THREADS - 1) / THREADS;
     static constexpr size_t CONV_BYTES = (size_t)KS * C * C * 2;  // packed weights of one convolution
     static_assert(C % (WM * 32) == 0 && N1 % (WN * 32) == 0, "tile/wave mismatch");
@@ -89,7 +75,7 @@ struct GTile {
     // C = 32: the pair is bound by the CU's share of HBM (100 KB per tile at ~8 B per tick: profiles/r03_c_narrow_stage_findings.md), and a third
     // of those bytes is the residual's second read of rows the staging pass has just had in registers: it keeps them, raw, in a second LDS
     // region (32 KB; 69 KB with the X tile, still two workgroups per CU) and epilogue 2 adds them from there
-    static constexpr bool RAWRES = VTTS_RAWRES && NXC == 1 && C == 32;
+    static constexpr bool RAWRES = NXC == 1 && C == 32;
     static constexpr int RAW_BYTES = RAWRES ? tile_rows16(N1) * P1 : 0;
     static __host__ __device__ constexpr int tile_bytes(int dil) {  // rows in multiples of 16 (tile_off's blocks of 16 rows at C = 32 / 64)
         const int bx = tile_rows16(N1 + 2 * H2 * dil) * P1, bt = tile_rows16(ROWST) * P2;
@@ -141,7 +127,6 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     const int b = a.zrev ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
     const int Lp = a.L;                                      // rows allocated per utterance
     const int L = a.lens ? min(max(a.lens[b], 0) * a.len_mul, a.L) : a.L;  // valid rows of this utterance, clamped to its slot (ragged batch: the rest reads as zero padding)
-#if VTTS_XCD_MAP
     // Workgroups go to the 8 XCDs round-robin in launch order (workgroup w -> XCD w % 8, each with its own L2), so consecutive
     // blockIdx.x would put every tile's neighbours — whose halo rows it shares — on OTHER L2s.  gridDim.x is padded to a
     // multiple of 8 and an XCD takes a contiguous eighth of THIS utterance's valid tiles, in order (a tile's left halo was staged by
@@ -156,10 +141,6 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     const int nt = (L + TS - 1) / TS, r = (int)((blockIdx.x + b) & 7), lo = (r * nt) >> 3, hi = ((r + 1) * nt) >> 3;
     const int tile = xmap ? lo + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (xmap && tile >= hi) return;
-#else
-    constexpr int TS = T::TAIL ? NT2 - 2 * T::TAIL_H : NT2;
-    const int tile = blockIdx.x;
-#endif
     const int t0 = tile * TS - (T::TAIL ? T::TAIL_H : 0);   // first output time step (row 0 of c2's output) of this workgroup
     if (t0 + (T::TAIL ? T::TAIL_H : 0) >= L) return;        // a tile past this utterance's end: nothing reads its rows
     const int dil = a.dil;
@@ -226,7 +207,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         // Blocked tiles (SPR1 = 4, 8): 8 consecutive lanes take 8 consecutive rows of one slot, which is what keeps the
         // ds_write_b128 conflict-free there (tile_off); the wave touches the same cache lines either way.
         constexpr int RW = 64 / SPR1;  // rows per wave and unit
-        const int row0 = (SPR1 >= 16 || !VTTS_TILE_BLOCKED) ? tid / SPR1 : wave * RW + lane % RW, c = (SPR1 >= 16 || !VTTS_TILE_BLOCKED) ? tid % SPR1 : lane / RW;
+        const int row0 = SPR1 >= 16 ? tid / SPR1 : wave * RW + lane % RW, c = SPR1 >= 16 ? tid % SPR1 : lane / RW;
         auto act2 = [](unsigned u) { return lrelu01_pack(bf16_lo(u), bf16_hi(u)); };  // LRELU_SLOPE, model.py:5,46
         unsigned char* const lds0 = xt + tile_off<SPR1>(row0, c);  // unit i: + i * RPI * P1 (RPI is a multiple of 16: same swizzle / same place in its block)
         // T::RAWRES: X-tile row r holds time t0 - H2 - h1 + r; rows of times t0 .. t0 + N1 - 1 also go, un-activated, to the residual region
@@ -368,7 +349,6 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             // of a step depend only on its position in the block
             constexpr int UB = NKS < 8 ? NKS : 8;
             static_assert(T::UNROLL_ALL || (UB % RA == 0 && UB % 2 == 0 && NKS % UB == 0), "ring slot / B parity must be compile-time in the block loop");
-#if VTTS_LEAN
             // Lean addressing of the rolled loop (round 2): the loop's own address arithmetic shares the SIMD's issue port with
             // the co-resident workgroup's staging / epilogue VALU work.  A fragments: buffer loads, lane offset in a VGPR, the
             // k-step's offset in an SGPR, the m-block an immediate.  B fragments: one row address + one swizzle term per tap
@@ -388,7 +368,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             };
             auto tap_terms = [&](int tap, unsigned& tapaddr, unsigned& xs) {
                 const int row = rowbase0 + tap * dl;
-                if constexpr (SPRB >= 16 || !VTTS_TILE_BLOCKED) {
+                if constexpr (SPRB >= 16) {
                     tapaddr = (unsigned)row * PB;
                     xs = (unsigned)(swz_of<SPRB>(row) ^ lh) << 4;
                 } else {  // blocked tile: slot 2*ks + lh is 512*ks + 256*lh bytes into the row's block
@@ -397,7 +377,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                 }
             };
             auto load_b2 = [&](unsigned tapaddr, unsigned xs, int ks, int par) {
-                const unsigned addr = (SPRB >= 16 || !VTTS_TILE_BLOCKED) ? tapaddr + (xs ^ (unsigned)(ks << 5)) : tapaddr + (unsigned)(ks << 9);
+                const unsigned addr = SPRB >= 16 ? tapaddr + (xs ^ (unsigned)(ks << 5)) : tapaddr + (unsigned)(ks << 9);
 #pragma unroll
                 for (int nr = 0; nr < NR; ++nr) bf[par][nr] = *reinterpret_cast<const bf16x8*>(xt + addr + nr * 32 * PB);
             };
@@ -418,18 +398,6 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                     pin_step(true);
                 }
             };
-#else
-            auto block = [&](int s0, auto first_tag) {  // the first block of a fresh pass is peeled: its first step reads the bias block
-#pragma unroll
-                for (int i = 0; i < UB; ++i) {
-                    const int sa = s0 + i + PA, sb = s0 + i + 1;
-                    load_a(sa / NKS, sa % NKS, (i + PA) % RA);
-                    load_b(sb < NSTEPS ? sb / NKS : KS - 1, sb < NSTEPS ? sb % NKS : 0, (i + 1) & 1);
-                    mfma_step(i % RA, i & 1, decltype(first_tag)::value && i == 0);
-                    pin_step(true);
-                }
-            };
-#endif
             block(0, std::integral_constant<bool, FRESH>{});
 #pragma nounroll
             for (int s0 = UB; s0 < NSTEPS; s0 += UB) block(s0, std::false_type{});
@@ -610,7 +578,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                     for (int e = 0; e < 8; ++e) v[e] = acc[mr][nr][8 * p + e];
                     if (dv != 1.0f) {  // x = xs / num_kernels  (model.py:121)
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = VTTS_MRF_DIV ? v[e] / dv : v[e] * rdv;
+                        for (int e = 0; e < 8; ++e) v[e] = v[e] * rdv;
                     }
                     if (s_out != 1.0f) {  // the (only) consumer's LeakyReLU, applied once by the producer
 #pragma unroll
@@ -698,9 +666,7 @@ static hipError_t launch_g(const BConvArgs& a, hipStream_t s) {
     if (a.dil < 1 || a.dil > T::MAXDIL) return hipErrorInvalidValue;
     constexpr int TS = T::TAIL ? T::NT2 - 2 * T::TAIL_H : T::NT2;
     dim3 grid((a.L + TS - 1) / TS, 1, a.B);
-#if VTTS_XCD_MAP
     if ((int)grid.x >= XCD_MAP_MIN_TILES) grid.x = (grid.x + 7) / 8 * 8;  // whole rounds of the 8 XCDs; a tile index past the utterance exits at once
-#endif
     hipLaunchKernelGGL(resblock_pair_g_bf16_k<T>, grid, dim3(T::THREADS), T::lds_bytes(a.dil) + VTTS_EXP_LDS_PAD, s, a);
     return hipGetLastError();
 }

@@ -30,10 +30,7 @@
 
 #include "bf16_common.h"
 
-#ifndef VTTS_WREG  // register-resident weights (A/B switch)
-#define VTTS_WREG 1
-#endif
-#ifndef VTTS_WREG_RB_MAX  // ... for convolutions of at most this many VGPRs of fragments per lane: 56 = C = 32 at k = 3, 7 (k = 11: 88, spills beside the
+#ifndef VTTS_WREG_RB_MAX  // register-resident weights for convolutions of at most this many VGPRs of fragments per lane: 56 = C = 32 at k = 3, 7 (k = 11: 88, spills beside the
 #define VTTS_WREG_RB_MAX 64  // running x; C = 64, k = 3: 96)
 #endif
 
@@ -61,7 +58,7 @@ struct RBTile {
     static_assert(RA == 4 && (NQT % 4 == 0 || NQT % 4 == 2), "ring of 4; a phase starts at slot 0 or 2");
     // C = 32: a convolution's A operand (NQT * MR fragments, <= 88 VGPRs) is loaded in one burst a phase ahead and the MFMA loops carry
     // no vector-memory instruction (kernels_bf16_rbg.hip: GTile::WREG, same reason)
-    static constexpr bool WREG = VTTS_WREG && NQT * MR * 4 <= VTTS_WREG_RB_MAX;
+    static constexpr bool WREG = NQT * MR * 4 <= VTTS_WREG_RB_MAX;
 };
 
 template <class T>
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         static_assert(THREADS % SPR == 0 && RPI % 16 == 0 && (W * SPR) % THREADS == 0, "a thread's units share their column and their swizzle");
         // lane -> (row, slot) as in resblock_pair_g_bf16_k: blocked tiles (SPR = 4, 8) give 8 consecutive lanes 8 consecutive rows of one slot
         constexpr int RW = 64 / SPR;
-        const int r0 = (SPR >= 16 || !VTTS_TILE_BLOCKED) ? tid / SPR : wave * RW + lane % RW, c = (SPR >= 16 || !VTTS_TILE_BLOCKED) ? tid % SPR : lane / RW;
+        const int r0 = SPR >= 16 ? tid / SPR : wave * RW + lane % RW, c = SPR >= 16 ? tid % SPR : lane / RW;
         unsigned char* const lds0 = tA + tile_off<SPR>(GUARD + r0, c);  // unit i: + i * RPI * P (RPI is a multiple of 16)
         uint4 v[XPT];
         if (tw >= 0 && tw + W <= L) {  // interior window: no clamping, no masking, constant strides
@@ -428,7 +425,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                     }
                     if (dv != 1.0f) {  // x = xs / num_kernels  (model.py:121)
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = VTTS_MRF_DIV ? v[e] / dv : v[e] * rdv;
+                        for (int e = 0; e < 8; ++e) v[e] = v[e] * rdv;
                     }
                     if (s_out != 1.0f) {  // the consumer's LeakyReLU (model.py:112 / :122), applied once by the producer
 #pragma unroll

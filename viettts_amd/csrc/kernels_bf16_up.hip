@@ -22,10 +22,6 @@
 
 #include "bf16_common.h"
 
-#ifndef VTTS_UP_STAGE_OUT  // LDS-staged, row-contiguous output of the two-chunk tiles (A/B switch)
-#define VTTS_UP_STAGE_OUT 1
-#endif
-
 namespace vtts {
 
 // TAPS / HALVES: the transposed convolutions run two taps per chunk, rows of the first half of the chunks on frames (q - 1, q), the others on
@@ -63,7 +59,7 @@ struct UTile {
     // 687 us, 597 vs 455).  Both chunks' packed results fit in registers (64 VGPRs), so they are held until the last chunk is done, go
     // through the — by then dead — input tile in LDS, and leave as whole rows: a wave stores 1 KiB contiguous per instruction.
     static constexpr int SPRO = M / 8;                  // 16-byte slots per OUTPUT row
-    static constexpr bool STAGE_OUT = VTTS_UP_STAGE_OUT && HALVES && NCH == 2 && tile_rows16(N1) * M * 2 <= LDS_BYTES && NCH * MR * NR * 8 <= 64 &&
+    static constexpr bool STAGE_OUT = HALVES && NCH == 2 && tile_rows16(N1) * M * 2 <= LDS_BYTES && NCH * MR * NR * 8 <= 64 &&
                                       (N1 * SPRO) % THREADS == 0;
 };
 

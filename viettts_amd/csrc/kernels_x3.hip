@@ -348,31 +348,16 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
 // half-width tiles with the X tile staged 64 channels at a time (one's staging / epilogues under the other's MFMAs; more halo per output):
 //   C = 128: k = 11  7.45 vs 7.52 ms, k = 7  5.20 vs 5.17, k = 3  3.07 vs 2.90      C = 64: 4.46 vs 4.06, 3.32 vs 3.09, 2.36 vs 2.18
 //   C = 32 : k = 11  3.55 vs 3.20, k = 7  2.80 vs 2.74, k = 3  1.92 vs 2.29           C = 256 (two workgroups do not fit): 3.56 / 2.37 / 1.21
-// The table takes the faster one per class (VTTS_X3_GEOM: 0 = this table, 1 = one workgroup everywhere, 2 = two workgroups wherever they fit).
+// The table takes the faster one per class.
 //                                        C   KS   N1  WM WN  XC  WPS
-#ifndef VTTS_X3_GEOM
-#define VTTS_X3_GEOM 0
-#endif
 template <int KS> using X256 = XTile<256, KS, 128, 4, 2, 128, 2>;
 template <int KS> using X128one = XTile<128, KS, 256, 2, 4, 128, 2>;
 template <int KS> using X128two = XTile<128, KS, 128, 2, 2, 64, 2>;
-template <int KS> using X64one = XTile<64, KS, 512, 1, 8, 64, 2>;
-template <int KS> using X64two = XTile<64, KS, 256, 1, 4, 64, 2>;
+template <int KS> using X64 = XTile<64, KS, 256, 1, 4, 64, 2>;
 template <int KS> using X32one = XTile<32, KS, 512, 1, 8, 32, 2>;
 template <int KS> using X32two = XTile<32, KS, 512, 1, 4, 32, 2>;
-#if VTTS_X3_GEOM == 1
-template <int KS> using X128 = X128one<KS>;
-template <int KS> using X64 = X64one<KS>;
-template <int KS> using X32 = X32one<KS>;
-#elif VTTS_X3_GEOM == 2
-template <int KS> using X128 = X128two<KS>;
-template <int KS> using X64 = X64two<KS>;
-template <int KS> using X32 = X32two<KS>;
-#else
 template <int KS> using X128 = std::conditional_t<KS == 3, X128two<KS>, X128one<KS>>;
-template <int KS> using X64 = X64two<KS>;
 template <int KS> using X32 = std::conditional_t<KS == 3, X32one<KS>, X32two<KS>>;
-#endif
 
 template <class T>
 static hipError_t launch_x3(const PairArgsX3& p, hipStream_t s) {
@@ -440,9 +425,6 @@ hipError_t launch_pair_x3(const ConvArgs& a, const void* w1, const void* w2, con
 // a lane ends up with consecutive output samples of one channel: SH = 4 -> a float4 per group (16 contiguous bytes of y[co][8 q + 4 g ..]),
 // SH = 1 -> a float2 of both groups (y[co][2 q], y[co][2 q + 1]).  fp32 in HBM on both sides, as everything outside the matrix products.
 // =====================================================================================================
-#ifndef VTTS_UX_STAGED
-#define VTTS_UX_STAGED 1
-#endif
 template <int CIN_, int COUT_, int SH_, int N1_, int WM_, int WN_>
 struct UXTile {
     static constexpr int CIN = CIN_, COUT = COUT_, SH = SH_, S = 2 * SH_, N1 = N1_, WM = WM_, WN = WN_;
@@ -455,9 +437,9 @@ struct UXTile {
     static constexpr int PLANE = tile_rows16(ROWS) * P;
     static constexpr int LDS_BYTES = 2 * PLANE;
     static constexpr size_t PLANE_W = (size_t)4 * KSTEPS * MB * 1024;  // bytes of one weight plane: [g][m][ks][mblk][lane][8]
-    // SH = 1: the output rows leave through an fp32 transposition area in the planes' LDS (kernel-development switch VTTS_UX_STAGED, default on)
+    // SH = 1: the output rows leave through an fp32 transposition area in the planes' LDS 
     static constexpr int FS = 2 * N1 + 4;
-    static constexpr bool STAGED = VTTS_UX_STAGED && SH == 1 && (size_t)MT * FS * 4 <= (size_t)LDS_BYTES;
+    static constexpr bool STAGED = SH == 1 && (size_t)MT * FS * 4 <= (size_t)LDS_BYTES;
     static_assert(MPG % MT == 0 && N1 % (WN * 32) == 0 && (SH == 4 || SH == 1) && KSTEPS % 2 == 0, "tiling");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };

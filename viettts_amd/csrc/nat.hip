@@ -248,7 +248,6 @@ static inline float nat_bf16_to_float(unsigned short h) {
 struct vtts_nat_acoustic : NatModel {
     vtts_nat_acoustic_cfg cfg;
     int x3 = 0;  // option "bf16x3": LSTM steps, gate GEMM and postnet as three bf16 x bf16 terms per product on the bf16 matrix pipe
-    int pp_split = 0;  // experiment builds (VTTS_NAT_PP_EXP) only: 1 = the decoder's projection + prenet step cut along its weights (measured slower; see nat_dec_proj_prenet_k)
     // forward_groups(): the postnet of a group of rows runs on `side` as soon as the decoder has produced the group's last frame
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_gates = nullptr;
@@ -1015,11 +1014,7 @@ __global__ __launch_bounds__(64 * KW) void nat_dec_lstm_k(NatLstmOps ops0, NatLs
 }
 
 // (Round 4 built the decoder as ONE resident kernel per run of frames — bit-identical, 26.7 ms against 22.4 with the per-frame launches; the L2s of the 8 XCDs
-//  are not coherent, so every barrier costs the workgroups their cached state — and did not ship it: profiles/r04_e_nat_decoder_findings.md.  The kernel lives in
-//  tools/kbench/experiments/nat_persist_*.inc and is compiled only into experiment builds: --define VTTS_NAT_PERSIST=1.)
-#ifdef VTTS_NAT_PERSIST
-#include "../../tools/kbench/experiments/nat_persist_kernel.inc"
-#endif
+//  are not coherent, so every barrier costs the workgroups their cached state — and did not ship it: profiles/r04_e_nat_decoder_findings.md.)
 
 // ---- the decoder step with the option "bf16x3": the gate sums as three bf16 x bf16 terms per product on the bf16 matrix pipe ----------------
 // The state lives in HBM already split: Zx[parity][hi | lo][row / 8][Bp][8] bf16 (rows [p | h1 | h2]; h = hi + lo to 16 mantissa bits), so that a
@@ -1350,12 +1345,9 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
     // weights in [row / 4][col][4] order (pack-time copies "…#k4"): one 16-byte load per lane = 4 consecutive rows of its
     // column, a wave's loads 1 KiB contiguous — dword loads made the step wait on the number of vector-memory instructions
     // a CU can issue (2 700 per workgroup and frame)
-    auto partial = [&](const float4* __restrict__ src, const float4* __restrict__ w4, int rows, int width, int col, int ch, int per, int phase_bit) {
+    auto partial = [&](const float4* __restrict__ src, const float4* __restrict__ w4, int rows, int width, int col, int ch, int per) {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
         const int k1 = (ch + 1) * per < rows ? (ch + 1) * per : rows;  // per and rows are multiples of 4
-#ifdef VTTS_NAT_PKFMA  // bisect builds only (tools/experiments/r05/pkfma_build.sh): the packed-f32 variants of this loop, wrong by construction beside a bf16 MFMA stream
-#include "../../tools/kbench/experiments/nat_pkfma_partial.inc"
-#endif
 #pragma unroll 4
         for (int k = ch * per; k < k1; k += 4) {
             const float4 wv = w4[(size_t)(k >> 2) * width + col];
@@ -1375,7 +1367,7 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
         return a;
     };
     const int nchP = 1024 / MEL, perP = ((2 * H + nchP - 1) / nchP + 3) / 4 * 4;
-    if (g < nchP * MEL) part[g] = partial(hs, wp, 2 * H, MEL, g % MEL, g / MEL, perP, 1);
+    if (g < nchP * MEL) part[g] = partial(hs, wp, 2 * H, MEL, g % MEL, g / MEL, perP);
     __syncthreads();
     if (g < MEL) {
         const float bb = bb_h;
@@ -1398,11 +1390,11 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
         return make_float4(v[0], v[1], v[2], v[3]);
     };
     const int nchN = 1024 / PN;
-    if (g < nchN * PN) part[g] = partial(prev, f1, MEL, PN, g % PN, g / PN, ((MEL + nchN - 1) / nchN + 3) / 4 * 4, 2);
+    if (g < nchN * PN) part[g] = partial(prev, f1, MEL, PN, g % PN, g / PN, ((MEL + nchN - 1) / nchN + 3) / 4 * 4);
     __syncthreads();
     if (g < PN) p1[g] = masked(gather(make_float4(0.f, 0.f, 0.f, 0.f), PN, g, nchN), 0, g);
     __syncthreads();
-    if (g < nchN * PN) part[g] = partial(p1, f2, PN, PN, g % PN, g / PN, ((PN + nchN - 1) / nchN + 3) / 4 * 4, 4);
+    if (g < nchN * PN) part[g] = partial(p1, f2, PN, PN, g % PN, g / PN, ((PN + nchN - 1) / nchN + 3) / 4 * 4);
     __syncthreads();
     if (g < PN) {
         const float4 r = masked(gather(make_float4(0.f, 0.f, 0.f, 0.f), PN, g, nchN), 1, g);
@@ -1425,10 +1417,7 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
 
 // (Round 6 cut the projection + prenet step along its WEIGHTS — a workgroup = a 32-sentence tile x a slice of a matrix, two launches per frame over 64-workgroup
 //  grids, every load requested before the first wait — and measured it SLOWER: 6.7 + 24.0 us per frame against this kernel's 15.2, the acoustic model 17.0 ms against
-//  12.5 (profiles/r06_c_nat_proj_prenet_findings.md).  The kernels live in tools/kbench/experiments/nat_pp_split_*.inc: --define VTTS_NAT_PP_EXP=1, option "pp_split".)
-#ifdef VTTS_NAT_PP_EXP
-#include "../../tools/kbench/experiments/nat_pp_split_kernels.inc"
-#endif
+//  12.5 (profiles/r06_c_nat_proj_prenet_findings.md).)
 // ---- shared host-side sequence: TokenEncoder of `m` under module prefix `te` -> enc [B][Lmax][2D] ------------------
 // scratch of the two encoder LSTMs: XT[2][Lmax], HS[2][Lmax + 1] slabs of [D][Bp] and the two cell states
 size_t nat_enc_lstm_floats(int D, int B, int Lmax) {
@@ -1737,13 +1726,6 @@ VTTS_API int vtts_nat_acoustic_set_option(vtts_nat_acoustic* h, const char* key,
         h->x3 = value;
         return VTTS_OK;
     }
-#ifdef VTTS_NAT_PP_EXP
-    if (!strcmp(key, "pp_split")) {
-        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "pp_split must be 0 or 1 (got %d)", value);
-        h->pp_split = value;
-        return VTTS_OK;
-    }
-#endif
     return failf(VTTS_ERR_INVALID, "unknown option '%s' (known: bf16x3)", key);
 }
 VTTS_API int vtts_nat_acoustic_get_option(const vtts_nat_acoustic* h, const char* key, int* value) {
@@ -1752,12 +1734,6 @@ VTTS_API int vtts_nat_acoustic_get_option(const vtts_nat_acoustic* h, const char
         *value = h->x3;
         return VTTS_OK;
     }
-#ifdef VTTS_NAT_PP_EXP
-    if (!strcmp(key, "pp_split")) {
-        *value = h->pp_split;
-        return VTTS_OK;
-    }
-#endif
     return failf(VTTS_ERR_INVALID, "unknown option '%s' (known: bf16x3)", key);
 }
 VTTS_API int vtts_nat_acoustic_num_params(const vtts_nat_acoustic* h, int* n) {
@@ -1800,11 +1776,7 @@ VTTS_API int vtts_nat_acoustic_workspace_bytes(const vtts_nat_acoustic* h, int B
              + 2 * align_up((size_t)B * Fmax * PD * 4, 256)                                                // postnet ping-pong
              + align_up(nat_dec_state_floats(h->cfg, B) * 4, 256)                                          // decoder state Z[2], c1, c2
              + 2 * align_up((size_t)B * Fmax * 4 * h->cfg.decoder_dim * 4, 256)                           // hoisted gate pre-activations G1, G2
-             + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256)                                     // encoder LSTMs' scratch
-#ifdef VTTS_NAT_PP_EXP
-             + align_up(nat_pp_part_floats((int)MEL, B) * 4, 256)                                          // the projection's partial sums of a frame
-#endif
-             + 4096;                                                                                       // resident decoder kernel: barrier counters, failure flag
+             + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256);                                    // encoder LSTMs' scratch
     return VTTS_OK;
 }
 VTTS_API int vtts_nat_acoustic_keep_masks(const vtts_nat_acoustic* h, const uint64_t* seeds_dev, int B, int Fmax, uint8_t* keep_dev, void* stream) {
@@ -1836,9 +1808,6 @@ VTTS_API int vtts_nat_acoustic_keep_masks_haiku(const vtts_nat_acoustic* h, uint
                                                 void* stream) {
     return vtts_nat_acoustic_keep_masks_haiku_mode(h, rng_key0, rng_key1, 0, B, Fmax, keep_dev, stream);
 }
-#ifdef VTTS_NAT_PERSIST
-#include "../../tools/kbench/experiments/nat_persist_host.inc"
-#endif
 // forward() and forward_groups(): ngroups = 0 is the plain call (the postnet on the caller's stream after the last frame)
 // enc_pre: the token encoder's output [B][Lmax][2D] computed ahead by vtts_nat_acoustic_encode() (tokens_dev is not read then), or nullptr
 static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
@@ -1896,10 +1865,6 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
     float* G1 = take((size_t)B * Fmax * G4 * 4);
     float* G2 = take((size_t)B * Fmax * G4 * 4);
     float* lstm_ws = take(nat_enc_lstm_floats(D, B, Lmax) * 4);
-#ifdef VTTS_NAT_PP_EXP
-    float4* ppart = reinterpret_cast<float4*>(take(nat_pp_part_floats(MEL, B) * 4));
-#endif
-    unsigned* ctl = reinterpret_cast<unsigned*>(take(4096));
     if (enc_pre) {
         enc = const_cast<float*>(enc_pre);  // read only from here on
     } else {
@@ -1989,12 +1954,6 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
             else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, nframes_dev, f, B, Bp, H);
         };
         const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);
-#ifdef VTTS_NAT_PP_EXP  // the projection + prenet step cut along its weights (round 6 experiment; option "pp_split")
-        const bool pp_split = h->pp_split && nat_pp_split_ok(PN, H, MEL);
-        const dim3 pgridA(NAT_PP_NSL, (B + NAT_PP_TS - 1) / NAT_PP_TS), pgridB(PN / 32, (B + NAT_PP_TS - 1) / NAT_PP_TS);
-        const int pthreadsA = 640;
-        const size_t pldsA = (size_t)128 * 8 * sizeof(float4), pldsB = ((size_t)80 * 8 + (size_t)256 * 8 + 2 * 8 * 32) * sizeof(float4);
-#endif
         auto group_handover = [&](int frames_done) -> int {  // a group whose last frame was frames_done - 1: its postnet starts now, on the side stream
             for (int g = 0; g < ngroups; ++g) {
                 if (group_frames[g] != frames_done) continue;
@@ -2005,10 +1964,6 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
             }
             return VTTS_OK;
         };
-        bool persist = false;
-#ifdef VTTS_NAT_PERSIST
-#include "../../tools/kbench/experiments/nat_persist_launch.inc"
-#endif
         // option "bf16x3": the split-state step (nat_dec_lstm_x3_k) where its 16-row steps divide the row blocks; the state's two parities hold
         // two bf16 planes each (the same bytes as the fp32 rows)
         const bool dx3 = h->x3 && PN % 16 == 0 && H % 16 == 0 && ((PN + H) / 16) % 8 == 0 && ((PN + 2 * H) / 16) % 8 == 0;
@@ -2020,7 +1975,7 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
             if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, nframes_dev, f, B, Bp, H);
             else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, nframes_dev, f, B, Bp, H);
         };
-        for (int f = 0; f < Fmax && !persist; ++f) {
+        for (int f = 0; f < Fmax; ++f) {
             if (f == 64) HIP_TRYN(hipStreamWaitEvent(s, h->ev_gates, 0));
             float* zc = Z[f & 1];
             float* zp = Z[(f + 1) & 1];
@@ -2029,30 +1984,16 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
                 const unsigned short* zpx = reinterpret_cast<const unsigned short*>(zp);
                 lstm_x3(zcx, zpx, PN, PN + H, w1x, G1, c1, PN, f);
                 lstm_x3(zcx, zpx, PN + H, PN + 2 * H, w2x, G2, c2, PN + H, f);
-#ifdef VTTS_NAT_PP_EXP
-                if (pp_split) {
-                    hipLaunchKernelGGL(nat_dec_proj_part_k<true>, pgridA, dim3(pthreadsA), pldsA, s, zc, nframes_dev, wp, ppart, f, B, Bp, PN, H, MEL, zplane);
-                    hipLaunchKernelGGL(nat_dec_prenet_k<true>, pgridB, dim3(512), pldsB, s, zp, nframes_dev, f1, f2, ppart, bp, keep_dev, mel0, f, B, Bp, Fmax, PN, MEL,
-                                       zplane);
-                } else
-#endif
-                    hipLaunchKernelGGL(nat_dec_proj_prenet_k<true>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, nframes_dev, f1, f2, wp, bp, keep_dev, mel0, f,
-                                       B, Bp, Fmax, PN, H, MEL, zplane);
+                hipLaunchKernelGGL(nat_dec_proj_prenet_k<true>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, nframes_dev, f1, f2, wp, bp, keep_dev, mel0, f,
+                                   B, Bp, Fmax, PN, H, MEL, zplane);
                 rc = group_handover(f + 1);
                 if (rc) return rc;
                 continue;
             }
             lstm(zc, PN, zp + (size_t)PN * Bp, w1, G1, c1, zc + (size_t)PN * Bp, f);
             lstm(zc, PN + H, zp + (size_t)(PN + H) * Bp, w2, G2, c2, zc + (size_t)(PN + H) * Bp, f);
-#ifdef VTTS_NAT_PP_EXP
-            if (pp_split) {
-                hipLaunchKernelGGL(nat_dec_proj_part_k<false>, pgridA, dim3(pthreadsA), pldsA, s, zc, nframes_dev, wp, ppart, f, B, Bp, PN, H, MEL, (size_t)0);
-                hipLaunchKernelGGL(nat_dec_prenet_k<false>, pgridB, dim3(512), pldsB, s, zp, nframes_dev, f1, f2, ppart, bp, keep_dev, mel0, f, B, Bp, Fmax, PN, MEL,
-                                   (size_t)0);
-            } else
-#endif
-                hipLaunchKernelGGL(nat_dec_proj_prenet_k<false>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, nframes_dev, f1, f2, wp, bp, keep_dev, mel0, f, B,
-                                   Bp, Fmax, PN, H, MEL, (size_t)0);
+            hipLaunchKernelGGL(nat_dec_proj_prenet_k<false>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, nframes_dev, f1, f2, wp, bp, keep_dev, mel0, f, B,
+                               Bp, Fmax, PN, H, MEL, (size_t)0);
             rc = group_handover(f + 1);  // under the remaining decoder steps
             if (rc) return rc;
         }
