@@ -157,14 +157,19 @@ class Generator:
             raise ValueError("mel must have at least one utterance and one frame")
         return mel.contiguous()
 
+    def _check_out(self, out: Optional[torch.Tensor], shape, what: str) -> torch.Tensor:
+        """``out`` as given, or a new tensor: a contiguous float32 tensor of ``shape`` on this generator's device (``what`` names the shape)."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out.shape != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 {what} tensor on the generator's device")
+        return out
+
     def __call__(self, mel: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Asynchronous on torch's current stream of the device."""
         mel = self._check_mel(mel)
         B, T, _ = mel.shape
-        if out is None:
-            out = torch.empty((B, self.hop * T), dtype=torch.float32, device=self.device)
-        elif out.shape != (B, self.hop * T) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous float32 [B, hop*T] tensor on the generator's device")
+        out = self._check_out(out, (B, self.hop * T), "[B, hop*T]")
         ws = self._workspace(B, T)
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
@@ -190,10 +195,7 @@ class Generator:
             fr = torch.tensor(fr_host, dtype=torch.int32, device=self.device)
         if fr.numel() != B or (fr_host is not None and (min(fr_host) < 1 or max(fr_host) > T)):
             raise ValueError("frames must hold one count per utterance, 1 <= frames[b] <= mel.shape[1]")
-        if out is None:
-            out = torch.empty((B, self.hop * T), dtype=torch.float32, device=self.device)
-        elif out.shape != (B, self.hop * T) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous float32 [B, hop*T] tensor on the generator's device")
+        out = self._check_out(out, (B, self.hop * T), "[B, hop*T]")
         ws = self._workspace(B, T)
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
@@ -225,10 +227,12 @@ class Generator:
             tap_t = tap_t.view(B, -1)
         return out, tap_t
 
-    def run_module(self, key: str, x: torch.Tensor, slope_in: float = 1.0, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def run_module(self, key: str, x: torch.Tensor, slope_in: float = 1.0, res: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run one convolution module (per-layer KATs).
         fp32 handle: ``x`` is ``[B, C, L]`` channel-major (``[B, L, num_mels]`` for conv_pre) -> ``[B, Cout, Lout]``.
-        bf16 handle: everything is channels-last fp32, ``x`` ``[B, L, C]`` -> ``[B, Lout, Cout]`` (``[B, Lout]`` for conv_post)."""
+        bf16 handle: everything is channels-last fp32, ``x`` ``[B, L, C]`` -> ``[B, Lout, Cout]`` (``[B, Lout]`` for conv_post).
+        ``out``: the result tensor to write (checked as in ``__call__``), else a new one."""
         spec = {s.key: s for s in conv_specs(self.cfg)}[key]
         x = x.contiguous()
         channels_last = self.dtype_name == "bf16" or key == "generator/~/conv1_d"
@@ -241,7 +245,7 @@ class Generator:
             shape = (B, lout) if key == "generator/~/conv1_d_1" else (B, lout, spec.cout)
         else:
             shape = (B, spec.cout, lout)
-        y = torch.empty(shape, dtype=torch.float32, device=self.device)
+        y = self._check_out(out, shape, "[" + ", ".join(str(d) for d in shape) + "]")
         if res is not None:
             res = res.contiguous()
         stream = torch.cuda.current_stream(self.device)
@@ -253,16 +257,18 @@ class Generator:
             )
         return y
 
-    def run_pair(self, key_c1: str, x: torch.Tensor) -> torch.Tensor:
+    def run_pair(self, key_c1: str, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One fused ResBlock pair ``x' = convs2_z(lrelu(convs1_z(lrelu(x)))) + x`` named by its first convolution.
         bf16 handles: ``x`` fp32 ``[B, L, C]`` channels-last (rounded to bf16 on the way in) -> same shape;
-        fp32 handles: ``x`` ``[B, C, L]`` channel-major -> same shape."""
+        fp32 handles: ``x`` ``[B, C, L]`` channel-major -> same shape.
+        ``out``: the result tensor to write (checked as in ``__call__``), else a new one.  On a bf16 handle the kernel writes an internal bf16
+        buffer that is then converted into ``out``."""
         x = x.contiguous()
         if self.dtype_name == "bf16":
             B, L, _ = x.shape
         else:
             B, _, L = x.shape
-        y = torch.empty_like(x)
+        y = self._check_out(out, tuple(x.shape), "[" + ", ".join(str(d) for d in x.shape) + "]")
         stream = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib, self.lib.vtts_hifigan_run_pair(self._h, key_c1.encode(), _ptr(x), B, L, _ptr(y), C.c_void_p(stream.cuda_stream)))
