@@ -71,6 +71,30 @@ def test_plan_matches_python_inventory(lib):
     lib.vtts_hifigan_destroy(h)
 
 
+@pytest.mark.parametrize("dtype, elem, chain_bufs", [(_lib.VTTS_F32, 4, 3), (_lib.VTTS_BF16X3, 4, 3), (_lib.VTTS_BF16, 2, 2)])
+def test_workspace_matches_documented_layout(lib, dtype, elem, chain_bufs):
+    # Every buffer holds the widest stage's activation of one micro-batch (V1: 32 channels x 256 T).  A micro-batch slot is
+    # X | T | C | S with the ResBlocks one after the other; with the parallel chains (one small micro-batch) it is
+    # X | S | (T, C[, Y]) per ResBlock: 2 + 3 * num_kernels buffers on fp32 and bf16x3, 2 + 2 * num_kernels on bf16.
+    h = _create(lib, V1, dtype)
+    widest = 32 * 256
+    nk = 3
+
+    def ws(B, T):
+        n = C.c_size_t(0)
+        _lib.check(lib, lib.vtts_hifigan_workspace_bytes(h, B, T, C.byref(n)))
+        return n.value
+
+    assert ws(1, 512) == (2 + chain_bufs * nk) * widest * 512 * elem  # 512 frames: parallel chains
+    assert ws(8, 1024) == 4 * widest * 8 * 1024 * elem  # 8192 frames: one micro-batch, sequential
+    assert ws(64, 1024) == 2 * 4 * widest * 32 * 1024 * elem  # two micro-batches of 32 utterances on two streams
+    _lib.check(lib, lib.vtts_hifigan_set_option(h, b"chains", 2))
+    assert ws(8, 1024) == (2 + chain_bufs * nk) * widest * 8 * 1024 * elem  # chains = 2: every single micro-batch
+    _lib.check(lib, lib.vtts_hifigan_set_option(h, b"chains", 0))
+    assert ws(1, 512) == 4 * widest * 512 * elem
+    lib.vtts_hifigan_destroy(h)
+
+
 def test_error_paths(lib):
     h = _create(lib, TINY)
     # forward before weights are bound

@@ -275,7 +275,7 @@ def test_resblock2_generator_vs_reference_golden(golden_dir, dev):
 
 def test_parallel_resblocks_schedule_is_bit_identical(dev):
     """fp32 engine, small launches: the three ResBlocks of a stage run side by side on parallel streams into separate buffers and
-    are combined afterwards (engine.hip: chains_parallel / mrf_mean_k).  Same additions in the same order as the accumulating
+    are combined afterwards (engine.hip: plan_pass / mrf_mean_k).  Same additions in the same order as the accumulating
     epilogues of the one-after-the-other schedule: the samples must be the same BITS, for ResBlock1 and ResBlock2 generators."""
     from viettts_amd.hifigan.generator import Generator
 

@@ -147,6 +147,30 @@ int conv_same_pad_a(int k, int s) {
     return (s > k - 1) ? (k - 1) : (pad_len + 1) / 2;
 }
 
+// option "profile" times the launches of one kernel class: the ResBlock (C, K) with the most FLOPs per mel frame, over the square
+// convolutions after conv_pre (fp32 engines: those on the MFMA kernel); the first one in execution order wins a tie
+void pick_dominant_class(vtts_hifigan* h, bool mfma_only) {
+    double best_flops = -1.0;
+    for (const Layer& l : h->layers) {
+        if (&l == &h->layers[h->idx_pre] || l.kind != KIND_CONV || l.cin != l.cout || (mfma_only && !l.has_wp)) continue;
+        double fl = 0.0;
+        long len2 = 1;
+        for (auto& m : h->layers) {
+            if (m.kind == KIND_CONVT) len2 *= m.stride;
+            if (m.kind == KIND_CONV && m.cin == l.cin && m.k == l.k && m.cin == m.cout) fl += 2.0 * len2 * m.cin * m.cout * m.k;
+        }
+        if (fl > best_flops) {
+            best_flops = fl;
+            h->prof_C = l.cin;
+            h->prof_K = l.k;
+        }
+    }
+}
+
+bool dominant(const vtts_hifigan* h, const Layer& l) {
+    return l.kind == KIND_CONV && l.cin == h->prof_C && l.cout == h->prof_C && l.k == h->prof_K;
+}
+
 int classify_bf16(const vtts_hifigan* h, const Layer& l, bool is_pre, bool is_post) {
     if (is_post) return (l.cin == 32 && l.cout == 1 && l.k == 7) ? BCLS_NONE - 1 : BCLS_NONE;  // -2 = streaming conv_post
     if (is_pre) return (l.cin <= 128 && l.cin % 8 == 0 && l.cout == 512 && l.k == 7) ? BCLS_PRE : BCLS_NONE;
@@ -169,7 +193,6 @@ int classify_bf16(const vtts_hifigan* h, const Layer& l, bool is_pre, bool is_po
 
 int build_layers_bf16(vtts_hifigan* h) {
     size_t off = 0;
-    double best_flops = -1.0;
     for (auto& l : h->layers) {
         const bool is_pre = (&l == &h->layers[h->idx_pre]), is_post = (&l == &h->layers[h->idx_post]);
         l.bcls = classify_bf16(h, l, is_pre, is_post);
@@ -193,19 +216,6 @@ int build_layers_bf16(vtts_hifigan* h) {
                 l.off_ug = off;
                 off = align_up(off + l.ug_bytes, 256);
             }
-            if (l.kind == KIND_CONV && l.cin == l.cout) {
-                double fl = 0.0;
-                long len2 = 1;
-                for (auto& m : h->layers) {
-                    if (m.kind == KIND_CONVT) len2 *= m.stride;
-                    if (m.kind == KIND_CONV && m.cin == l.cin && m.k == l.k && m.cin == m.cout) fl += 2.0 * len2 * m.cin * m.cout * m.k;
-                }
-                if (fl > best_flops) {
-                    best_flops = fl;
-                    h->prof_C = l.cin;
-                    h->prof_K = l.k;
-                }
-            }
         }
     }
     // (ResBlock2 generators, model.py:54-74, have no fused packings: their two convolutions per block run on the per-convolution kernel)
@@ -215,7 +225,7 @@ int build_layers_bf16(vtts_hifigan* h) {
             const Layer& c2 = h->layers[h->idx_res[r] + 2 * z + 1];
             if (!pair_bf16_supported(c1.cin, c1.k, c1.dil) || c2.dil != 1 || c2.k != c1.k) continue;
             c1.has_pair = true;
-            c1.pw_bytes = 2 * bf16_packed_bytes(pair_pack_geom(c1.cin, c1.k));
+            c1.pw_bytes = 2 * bf16_packed_bytes(pair_g_pack_geom(c1.cin, c1.k));
             c1.off_pw = off;
             off = align_up(off + c1.pw_bytes, 256);
             c1.off_pb = off;
@@ -239,9 +249,10 @@ int build_layers_bf16(vtts_hifigan* h) {
         off = align_up(off + (size_t)6 * c0.cin * sizeof(float), 256);
     }
     h->blob_bytes = off;
+    pick_dominant_class(h, false);
     for (auto& l : h->layers)
-        if (l.kind == KIND_CONV && l.cin == h->prof_C && l.cout == h->prof_C && l.k == h->prof_K) h->prof_name = bf16_kernel_name(l.bcls, l.k);
-    h->prof_name_pair = pair_kernel_name(h->prof_C, h->prof_K);
+        if (dominant(h, l)) h->prof_name = bf16_kernel_name(l.bcls, l.k);
+    h->prof_name_pair = pair_g_kernel_name(h->prof_C, h->prof_K);
     return VTTS_OK;
 }
 
@@ -287,8 +298,7 @@ int build_layers(vtts_hifigan* h) {
             for (int z = 0; z < 3; ++z) {
                 int i1 = add(base + "convs1_" + std::to_string(z), KIND_CONV, cout, cout, c.resblock_kernel_sizes[j],
                              c.resblock_dilation_sizes[j][z], 1);
-                int i2 = add(base + "convs2_" + std::to_string(z), KIND_CONV, cout, cout, c.resblock_kernel_sizes[j], 1, 1);
-                (void)i2;
+                add(base + "convs2_" + std::to_string(z), KIND_CONV, cout, cout, c.resblock_kernel_sizes[j], 1, 1);
                 if (z == 0) first = i1;
             }
             h->idx_res.push_back(first);  // layers first..first+5 = c1_0, c2_0, c1_1, c2_1, c1_2, c2_2
@@ -301,7 +311,6 @@ int build_layers(vtts_hifigan* h) {
 
     // blob layout: per layer plain weights, bias, optional MFMA-packed weights; 256-B aligned
     size_t off = 0;
-    double best_flops = -1.0;
     for (auto& l : h->layers) {
         l.off_w = off;
         off = align_up(off + (size_t)l.k * l.cin * l.cout * sizeof(float), 256);
@@ -313,20 +322,6 @@ int build_layers(vtts_hifigan* h) {
             l.wp_floats = conv1d_f32_mfma_packed_floats(l.cin, l.cout, l.k);
             l.off_wp = off;
             off = align_up(off + l.wp_floats * sizeof(float), 256);
-            if (!is_pre) {
-                // dominant kernel class = the ResBlock (C, K) with the most FLOPs per mel frame
-                double fl = 0.0;
-                long len2 = 1;
-                for (auto& m : h->layers) {
-                    if (m.kind == KIND_CONVT) len2 *= m.stride;
-                    if (m.kind == KIND_CONV && m.cin == l.cin && m.k == l.k && m.cin == m.cout) fl += 2.0 * len2 * m.cin * m.cout * m.k;
-                }
-                if (fl > best_flops) {
-                    best_flops = fl;
-                    h->prof_C = l.cin;
-                    h->prof_K = l.k;
-                }
-            }
         } else if (h->dtype == VTTS_F32 && l.kind == KIND_CONVT &&
                    convT1d_f32_mfma_supported(l.cin, l.cout, l.k, l.stride, l.pad_a, 4)) {
             l.has_wp = true;
@@ -361,6 +356,7 @@ int build_layers(vtts_hifigan* h) {
             }
     }
     h->blob_bytes = off;
+    pick_dominant_class(h, true);
     if (h->prof_C) h->prof_name = conv1d_f32_mfma_kernel_name(h->prof_C, h->prof_K);
     if (h->prof_C && h->x3) {
         char buf[96];
@@ -388,11 +384,37 @@ struct Act {  // channel-major activation view
 // gpurun_out/r03_exp40; the fp32 MFMA kernels take the same flag).  The samples do not depend on the order: utterances are independent.
 int next_zrev(vtts_hifigan* h) { return h->opt_zigzag ? (int)(h->zrev_count++ & 1) : 0; }
 
-// ragged batches on the fp32 / bf16x3 engines (vtts_hifigan_forward_ragged): a layer whose input has L columns per utterance slot learns each
-// utterance's valid columns = frames * (columns per frame) (device_common.h: valid_len)
-void set_ragged(const vtts_hifigan* h, ConvArgs& a, int L) {
+// ragged batches (vtts_hifigan_forward_ragged): a layer whose input has L columns (fp32) / rows (bf16) per utterance slot learns each
+// utterance's valid ones = frames * (columns per frame) (device_common.h: valid_len)
+template <class Args>
+void set_ragged(const vtts_hifigan* h, Args& a, int L) {
     a.lens = h->cur_lens ? h->cur_lens + h->cur_b0 : nullptr;
     a.len_mul = h->cur_lens ? L / h->cur_T : 1;
+}
+
+// Issues one launch of layer l's module (`launch` enqueues it on s) and reports its failure as "<what> for <module> failed".
+// Option "profile": a launch of the dominant class that runs `convs` of its convolutions (0 = not timed) is bracketed by an event pair
+// and credited with their ALGORITHMIC FLOPs (the bf16x3 kernels issue 3x as many bf16 MFMA FLOPs).
+template <class Launch>
+int launch_timed(vtts_hifigan* h, const Layer& l, int convs, int B, int L, hipStream_t s, const char* what, Launch launch) {
+    const bool prof = convs > 0 && h->opt_profile && dominant(h, l);
+    if (prof) {
+        if (h->prof_used == h->prof_events.size()) {
+            hipEvent_t e0, e1;
+            HIP_TRY(hipEventCreate(&e0));
+            HIP_TRY(hipEventCreate(&e1));
+            h->prof_events.emplace_back(e0, e1);
+        }
+        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
+    }
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "%s for %s failed: %s", what, l.key.c_str(), hipGetErrorString(e));
+    if (prof) {
+        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
+        h->prof_used++;
+        h->prof_flops += convs * 2.0 * (double)B * L * l.cin * l.cout * l.k;
+    }
+    return VTTS_OK;
 }
 
 int run_layer(vtts_hifigan* h, const Layer& l, Act x, int B, int L, float slope_in, const float* res, float* y,
@@ -427,63 +449,68 @@ int run_layer(vtts_hifigan* h, const Layer& l, Act x, int B, int L, float slope_
     a.zrev = next_zrev(h);
     set_ragged(h, a, L);
 
-    hipError_t e;
+    hipError_t (*launch)(const ConvArgs&, hipStream_t) = launch_conv1d_generic;
+    int timed = 0;
     const bool ncw = x.st == 1 && x.sc == L && (x.sb % 4) == 0;
     const bool want_mfma = h->opt_kernels == 0 && l.has_wp;
     if (l.kind == KIND_CONVT) {
         if (h->x3 && l.has_x3 && h->opt_kernels == 0 && h->opt_fuse >= 1 && ncw && !res && acc_mode == ACC_STORE) {
             a.wp = h->blob + l.off_x3;  // VTTS_BF16X3: the transposed convolutions on the bf16 matrix pipe with split operands too (kernels_x3.hip)
-            e = launch_convt_x3(a, s);
+            launch = launch_convt_x3;
         } else if (want_mfma && ncw && !res && acc_mode == ACC_STORE && convT1d_f32_mfma_supported(l.cin, l.cout, l.k, l.stride, l.pad_a, L))
-            e = launch_convT1d_f32_mfma(a, s);
+            launch = launch_convT1d_f32_mfma;
         else
-            e = launch_convT1d_generic(a, s);
+            launch = launch_convT1d_generic;
     } else if (tanh_out) {
         if (h->opt_kernels == 0 && ncw && !res && acc_mode == ACC_STORE && conv_post_fast_supported(l.cin, l.cout, l.k, L))
-            e = launch_conv_post_fast(a, s);
-        else
-            e = launch_conv1d_generic(a, s);
+            launch = launch_conv_post_fast;
     } else {
         const bool nwc = x.sc == 1 && x.st == l.cin;
         if (h->x3 && l.has_x3 && nwc && h->opt_kernels == 0 && h->opt_fuse >= 1 && !res && acc_mode == ACC_STORE && &l == &h->layers[h->idx_pre] &&
             (reinterpret_cast<uintptr_t>(x.p) & 15) == 0) {  // (float4 row loads: a mel pointer that is not 16-byte aligned takes the fp32 kernel)
             a.wp = h->blob + l.off_x3;  // VTTS_BF16X3: conv_pre with split operands (kernels_x3.hip: conv_pre_x3_k)
-            const hipError_t ex = launch_conv_pre_x3(a, s);
-            if (ex != hipSuccess) return fail(VTTS_ERR_HIP, "kernel launch for %s failed: %s", l.key.c_str(), hipGetErrorString(ex));
-            return VTTS_OK;
-        }
-        const bool mfma = want_mfma && (ncw || nwc) && conv1d_f32_mfma_supported(l.cin, l.cout, l.k, l.dil, L, nwc);
-        if (mfma) {
-            const bool prof = h->opt_profile && l.cin == h->prof_C && l.cout == h->prof_C && l.k == h->prof_K;
-            if (prof) {
-                if (h->prof_used == h->prof_events.size()) {
-                    hipEvent_t e0, e1;
-                    HIP_TRY(hipEventCreate(&e0));
-                    HIP_TRY(hipEventCreate(&e1));
-                    h->prof_events.emplace_back(e0, e1);
-                }
-                HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
-            }
-            e = launch_conv1d_f32_mfma(a, s);
-            if (prof) {
-                HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
-                h->prof_used++;
-                h->prof_flops += 2.0 * (double)B * L * l.cin * l.cout * l.k;
-            }
-        } else {
-            e = launch_conv1d_generic(a, s);
+            launch = launch_conv_pre_x3;
+        } else if (want_mfma && (ncw || nwc) && conv1d_f32_mfma_supported(l.cin, l.cout, l.k, l.dil, L, nwc)) {
+            launch = launch_conv1d_f32_mfma;
+            timed = 1;
         }
     }
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "kernel launch for %s failed: %s", l.key.c_str(), hipGetErrorString(e));
-    return VTTS_OK;
+    return launch_timed(h, l, timed, B, L, s, "kernel launch", [&] { return launch(a, s); });
 }
 
+// ---- ResBlock routes of the fp32 / bf16x3 engine --------------------------------------------------
+// the fields every ResBlock launch shares: x [B][C][L] channel-major (rb[0]'s C and K) -> y with the MRF accumulate mode
+ConvArgs resblock_args(vtts_hifigan* h, const Layer& c1, const float* x, int B, int L, float* y, int acc_mode, float div) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x;
+    a.x_sb = (long)c1.cin * L;
+    a.x_sc = L;
+    a.x_st = 1;
+    a.y = y;
+    a.B = B;
+    a.Cin = c1.cin;
+    a.Cout = c1.cin;
+    a.K = c1.k;
+    a.stride = 1;
+    a.L = L;
+    a.Lout = L;
+    a.slope_in = 0.1f;  // LRELU_SLOPE, both activations of every pair (model.py:46,48)
+    a.acc_mode = acc_mode;
+    a.div = div;
+    a.zrev = next_zrev(h);
+    set_ragged(h, a, L);
+    return a;
+}
 
-// fp32 fused pair: c1 = convs1_z (rate d), c2 = convs2_z (rate 1): x [B][C][L] -> out, with the accumulate mode of the unfused c2 launch
+// fp32 fused pair: c1 = convs1_z (rate d), c2 = convs2_z (rate 1) in one kernel (kernels_f32_pair.hip)
+bool pair_f32_fusable(const Layer& c1, const Layer& c2, int L) {
+    return c1.has_wp && c2.has_wp && c1.cin == c1.cout && c2.cin == c1.cin && c2.cout == c1.cin && c2.k == c1.k && c2.dil == 1 &&
+           pair_f32_supported(c1.cin, c1.k, c1.dil, L);
+}
+
 bool pair_f32_wanted(const vtts_hifigan* h, const Layer& c1, const Layer& c2, int L) {
-    if (h->opt_kernels != 0 || h->opt_fuse < 1 || !c1.has_wp || !c2.has_wp) return false;
-    if (c1.cin != c1.cout || c2.cin != c1.cin || c2.cout != c1.cin || c2.k != c1.k || c2.dil != 1) return false;
-    if (!pair_f32_supported(c1.cin, c1.k, c1.dil, L)) return false;
+    if (h->opt_kernels != 0 || h->opt_fuse < 1 || !pair_f32_fusable(c1, c2, L)) return false;
     // Where the fused pair measured faster than the two launches it replaces (64 x 1024 frames, rocprofv3 per launch, gpurun_out/r04_run3):
     // C = 32: k = 3 / 7 / 11  -16 / -17 / -20 %;  C = 64: -13 / -6 / +-0 %;  C = 128: k = 3 -10 %, k = 7 -1 %, k = 11 +4.5 % (a fused pair
     // recomputes KS - 1 of every 128 columns and holds 78 KB of LDS: at C = 128, k = 11 that costs more than the saved traffic gains).
@@ -491,99 +518,10 @@ bool pair_f32_wanted(const vtts_hifigan* h, const Layer& c1, const Layer& c2, in
     return c1.cin <= 64 || (h->opt_fuse >= 2 && c1.cin == 128 && c1.k == 3) || h->opt_fuse >= 3;
 }
 
-int run_pair_f32(vtts_hifigan* h, const Layer& c1, const Layer& c2, const float* x, int B, int L, float* y, int acc_mode, float div, hipStream_t s) {
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.x_sb = (long)c1.cin * L;
-    a.x_sc = L;
-    a.x_st = 1;
-    a.wp = h->blob + c1.off_wp;
-    a.bias = reinterpret_cast<const float*>(h->blob + c1.off_b);
-    a.res = x;  // x = xt + x (model.py:50)
-    a.y = y;
-    a.B = B;
-    a.Cin = c1.cin;
-    a.Cout = c1.cout;
-    a.K = c1.k;
-    a.dil = c1.dil;
-    a.pad = c1.pad;
-    a.stride = 1;
-    a.L = L;
-    a.Lout = L;
-    a.slope_in = 0.1f;  // LRELU_SLOPE, both activations of the pair (model.py:46,48)
-    a.acc_mode = acc_mode;
-    a.div = div;
-    a.zrev = next_zrev(h);
-    set_ragged(h, a, L);
-    const bool prof = h->opt_profile && c1.cin == h->prof_C && c1.k == h->prof_K;  // (fuse = 3: the dominant class runs here)
-    if (prof) {
-        if (h->prof_used == h->prof_events.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            h->prof_events.emplace_back(e0, e1);
-        }
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
-    }
-    hipError_t e = launch_pair_f32(a, h->blob + c2.off_wp, reinterpret_cast<const float*>(h->blob + c2.off_b), s);
-    if (prof) {
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
-        h->prof_used++;
-        h->prof_flops += 2.0 * 2.0 * (double)B * L * c1.cin * c1.cout * c1.k;  // two convolutions
-    }
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "fused fp32 pair launch for %s failed: %s", c1.key.c_str(), hipGetErrorString(e));
-    return VTTS_OK;
-}
-
 // VTTS_BF16X3: the same pair on the bf16 matrix pipe with split operands (kernels_x3.hip); same buffers, same accumulate modes
 bool pair_x3_wanted(const vtts_hifigan* h, const Layer& c1, const Layer& c2, int L) {
     return h->x3 && h->opt_kernels == 0 && h->opt_fuse >= 1 && c1.has_x3 && c2.has_x3 && c2.k == c1.k && c2.dil == 1 && c2.cin == c1.cin &&
            pair_x3_supported(c1.cin, c1.k, c1.dil, L);
-}
-
-int run_pair_x3(vtts_hifigan* h, const Layer& c1, const Layer& c2, const float* x, int B, int L, float* y, int acc_mode, float div, hipStream_t s) {
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.x_sb = (long)c1.cin * L;
-    a.x_sc = L;
-    a.x_st = 1;
-    a.bias = reinterpret_cast<const float*>(h->blob + c1.off_b);
-    a.res = x;
-    a.y = y;
-    a.B = B;
-    a.Cin = c1.cin;
-    a.Cout = c1.cout;
-    a.K = c1.k;
-    a.dil = c1.dil;
-    a.pad = c1.pad;
-    a.stride = 1;
-    a.L = L;
-    a.Lout = L;
-    a.slope_in = 0.1f;
-    a.acc_mode = acc_mode;
-    a.div = div;
-    a.zrev = next_zrev(h);
-    set_ragged(h, a, L);
-    const bool prof = h->opt_profile && c1.cin == h->prof_C && c1.k == h->prof_K;
-    if (prof) {
-        if (h->prof_used == h->prof_events.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            h->prof_events.emplace_back(e0, e1);
-        }
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
-    }
-    hipError_t e = launch_pair_x3(a, h->blob + c1.off_x3, h->blob + c2.off_x3, reinterpret_cast<const float*>(h->blob + c2.off_b), s);
-    if (prof) {
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
-        h->prof_used++;
-        h->prof_flops += 2.0 * 2.0 * (double)B * L * c1.cin * c1.cout * c1.k;  // ALGORITHMIC flops of the two convolutions (the kernel issues 3x as many bf16 MFMA flops)
-    }
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "split-operand pair launch for %s failed: %s", c1.key.c_str(), hipGetErrorString(e));
-    return VTTS_OK;
 }
 
 // VTTS_BF16X3: a whole ResBlock1 (three pairs + the MRF bookkeeping) in one launch where the kernel exists and is the faster choice
@@ -597,26 +535,34 @@ bool resblock_x3_wanted(const vtts_hifigan* h, const Layer* rb, int L) {
     return h->opt_fuse >= 3 || resblock_x3_preferred(rb[0].cin, rb[0].k);
 }
 
+// how a ResBlock1's six convolutions (rb[0..5] = c1_0, c2_0, c1_1, c2_1, c1_2, c2_2) are launched; all routes give the same bits
+enum Route { ROUTE_CONVS, ROUTE_PAIRS, ROUTE_RESBLOCK, ROUTE_X3_PAIRS, ROUTE_X3_RESBLOCK };
+
+Route route_f32(const vtts_hifigan* h, const Layer* rb, int L) {
+    if (resblock_x3_wanted(h, rb, L)) return ROUTE_X3_RESBLOCK;
+    if (pair_x3_wanted(h, rb[0], rb[1], L) && pair_x3_wanted(h, rb[2], rb[3], L) && pair_x3_wanted(h, rb[4], rb[5], L)) return ROUTE_X3_PAIRS;
+    if (pair_f32_wanted(h, rb[0], rb[1], L) && pair_f32_wanted(h, rb[2], rb[3], L) && pair_f32_wanted(h, rb[4], rb[5], L)) return ROUTE_PAIRS;
+    return ROUTE_CONVS;
+}
+
+// one fused pair x' = c2(lrelu(c1(lrelu(x)))) + x on the fp32 kernel or (x3) the split-operand one
+int run_pair_f32(vtts_hifigan* h, const Layer& c1, const Layer& c2, bool x3, const float* x, int B, int L, float* y, int acc_mode, float div,
+                 hipStream_t s) {
+    ConvArgs a = resblock_args(h, c1, x, B, L, y, acc_mode, div);
+    a.bias = reinterpret_cast<const float*>(h->blob + c1.off_b);
+    a.res = x;  // x = xt + x (model.py:50)
+    a.dil = c1.dil;
+    a.pad = c1.pad;
+    const float* bias2 = reinterpret_cast<const float*>(h->blob + c2.off_b);
+    if (x3)
+        return launch_timed(h, c1, 2, B, L, s, "split-operand pair launch",
+                            [&] { return launch_pair_x3(a, h->blob + c1.off_x3, h->blob + c2.off_x3, bias2, s); });
+    a.wp = h->blob + c1.off_wp;
+    return launch_timed(h, c1, 2, B, L, s, "fused fp32 pair launch", [&] { return launch_pair_f32(a, h->blob + c2.off_wp, bias2, s); });
+}
+
 int run_resblock_x3(vtts_hifigan* h, const Layer* rb, const float* x, int B, int L, float* y, int acc_mode, float div, hipStream_t s) {
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.x_sb = (long)rb[0].cin * L;
-    a.x_sc = L;
-    a.x_st = 1;
-    a.y = y;
-    a.B = B;
-    a.Cin = rb[0].cin;
-    a.Cout = rb[0].cin;
-    a.K = rb[0].k;
-    a.stride = 1;
-    a.L = L;
-    a.Lout = L;
-    a.slope_in = 0.1f;  // LRELU_SLOPE (model.py:46,48)
-    a.acc_mode = acc_mode;
-    a.div = div;
-    a.zrev = next_zrev(h);
-    set_ragged(h, a, L);
+    const ConvArgs a = resblock_args(h, rb[0], x, B, L, y, acc_mode, div);
     const int dils[3] = {rb[0].dil, rb[2].dil, rb[4].dil};
     const void* w[6];
     const float* bias[6];
@@ -624,34 +570,11 @@ int run_resblock_x3(vtts_hifigan* h, const Layer* rb, const float* x, int B, int
         w[q] = h->blob + rb[q].off_x3;
         bias[q] = reinterpret_cast<const float*>(h->blob + rb[q].off_b);
     }
-    // option "profile": a class the whole-ResBlock kernel serves is bracketed like the pair launches it replaces (six convolutions per launch)
-    const bool prof = h->opt_profile && rb[0].cin == h->prof_C && rb[0].k == h->prof_K;
-    if (prof) {
-        if (h->prof_used == h->prof_events.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            h->prof_events.emplace_back(e0, e1);
-        }
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
-    }
-    hipError_t e = launch_resblock_x3(a, dils, w, bias, s);
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "split-operand ResBlock launch for %s failed: %s", rb[0].key.c_str(), hipGetErrorString(e));
-    if (prof) {
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
-        h->prof_used++;
-        h->prof_flops += 6 * 2.0 * (double)B * L * rb[0].cin * rb[0].cin * rb[0].k;
-    }
-    return VTTS_OK;
+    // timed like the pair launches it replaces (six convolutions per launch)
+    return launch_timed(h, rb[0], 6, B, L, s, "split-operand ResBlock launch", [&] { return launch_resblock_x3(a, dils, w, bias, s); });
 }
 
 // ---- bf16 path -------------------------------------------------------------------------------------
-// ragged batches (vtts_hifigan_forward_ragged): every layer learns each utterance's valid rows = frames * (rows per frame)
-void set_ragged(const vtts_hifigan* h, BConvArgs& a, int L) {
-    a.lens = h->cur_lens ? h->cur_lens + h->cur_b0 : nullptr;
-    a.len_mul = h->cur_lens ? L / h->cur_T : 1;
-}
-
 int run_layer_bf16(vtts_hifigan* h, const Layer& l, const void* x, int x_pitch, int cin_real, int B, int L, float slope_in,
                    float slope_out, const void* res, void* y, int acc_add, float div, hipStream_t s) {
     BConvArgs a;
@@ -674,16 +597,6 @@ int run_layer_bf16(vtts_hifigan* h, const Layer& l, const void* x, int x_pitch, 
     a.acc_add = acc_add;
     a.div = div;
     const int K = (l.kind == KIND_CONVT) ? 3 : l.k;
-    const bool prof = h->opt_profile && l.kind == KIND_CONV && l.cin == h->prof_C && l.cout == h->prof_C && l.k == h->prof_K;
-    if (prof) {
-        if (h->prof_used == h->prof_events.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            h->prof_events.emplace_back(e0, e1);
-        }
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
-    }
     // transposed convolutions: the register-streamed kernel (fuse >= 1), else the first-generation 3-tap convolution.  Per launch at B = 64 x
     // T = 1024 (rocprofv3): ups_0 305 vs 422 us, ups_1 551 vs 985; ups_2 529 vs 688 and ups_3 422 vs 453 since round 3, when the two
     // HBM-bound ones (128 -> 2 x 64, 64 -> 2 x 32) got an LDS-staged epilogue that stores whole rows (round 2: 684 / 597 us with 32-byte
@@ -692,95 +605,77 @@ int run_layer_bf16(vtts_hifigan* h, const Layer& l, const void* x, int x_pitch, 
     const bool ug = (l.kind == KIND_CONVT || l.bcls == BCLS_PRE) && l.has_ug && h->opt_fuse >= 1 && res == nullptr && acc_add == 0 && div == 1.0f;
     if (ug) a.wp = h->blob + l.off_ug;
     if (ug) a.zrev = next_zrev(h);
-    hipError_t e = ug ? launch_convt_g_bf16(l.bcls, a, s) : launch_conv_bf16(l.bcls, K, a, s);
-    if (prof) {
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
-        h->prof_used++;
-        h->prof_flops += 2.0 * (double)B * L * l.cin * l.cout * l.k;
-    }
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "bf16 kernel launch for %s failed: %s", l.key.c_str(), hipGetErrorString(e));
-    return VTTS_OK;
+    return launch_timed(h, l, 1, B, L, s, "bf16 kernel launch",
+                        [&] { return ug ? launch_convt_g_bf16(l.bcls, a, s) : launch_conv_bf16(l.bcls, K, a, s); });
 }
 
-int run_pair_bf16(vtts_hifigan* h, const Layer& c1, const void* x, int B, int L, float slope_out, void* y, int acc_add, float div,
-                  hipStream_t s, float* tail_wav = nullptr) {
+// the fields every ResBlock launch of the bf16 engine shares: x [B][L][C] channels-last (rb[0]'s C) -> y, the consumer's activation
+// and the MRF accumulate / mean in the epilogue
+BConvArgs resblock_args_bf16(vtts_hifigan* h, const Layer& c1, const void* x, int B, int L, float slope_out, void* y, int acc_add, float div) {
     BConvArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x;
-    a.wp = h->blob + c1.off_pw;
-    a.bias = reinterpret_cast<const float*>(h->blob + c1.off_pb);
     a.y = y;
     a.B = B;
     a.L = L;
     set_ragged(h, a, L);
     a.x_pitch = c1.cin;
     a.cin_real = c1.cin;
-    a.dil = c1.dil;
-    a.pad = c1.pad;
     a.slope_in = 0.1f;
     a.slope_out = slope_out;
     a.acc_add = acc_add;
     a.div = div;
-    a.tile_pref = (int)h->opt_tiles;
     a.zrev = next_zrev(h);
+    return a;
+}
+
+int run_pair_bf16(vtts_hifigan* h, const Layer& c1, const void* x, int B, int L, float slope_out, void* y, int acc_add, float div,
+                  hipStream_t s, float* tail_wav = nullptr) {
+    BConvArgs a = resblock_args_bf16(h, c1, x, B, L, slope_out, y, acc_add, div);
+    a.wp = h->blob + c1.off_pw;
+    a.bias = reinterpret_cast<const float*>(h->blob + c1.off_pb);
+    a.dil = c1.dil;
+    a.pad = c1.pad;
+    a.tile_pref = (int)h->opt_tiles;
     if (tail_wav) {  // the stage-4 tail rides on this launch: conv_post + tanh from the rows this pair produces (kernels_bf16_rbg.hip: GTail)
         const Layer& post = h->layers[h->idx_post];
         a.tail_wav = tail_wav;
         a.tail_wf = reinterpret_cast<const float*>(h->blob + post.off_w);
         a.tail_bias = reinterpret_cast<const float*>(h->blob + post.off_b);
     }
-    const bool prof = h->opt_profile && c1.cin == h->prof_C && c1.k == h->prof_K;
-    if (prof) {
-        if (h->prof_used == h->prof_events.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            h->prof_events.emplace_back(e0, e1);
-        }
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
-    }
-    hipError_t e = launch_pair_bf16(c1.cin, c1.k, a, s);
-    if (prof) {
-        HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
-        h->prof_used++;
-        h->prof_flops += 2.0 * 2.0 * (double)B * L * c1.cin * c1.cout * c1.k;  // two convolutions
-    }
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "fused pair launch for %s failed: %s", c1.key.c_str(), hipGetErrorString(e));
-    return VTTS_OK;
+    return launch_timed(h, c1, 2, B, L, s, "fused pair launch", [&] { return launch_pair_g_bf16(c1.cin, c1.k, a, s); });
 }
 
 int run_resblock_bf16(vtts_hifigan* h, const Layer* rb, const void* x, int B, int L, float slope_out, void* y, int acc_add, float div,
-                        hipStream_t s) {
-    BConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
+                      hipStream_t s) {
+    BConvArgs a = resblock_args_bf16(h, rb[0], x, B, L, slope_out, y, acc_add, div);
     a.wp = h->blob + rb[0].off_rw;
     a.bias = reinterpret_cast<const float*>(h->blob + rb[0].off_rb);
-    a.y = y;
-    a.B = B;
-    a.L = L;
-    set_ragged(h, a, L);
-    a.x_pitch = rb[0].cin;
-    a.cin_real = rb[0].cin;
     a.dils[0] = rb[0].dil;
     a.dils[1] = rb[2].dil;
     a.dils[2] = rb[4].dil;
-    a.slope_in = 0.1f;
-    a.slope_out = slope_out;
-    a.acc_add = acc_add;
-    a.div = div;
-    a.zrev = next_zrev(h);
-    hipError_t e = launch_resblock_bf16(rb[0].cin, rb[0].k, a, s);
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "fused ResBlock launch for %s failed: %s", rb[0].key.c_str(), hipGetErrorString(e));
-    return VTTS_OK;
+    return launch_timed(h, rb[0], 0, B, L, s, "fused ResBlock launch", [&] { return launch_resblock_bf16(rb[0].cin, rb[0].k, a, s); });
 }
 
-struct Taps;
-int tap_copy_bf16(const void* src, float* dst, size_t n, hipStream_t s) {
-    hipError_t e = launch_bf16_to_f32(src, dst, n, s);
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "tap conversion failed: %s", hipGetErrorString(e));
-    return VTTS_OK;
+Route route_bf16(const vtts_hifigan* h, const Layer* rb) {
+    // the whole-ResBlock kernel where it exists and is the faster choice (fuse = 3: wherever it exists)
+    if (h->opt_fuse >= 2 && rb[0].has_rb && (h->opt_fuse >= 3 || resblock_bf16_preferred(rb[0].cin, rb[0].k))) return ROUTE_RESBLOCK;
+    if (h->opt_fuse >= 1 && rb[0].has_pair && rb[2].has_pair && rb[4].has_pair) return ROUTE_PAIRS;
+    return ROUTE_CONVS;
 }
+
+// the stage-4 tail (option "tail", default on): the generator's last pair launch also runs conv_post + tanh on its own rows, so the stage
+// output is never written and conv_post_bf16_k is not launched.  Where the last ResBlock runs as pairs and its last pair can carry it (V1:
+// C = 32, k = 11); the caller also requires that nothing needs the stage output itself (no tap)
+bool tail_fused_bf16(const vtts_hifigan* h) {
+    if (!h->opt_tail || h->cfg.resblock == 2) return false;
+    const Layer* rb = &h->layers[h->idx_res.back()];
+    const Layer& post = h->layers[h->idx_post];
+    return route_bf16(h, rb) == ROUTE_PAIRS && pair_tail_bf16_supported(rb[0].cin, rb[0].k, post.cin, post.cout, post.k);
+}
+
+// ---- the pass plan: micro-batches, streams, workspace -------------------------------------------------------
+size_t elem_bytes(const vtts_hifigan* h) { return h->dtype == VTTS_BF16 ? 2 : sizeof(float); }
 
 size_t max_act_elems(const vtts_hifigan* h, int T) {
     // largest [C][L] activation per utterance over all stages (8192*T for V1)
@@ -833,57 +728,70 @@ int pick_microbatch(const vtts_hifigan* h, int B, int T) {
 // blockIdx.z: a longer utterance goes through the chunk scheduler (viettts_amd/longform.py: 13-frame halo), a larger batch in
 // several calls.
 int check_pass_size(const vtts_hifigan* h, int B, int T) {
-    const size_t es = h->dtype == VTTS_BF16 ? 2 : sizeof(float);
-    if (max_act_elems(h, T) * es >= ((size_t)1 << 31))
+    const size_t bytes = max_act_elems(h, T) * elem_bytes(h);
+    if (bytes >= ((size_t)1 << 31))
         return fail(VTTS_ERR_INVALID, "T=%d frames is too long for one pass (%zu activation bytes per utterance, limit 2^31): synthesize it in chunks",
-                    T, max_act_elems(h, T) * es);
+                    T, bytes);
     if (pick_microbatch(h, B, T) > 65535) return fail(VTTS_ERR_INVALID, "at most 65535 utterances per pass (got %d)", B);
     return VTTS_OK;
 }
 
-// x = (rb_0(x) + rb_1(x) [+ rb_2(x)]) / num_kernels with the ResBlocks' outputs in separate buffers (model.py:115-121): the same
-// additions in the same order as the ACC_STORE / ACC_ADD / ACC_MEAN epilogues (device_common.h), hence the same bits.
-__global__ __launch_bounds__(256) void mrf_mean_k(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ y2,
-                                                  float* __restrict__ out, size_t n, float div) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        float v = y0[i] + y1[i];
-        if (y2) v = v + y2[i];
-        out[i] = v / div;
-    }
-}
-
 // A single small micro-batch leaves most of the chip idle (B = 1 x T = 512: 256 workgroups of 4 waves in stage 1), and the MRF's
-// ResBlocks of a stage are independent given the stage input: the fp32 engine then runs them on parallel streams into separate
-// buffers and combines them with mrf_mean_k (3 forwards in flight measured 2.2x the time of one: 1.36x the throughput).
+// ResBlocks of a stage are independent given the stage input: they then run on parallel streams (3 forwards in flight measured 2.2x the
+// time of one: 1.36x the throughput).
 constexpr int PAR_CHAIN_FRAMES = 2048;
-bool chains_parallel(const vtts_hifigan* h, int B, int T) {
-    const int nk = h->cfg.num_kernels;
-    if (!h->opt_chains || ((long)B * T > PAR_CHAIN_FRAMES && h->opt_chains != 2) || pick_microbatch(h, B, T) < B) return false;
-    return h->dtype == VTTS_F32 ? (nk == 2 || nk == 3) : (nk == 3 && h->cfg.resblock != 2);
-}
-// workspace buffers of one pass: [X | S | per ResBlock: T, C (, Y: the fp32 engine's separate output)] or the sequential schedule's X, T, C, S
-int pass_buffers(const vtts_hifigan* h, int B, int T) {
-    if (!chains_parallel(h, B, T)) return 4;
-    return 2 + (h->dtype == VTTS_F32 ? 3 : 2) * h->cfg.num_kernels;
-}
 
-struct Taps {
-    const char* name = nullptr;
-    float* out = nullptr;
-    int Bfull = 0;
+// one micro-batch's buffers: X the stage input (ups output), S the MRF accumulator / stage output; ResBlock j's scratch T[j] (xt inside a
+// pair), C[j] (the running x inside the ResBlock) and, fp32 parallel chains only, Y[j] (its separate output)
+struct PassBufs {
+    char *X = nullptr, *S = nullptr;
+    char *T[VTTS_MAX_KERNELS] = {}, *C[VTTS_MAX_KERNELS] = {}, *Y[VTTS_MAX_KERNELS] = {};
 };
 
+// How a forward of B x T frames runs: micro-batches of mb utterances rotate over nstr streams, each in a workspace slot of its own.
+// A slot holds nbuf buffers of `per` bytes (the widest stage's [C][L] activation of mb utterances):
+//   ResBlocks one after the other: X | T | C | S (every ResBlock uses the same T, C)
+//   parallel chains (one micro-batch, one slot): X | S | (T, C[, Y]) per ResBlock — fp32 / bf16x3: 2 + 3 * num_kernels, bf16: 2 + 2 * num_kernels
+struct PassPlan {
+    int mb = 1, nstr = 1, nbuf = 4;
+    size_t es = 0, per = 0;
+    bool par = false;
+    int chain_bufs = 0;  // buffers per parallel chain
 
+    size_t bytes() const { return (size_t)nstr * nbuf * per; }
+    PassBufs buffers(void* ws, int si, int nk) const {
+        char* slot = static_cast<char*>(ws) + (size_t)si * nbuf * per;
+        auto at = [&](int q) { return slot + (size_t)q * per; };
+        PassBufs b;
+        b.X = at(0);
+        b.S = at(par ? 1 : 3);
+        for (int j = 0; j < nk; ++j) {
+            b.T[j] = par ? at(2 + chain_bufs * j) : at(1);
+            b.C[j] = par ? at(3 + chain_bufs * j) : at(2);
+            if (par && chain_bufs == 3) b.Y[j] = at(4 + 3 * j);
+        }
+        return b;
+    }
+};
 
-// Micro-batches are independent, so consecutive ones may run on different HIP streams: workgroups of
-// one micro-batch in an HBM phase (tile staging / epilogue) then share the CUs with workgroups of
-// another in its MFMA phase instead of every workgroup on the chip hitting HBM at the same time.
-int num_streams(const vtts_hifigan* h, int B, int T) {
-    const int mb = pick_microbatch(h, B, T);
-    const int nmb = (B + mb - 1) / mb;
-    int n = auto_streams(h);
-    if (n > nmb) n = nmb;
-    return n < 1 ? 1 : n;
+PassPlan plan_pass(const vtts_hifigan* h, int B, int T) {
+    PassPlan p;
+    p.mb = pick_microbatch(h, B, T);
+    // Micro-batches are independent, so consecutive ones may run on different HIP streams: workgroups of
+    // one micro-batch in an HBM phase (tile staging / epilogue) then share the CUs with workgroups of
+    // another in its MFMA phase instead of every workgroup on the chip hitting HBM at the same time.
+    const int nmb = (B + p.mb - 1) / p.mb;
+    p.nstr = std::max(1, std::min(auto_streams(h), nmb));
+    p.es = elem_bytes(h);
+    p.per = align_up(max_act_elems(h, T) * (size_t)p.mb * p.es, 256);
+    const int nk = h->cfg.num_kernels;
+    if (h->opt_chains && ((long)B * T <= PAR_CHAIN_FRAMES || h->opt_chains == 2) && p.mb >= B)
+        p.par = h->dtype == VTTS_F32 ? (nk == 2 || nk == 3) : (nk == 3 && h->cfg.resblock != 2);
+    if (p.par) {
+        p.chain_bufs = h->dtype == VTTS_F32 ? 3 : 2;
+        p.nbuf = 2 + p.chain_bufs * nk;
+    }
+    return p;
 }
 
 int fork_streams(vtts_hifigan* h, int n, hipStream_t s, hipStream_t* out) {
@@ -912,332 +820,288 @@ int join_streams(vtts_hifigan* h, int n, hipStream_t s) {
     return VTTS_OK;
 }
 
-// bf16 schedule.  Same dataflow as the fp32 one, with two differences that only bf16 needs:
+// runs chain(j, stream) for the nk ResBlocks of a stage on streams forked from s.  The streams are joined back into s whatever
+// happens: during a graph capture an un-joined fork invalidates the capture
+template <class Chain>
+int run_chains_parallel(vtts_hifigan* h, int nk, hipStream_t s, Chain chain) {
+    hipStream_t cs[4];
+    int rc = fork_streams(h, nk, s, cs);
+    for (int j = 0; j < nk && !rc; ++j) rc = chain(j, cs[j]);
+    const int rj = join_streams(h, nk, s);
+    return rc ? rc : rj;
+}
+
+// ---- the forward: one frame, each engine's steps -------------------------------------------------------------
+struct Taps {
+    const char* name = nullptr;
+    float* out = nullptr;
+    // "conv_pre" / "pre_tanh", or "ups_<i>" / "mrf_<i>" with stage i
+    bool is(const char* tap, int i = -1) const {
+        if (!name) return false;
+        return i < 0 ? !strcmp(name, tap) : !strncmp(name, tap, 4) && atoi(name + 4) == i;
+    }
+};
+
+// one micro-batch of a forward: utterances b0 .. b0 + nb - 1 on stream s
+struct MicroBatch {
+    int b0, nb;
+    hipStream_t s;
+    PassBufs buf;
+    bool par;    // the MRF's ResBlocks as parallel chains
+    float* wav;  // this micro-batch's waveform [nb][hop * T]
+    bool tail;   // bf16: conv_post + tanh ride on the last pair launch (tail_fused_bf16)
+};
+
+// tap copies: the engine's activation (bf16 channels-last or fp32 channel-major, its own layout) into the caller's fp32 tensor
+int tap_copy(const vtts_hifigan* h, const MicroBatch& m, const void* src, float* dst, size_t n) {
+    const hipError_t e = h->dtype == VTTS_BF16 ? launch_bf16_to_f32(src, dst, n, m.s)
+                                               : hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, m.s);
+    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "tap copy failed: %s", hipGetErrorString(e));
+    return VTTS_OK;
+}
+
+// x = (rb_0(x) + rb_1(x) [+ rb_2(x)]) / num_kernels with the ResBlocks' outputs in separate buffers (model.py:115-121): the same
+// additions in the same order as the ACC_STORE / ACC_ADD / ACC_MEAN epilogues (device_common.h), hence the same bits.
+__global__ __launch_bounds__(256) void mrf_mean_k(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ y2,
+                                                  float* __restrict__ out, size_t n, float div) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        float v = y0[i] + y1[i];
+        if (y2) v = v + y2[i];
+        out[i] = v / div;
+    }
+}
+
+// fp32 / bf16x3 engine: channel-major fp32 activations [B][C][L]
+float* f32(char* p) { return reinterpret_cast<float*>(p); }
+
+int conv_pre_f32(vtts_hifigan* h, const MicroBatch& m, const float* mel, int T) {
+    // conv_pre (model.py:110): mel [nb][T][num_mels] NWC -> S [nb][C0][T]
+    const int nm = h->cfg.num_mels;
+    return run_layer(h, h->layers[h->idx_pre], Act{mel, (long)T * nm, 1, nm}, m.nb, T, 1.0f, nullptr, f32(m.buf.S), ACC_STORE, 1.f, 0,
+                     nullptr, m.s);
+}
+
+int upsample_f32(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
+    // x = ups_i(leaky_relu(x, 0.1))   (model.py:112-114)
+    const Layer& up = h->layers[h->idx_ups[i]];
+    return run_layer(h, up, Act{f32(m.buf.S), (long)up.cin * L, L, 1}, m.nb, L, 0.1f, nullptr, f32(m.buf.X), ACC_STORE, 1.f, 0, nullptr, m.s);
+}
+
+int mrf_f32(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
+    const int nk = h->cfg.num_kernels;
+    const long CL = (long)h->layers[h->idx_ups[i]].cout * L;
+    // one ResBlock of the MRF: X -> (T, C scratch) -> out with the given accumulate mode, on stream cs
+    auto run_chain = [&](int j, float* out, int mode, float div, hipStream_t cs) -> int {
+        const Layer* rb = &h->layers[h->idx_res[i * nk + j]];
+        float* tT = f32(m.buf.T[j]);
+        float* tC = f32(m.buf.C[j]);
+        const float* cur = f32(m.buf.X);
+        int rc;
+        if (h->cfg.resblock == 2) {
+            // ResBlock2: x = c_z(leaky_relu(x, 0.1)) + x, z = 0, 1 (model.py:69-74); the MRF sum / mean in the last epilogue
+            if ((rc = run_layer(h, rb[0], Act{cur, CL, L, 1}, m.nb, L, 0.1f, cur, tC, ACC_STORE, 1.f, 0, nullptr, cs))) return rc;
+            return run_layer(h, rb[1], Act{tC, CL, L, 1}, m.nb, L, 0.1f, tC, out, mode, div, 0, nullptr, cs);
+        }
+        const Route route = route_f32(h, rb, L);
+        if (route == ROUTE_X3_RESBLOCK) return run_resblock_x3(h, rb, cur, m.nb, L, out, mode, div, cs);  // X -> out in one launch
+        if (route == ROUTE_PAIRS || route == ROUTE_X3_PAIRS) {
+            // fused pairs cannot run in place (a neighbour tile's halo would see updated columns): X -> T -> C -> out
+            const bool x3 = route == ROUTE_X3_PAIRS;
+            if ((rc = run_pair_f32(h, rb[0], rb[1], x3, cur, m.nb, L, tT, ACC_STORE, 1.f, cs))) return rc;
+            if ((rc = run_pair_f32(h, rb[2], rb[3], x3, tT, m.nb, L, tC, ACC_STORE, 1.f, cs))) return rc;
+            return run_pair_f32(h, rb[4], rb[5], x3, tC, m.nb, L, out, mode, div, cs);
+        }
+        for (int z = 0; z < 3; ++z) {
+            // xt = c1(leaky_relu(x, 0.1))                       (model.py:46-47)
+            if ((rc = run_layer(h, rb[2 * z], Act{cur, CL, L, 1}, m.nb, L, 0.1f, nullptr, tT, ACC_STORE, 1.f, 0, nullptr, cs))) return rc;
+            // x = c2(leaky_relu(xt, 0.1)) + x                  (model.py:48-50); the last pair's output takes the MRF sum / mean (model.py:115-121)
+            const bool last = z == 2;
+            if ((rc = run_layer(h, rb[2 * z + 1], Act{tT, CL, L, 1}, m.nb, L, 0.1f, cur, last ? out : tC, last ? mode : ACC_STORE, last ? div : 1.f,
+                                0, nullptr, cs)))
+                return rc;
+            cur = tC;
+        }
+        return VTTS_OK;
+    };
+    if (!m.par) {
+        for (int j = 0; j < nk; ++j) {
+            const int mode = (j == 0) ? ACC_STORE : (j == nk - 1 ? ACC_MEAN : ACC_ADD);
+            if (int rc = run_chain(j, f32(m.buf.S), mode, (float)nk, m.s)) return rc;
+        }
+        return VTTS_OK;
+    }
+    // the ResBlocks side by side, each into its own buffers; ((y0 + y1) + y2) / nk afterwards: same additions, same order
+    float* ys[3] = {f32(m.buf.Y[0]), f32(m.buf.Y[1]), f32(m.buf.Y[2])};
+    if (int rc = run_chains_parallel(h, nk, m.s, [&](int j, hipStream_t cs) { return run_chain(j, ys[j], ACC_STORE, 1.f, cs); })) return rc;
+    const size_t n = (size_t)m.nb * CL;
+    hipLaunchKernelGGL(mrf_mean_k, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, m.s, ys[0], ys[1], ys[2], f32(m.buf.S),
+                       n, (float)nk);
+    if (hipGetLastError() != hipSuccess) return fail(VTTS_ERR_HIP, "mrf_mean launch failed");
+    return VTTS_OK;
+}
+
+int conv_post_f32(vtts_hifigan* h, const MicroBatch& m, int L, float* pre_act) {
+    // tail: tanh(conv_post(leaky_relu(x)))  — slope 0.01, the jax default (model.py:122-124)
+    const Layer& l = h->layers[h->idx_post];
+    return run_layer(h, l, Act{f32(m.buf.S), (long)l.cin * L, L, 1}, m.nb, L, 0.01f, nullptr, m.wav, ACC_STORE, 1.f, 1, pre_act, m.s);
+}
+
+// bf16 engine.  Same dataflow as the fp32 one, with two differences that only bf16 needs:
 //  * activations are channels-last bf16 [B][L][C] (a transposed convolution's [L][s*Cout] output IS the
 //    [s*L][Cout] tensor);
 //  * a tensor that is only ever consumed through LeakyReLU is stored already activated by its producer
 //    (in fp32, before the bf16 rounding): conv_pre -> ups_0, xt = c1(.) -> c2, MRF mean -> next ups / conv_post.
 //    Only the ResBlock's running x is stored raw (it is also the residual) and activated on load by c1.
-int forward_bf16(vtts_hifigan* h, const float* mel, int B, int T, float* wav, void* ws, hipStream_t s0, Taps tap) {
-    const vtts_hifigan_cfg& c = h->cfg;
-    const int mb = pick_microbatch(h, B, T);
-    const size_t per = align_up(max_act_elems(h, T) * (size_t)mb * 2, 256);
-    const int nstr = num_streams(h, B, T);
-    hipStream_t streams[4];
-    int rc0 = fork_streams(h, nstr, s0, streams);
-    if (rc0) return rc0;
-    const int nk = c.num_kernels;
-    const long wav_len = (long)h->hop * T;
-    const bool par = chains_parallel(h, B, T);
-    for (int b0 = 0; b0 < B; b0 += mb) {
-        const int si = (b0 / mb) % nstr;
-        hipStream_t s = streams[si];
-        char* wsb = static_cast<char*>(ws) + (size_t)si * 4 * per;
-        char* bufX = wsb + 0 * per;
-        char* bufT = wsb + 1 * per;
-        char* bufC = wsb + 2 * per;
-        char* bufS = wsb + 3 * per;
-        if (par) bufS = wsb + 1 * per;  // parallel ResBlocks: [X | S | (T, C) per ResBlock] (one micro-batch, si == 0)
-        const int nb = std::min(mb, B - b0);
-        h->cur_b0 = b0;
-        int rc;
-        {
-            const Layer& l = h->layers[h->idx_pre];
-            rc = run_layer_bf16(h, l, mel + (size_t)b0 * T * c.num_mels, c.num_mels, c.num_mels, nb, T, 1.0f, 0.1f, nullptr, bufS, 0, 1.f, s);
-            if (rc) return rc;
-            if (tap.name && !strcmp(tap.name, "conv_pre")) {
-                rc = tap_copy_bf16(bufS, tap.out + (size_t)b0 * l.cout * T, (size_t)nb * l.cout * T, s);
-                if (rc) return rc;
-            }
-        }
-        long L = T;
-        bool tail_done = false;  // conv_post + tanh already ran inside the last pair launch
-        for (int i = 0; i < c.num_upsamples; ++i) {
-            const Layer& up = h->layers[h->idx_ups[i]];
-            rc = run_layer_bf16(h, up, bufS, up.cin, up.cin, nb, (int)L, 1.0f, 1.0f, nullptr, bufX, 0, 1.f, s);
-            if (rc) return rc;
-            L *= up.stride;
-            const int C = up.cout;
-            const size_t CL = (size_t)C * L;
-            if (tap.name && !strncmp(tap.name, "ups_", 4) && atoi(tap.name + 4) == i) {
-                rc = tap_copy_bf16(bufX, tap.out + (size_t)b0 * CL, (size_t)nb * CL, s);
-                if (rc) return rc;
-            }
-            const float next_slope = (i + 1 < c.num_upsamples) ? 0.1f : 0.01f;  // model.py:112 / :122
-            // the stage-4 tail (option "tail", default on): the generator's last pair launch also runs conv_post + tanh on its own rows, so the stage
-            // output is never written and conv_post_bf16_k is not launched.  Where the last ResBlock ends in a pair launch that can carry it (V1: C = 32,
-            // k = 11) and nothing needs the stage output itself (no tap)
-            float* tail_dst = nullptr;
-            if (h->opt_tail && !tap.name && i + 1 == c.num_upsamples && c.resblock != 2 && h->opt_fuse >= 1) {
-                const int lb = h->idx_res[i * nk + nk - 1];
-                const Layer& lc = h->layers[lb];
-                const Layer& post = h->layers[h->idx_post];
-                const bool whole_rb = h->opt_fuse >= 2 && lc.has_rb && (h->opt_fuse >= 3 || resblock_bf16_preferred(lc.cin, lc.k));
-                if (!whole_rb && lc.has_pair && h->layers[lb + 2].has_pair && h->layers[lb + 4].has_pair &&
-                    pair_tail_bf16_supported(lc.cin, lc.k, post.cin, post.cout, post.k))
-                    tail_dst = wav + (size_t)b0 * wav_len;
-            }
-            tail_done = tail_dst != nullptr;
-            // one ResBlock of the MRF: X -> (tT, tC scratch) -> the shared accumulator S (store / accumulate / accumulate-and-divide in the
-            // LAST kernel's epilogue); `before_last` runs right before that kernel is enqueued (the parallel schedule's ordering point)
-            auto run_chain = [&](int j, char* tT, char* tC, hipStream_t cs, auto before_last) -> int {
-                const int base = h->idx_res[i * nk + j];
-                const char* cur = bufX;
-                const bool last_rb = (j == nk - 1);
-                int rcc;
-                if (c.resblock == 2) {
-                    // ResBlock2: x = c_z(leaky_relu(x, 0.1)) + x, z = 0, 1 (model.py:69-74): the running x is stored raw (it is the residual) and
-                    // activated on load; the MRF sum / mean and the consumer's LeakyReLU in the second convolution's epilogue.  X -> C -> S
-                    if ((rcc = run_layer_bf16(h, h->layers[base], cur, C, C, nb, (int)L, 0.1f, 1.0f, cur, tC, 0, 1.f, cs))) return rcc;
-                    if ((rcc = before_last())) return rcc;
-                    return run_layer_bf16(h, h->layers[base + 1], tC, C, C, nb, (int)L, 0.1f, last_rb ? next_slope : 1.0f, tC, bufS, j > 0 ? 1 : 0,
-                                          last_rb ? (float)nk : 1.0f, cs);
-                }
-                // the whole-ResBlock kernel where it exists and is the faster choice (fuse = 3: wherever it exists)
-                if (h->opt_fuse >= 2 && h->layers[base].has_rb && (h->opt_fuse >= 3 || resblock_bf16_preferred(h->layers[base].cin, h->layers[base].k))) {
-                    // the whole ResBlock in one kernel: X -> S (store / accumulate / accumulate-and-divide)
-                    if ((rcc = before_last())) return rcc;
-                    return run_resblock_bf16(h, &h->layers[base], cur, nb, (int)L, last_rb ? next_slope : 1.0f, bufS, j > 0 ? 1 : 0,
-                                             last_rb ? (float)nk : 1.0f, cs);
-                }
-                if (h->opt_fuse && h->layers[base].has_pair && h->layers[base + 2].has_pair && h->layers[base + 4].has_pair) {
-                    // fused pairs cannot run in place (a neighbour tile's halo would see updated rows):
-                    // X -> T -> C -> S, with X kept for the other ResBlocks of the stage
-                    if ((rcc = run_pair_bf16(h, h->layers[base + 0], cur, nb, (int)L, 1.0f, tT, 0, 1.f, cs))) return rcc;
-                    if ((rcc = run_pair_bf16(h, h->layers[base + 2], tT, nb, (int)L, 1.0f, tC, 0, 1.f, cs))) return rcc;
-                    if ((rcc = before_last())) return rcc;
-                    return run_pair_bf16(h, h->layers[base + 4], tC, nb, (int)L, last_rb ? next_slope : 1.0f, bufS, j > 0 ? 1 : 0,
-                                         last_rb ? (float)nk : 1.0f, cs, last_rb ? tail_dst : nullptr);
-                }
-                for (int z = 0; z < 3; ++z) {
-                    const Layer& c1 = h->layers[base + 2 * z];
-                    const Layer& c2 = h->layers[base + 2 * z + 1];
-                    if ((rcc = run_layer_bf16(h, c1, cur, C, C, nb, (int)L, 0.1f, 0.1f, nullptr, tT, 0, 1.f, cs))) return rcc;
-                    if (z < 2) {
-                        if ((rcc = run_layer_bf16(h, c2, tT, C, C, nb, (int)L, 1.0f, 1.0f, cur, tC, 0, 1.f, cs))) return rcc;
-                        cur = tC;
-                    } else {
-                        if ((rcc = before_last())) return rcc;
-                        if ((rcc = run_layer_bf16(h, c2, tT, C, C, nb, (int)L, 1.0f, last_rb ? next_slope : 1.0f, cur, bufS, j > 0 ? 1 : 0,
-                                                  last_rb ? (float)nk : 1.0f, cs))) return rcc;
-                    }
-                }
-                return VTTS_OK;
-            };
-            if (par) {
-                // The ResBlocks side by side on nk streams with scratch of their own.  Only a ResBlock's LAST kernel touches the shared
-                // accumulator (bf16, rounded after every addition): those kernels are chained by events in the sequential order
-                // rb_0 -> rb_1 -> rb_2, so every sample sees the same additions and roundings as one-after-the-other — the same bits.
-                hipStream_t cs[4];
-                if ((rc = fork_streams(h, nk, s, cs))) {
-                    (void)join_streams(h, nk, s);
-                    return rc;
-                }
-                // every failure inside this block is collected in rc (no early return): the forked chain streams MUST be re-joined into
-                // `s` below, also when a launch fails — during graph capture an un-joined fork invalidates the capture
-                auto hip_rc = [&](hipError_t e, const char* what) -> int {
-                    return e == hipSuccess ? VTTS_OK : fail(VTTS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-                };
-                for (int j = 0; j < nk && !rc; ++j) {
-                    char* tT = wsb + (size_t)(2 + 2 * j) * per;
-                    char* tC = wsb + (size_t)(3 + 2 * j) * per;
-                    rc = run_chain(j, tT, tC, cs[j], [&]() -> int {
-                        return j > 0 ? hip_rc(hipStreamWaitEvent(cs[j], h->ev_chain[j - 1], 0), "hipStreamWaitEvent(chain)") : VTTS_OK;
-                    });
-                    if (!rc && j + 1 < nk) {
-                        if (!h->ev_chain[j]) rc = hip_rc(hipEventCreateWithFlags(&h->ev_chain[j], hipEventDisableTiming), "hipEventCreateWithFlags(chain)");
-                        if (!rc) rc = hip_rc(hipEventRecord(h->ev_chain[j], cs[j]), "hipEventRecord(chain)");
-                    }
-                }
-                const int rj = join_streams(h, nk, s);
-                if (rc) return rc;
-                if (rj) return rj;
-            } else {
-                for (int j = 0; j < nk; ++j)
-                    if ((rc = run_chain(j, bufT, bufC, s, []() -> int { return VTTS_OK; }))) return rc;
-            }
-            if (tap.name && !strncmp(tap.name, "mrf_", 4) && atoi(tap.name + 4) == i) {
-                rc = tap_copy_bf16(bufS, tap.out + (size_t)b0 * CL, (size_t)nb * CL, s);
-                if (rc) return rc;
-            }
-        }
-        if (!tail_done) {
-            const Layer& l = h->layers[h->idx_post];
-            BConvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = bufS;
-            a.wf = reinterpret_cast<const float*>(h->blob + l.off_w);
-            a.bias = reinterpret_cast<const float*>(h->blob + l.off_b);
-            a.B = nb;
-            a.L = (int)L;
-            set_ragged(h, a, (int)L);
-            float* pre = (tap.name && !strcmp(tap.name, "pre_tanh")) ? tap.out + (size_t)b0 * wav_len : nullptr;
-            hipError_t e = launch_conv_post_bf16(a, wav + (size_t)b0 * wav_len, pre, s);
-            if (e != hipSuccess) return fail(VTTS_ERR_HIP, "conv_post launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    return join_streams(h, nstr, s0);
+int conv_pre_bf16(vtts_hifigan* h, const MicroBatch& m, const float* mel, int T) {
+    const int nm = h->cfg.num_mels;
+    return run_layer_bf16(h, h->layers[h->idx_pre], mel, nm, nm, m.nb, T, 1.0f, 0.1f, nullptr, m.buf.S, 0, 1.f, m.s);
 }
 
-int forward_impl(vtts_hifigan* h, const float* mel, int B, int T, float* wav, void* ws, size_t ws_bytes, hipStream_t s,
-                 Taps tap) {
+int upsample_bf16(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
+    const Layer& up = h->layers[h->idx_ups[i]];
+    return run_layer_bf16(h, up, m.buf.S, up.cin, up.cin, m.nb, L, 1.0f, 1.0f, nullptr, m.buf.X, 0, 1.f, m.s);
+}
+
+int mrf_bf16(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
+    const vtts_hifigan_cfg& c = h->cfg;
+    const int nk = c.num_kernels;
+    const int C = h->layers[h->idx_ups[i]].cout;
+    const bool last_stage = i + 1 == c.num_upsamples;
+    const float next_slope = last_stage ? 0.01f : 0.1f;  // model.py:112 / :122
+    // one ResBlock of the MRF: X -> (tT, tC scratch) -> the shared accumulator S (store / accumulate / accumulate-and-divide in the
+    // LAST kernel's epilogue); `before_last` runs right before that kernel is enqueued (the parallel schedule's ordering point)
+    auto run_chain = [&](int j, hipStream_t cs, auto before_last) -> int {
+        const Layer* rb = &h->layers[h->idx_res[i * nk + j]];
+        char* tT = m.buf.T[j];
+        char* tC = m.buf.C[j];
+        const char* cur = m.buf.X;
+        const bool last_rb = j == nk - 1;
+        const float slope = last_rb ? next_slope : 1.0f;
+        const int acc = j > 0 ? 1 : 0;
+        const float div = last_rb ? (float)nk : 1.0f;
+        int rc;
+        if (c.resblock == 2) {
+            // ResBlock2: x = c_z(leaky_relu(x, 0.1)) + x, z = 0, 1 (model.py:69-74): the running x is stored raw (it is the residual) and
+            // activated on load; the MRF sum / mean and the consumer's LeakyReLU in the second convolution's epilogue.  X -> C -> S
+            if ((rc = run_layer_bf16(h, rb[0], cur, C, C, m.nb, L, 0.1f, 1.0f, cur, tC, 0, 1.f, cs))) return rc;
+            if ((rc = before_last())) return rc;
+            return run_layer_bf16(h, rb[1], tC, C, C, m.nb, L, 0.1f, slope, tC, m.buf.S, acc, div, cs);
+        }
+        switch (route_bf16(h, rb)) {
+            case ROUTE_RESBLOCK:  // the whole ResBlock in one kernel: X -> S
+                if ((rc = before_last())) return rc;
+                return run_resblock_bf16(h, rb, cur, m.nb, L, slope, m.buf.S, acc, div, cs);
+            case ROUTE_PAIRS:
+                // fused pairs cannot run in place (a neighbour tile's halo would see updated rows):
+                // X -> T -> C -> S, with X kept for the other ResBlocks of the stage
+                if ((rc = run_pair_bf16(h, rb[0], cur, m.nb, L, 1.0f, tT, 0, 1.f, cs))) return rc;
+                if ((rc = run_pair_bf16(h, rb[2], tT, m.nb, L, 1.0f, tC, 0, 1.f, cs))) return rc;
+                if ((rc = before_last())) return rc;
+                return run_pair_bf16(h, rb[4], tC, m.nb, L, slope, m.buf.S, acc, div, cs, last_stage && last_rb && m.tail ? m.wav : nullptr);
+            default:
+                for (int z = 0; z < 2; ++z) {
+                    if ((rc = run_layer_bf16(h, rb[2 * z], cur, C, C, m.nb, L, 0.1f, 0.1f, nullptr, tT, 0, 1.f, cs))) return rc;
+                    if ((rc = run_layer_bf16(h, rb[2 * z + 1], tT, C, C, m.nb, L, 1.0f, 1.0f, cur, tC, 0, 1.f, cs))) return rc;
+                    cur = tC;
+                }
+                if ((rc = run_layer_bf16(h, rb[4], cur, C, C, m.nb, L, 0.1f, 0.1f, nullptr, tT, 0, 1.f, cs))) return rc;
+                if ((rc = before_last())) return rc;
+                return run_layer_bf16(h, rb[5], tT, C, C, m.nb, L, 1.0f, slope, cur, m.buf.S, acc, div, cs);
+        }
+    };
+    if (!m.par) {
+        for (int j = 0; j < nk; ++j)
+            if (int rc = run_chain(j, m.s, [] { return VTTS_OK; })) return rc;
+        return VTTS_OK;
+    }
+    // The ResBlocks side by side with scratch of their own.  Only a ResBlock's LAST kernel touches the shared accumulator (bf16, rounded
+    // after every addition): those kernels are chained by events in the sequential order rb_0 -> rb_1 -> rb_2, so every sample sees the
+    // same additions and roundings as one-after-the-other — the same bits.
+    auto hip_rc = [&](hipError_t e, const char* what) -> int {
+        return e == hipSuccess ? VTTS_OK : fail(VTTS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    return run_chains_parallel(h, nk, m.s, [&](int j, hipStream_t cs) -> int {
+        int rc = run_chain(j, cs, [&]() -> int {
+            return j > 0 ? hip_rc(hipStreamWaitEvent(cs, h->ev_chain[j - 1], 0), "hipStreamWaitEvent(chain)") : VTTS_OK;
+        });
+        if (!rc && j + 1 < nk) {
+            if (!h->ev_chain[j]) rc = hip_rc(hipEventCreateWithFlags(&h->ev_chain[j], hipEventDisableTiming), "hipEventCreateWithFlags(chain)");
+            if (!rc) rc = hip_rc(hipEventRecord(h->ev_chain[j], cs), "hipEventRecord(chain)");
+        }
+        return rc;
+    });
+}
+
+int conv_post_bf16(vtts_hifigan* h, const MicroBatch& m, int L, float* pre_act) {
+    const Layer& l = h->layers[h->idx_post];
+    BConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = m.buf.S;
+    a.wf = reinterpret_cast<const float*>(h->blob + l.off_w);
+    a.bias = reinterpret_cast<const float*>(h->blob + l.off_b);
+    a.B = m.nb;
+    a.L = L;
+    set_ragged(h, a, L);
+    hipError_t e = launch_conv_post_bf16(a, m.wav, pre_act, m.s);
+    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "conv_post launch failed: %s", hipGetErrorString(e));
+    return VTTS_OK;
+}
+
+// one engine's steps of a micro-batch; forward_impl runs them stage by stage
+struct Engine {
+    int (*conv_pre)(vtts_hifigan*, const MicroBatch&, const float* mel, int T);  // mel -> S
+    int (*upsample)(vtts_hifigan*, const MicroBatch&, int i, int L);             // S -> X, L = stage i's input length
+    int (*mrf)(vtts_hifigan*, const MicroBatch&, int i, int L);                  // X -> S, L = stage i's length
+    int (*conv_post)(vtts_hifigan*, const MicroBatch&, int L, float* pre_act);   // S -> wav
+};
+constexpr Engine ENGINE_F32{conv_pre_f32, upsample_f32, mrf_f32, conv_post_f32};
+constexpr Engine ENGINE_BF16{conv_pre_bf16, upsample_bf16, mrf_bf16, conv_post_bf16};
+
+int run_micro_batch(vtts_hifigan* h, const Engine& e, const MicroBatch& m, const float* mel, int T, const Taps& tap) {
+    const vtts_hifigan_cfg& c = h->cfg;
+    const Layer& pre = h->layers[h->idx_pre];
+    int rc;
+    if ((rc = e.conv_pre(h, m, mel + (size_t)m.b0 * T * c.num_mels, T))) return rc;
+    if (tap.is("conv_pre") && (rc = tap_copy(h, m, m.buf.S, tap.out + (size_t)m.b0 * pre.cout * T, (size_t)m.nb * pre.cout * T))) return rc;
+    long L = T;
+    for (int i = 0; i < c.num_upsamples; ++i) {
+        const Layer& up = h->layers[h->idx_ups[i]];
+        if ((rc = e.upsample(h, m, i, (int)L))) return rc;
+        L *= up.stride;
+        const size_t CL = (size_t)up.cout * L;
+        if (tap.is("ups_", i) && (rc = tap_copy(h, m, m.buf.X, tap.out + (size_t)m.b0 * CL, (size_t)m.nb * CL))) return rc;
+        if ((rc = e.mrf(h, m, i, (int)L))) return rc;
+        if (tap.is("mrf_", i) && (rc = tap_copy(h, m, m.buf.S, tap.out + (size_t)m.b0 * CL, (size_t)m.nb * CL))) return rc;
+    }
+    if (m.tail) return VTTS_OK;  // conv_post + tanh already ran inside the last pair launch
+    return e.conv_post(h, m, (int)L, tap.is("pre_tanh") ? tap.out + (size_t)m.b0 * h->hop * T : nullptr);
+}
+
+int forward_impl(vtts_hifigan* h, const float* mel, int B, int T, float* wav, void* ws, size_t ws_bytes, hipStream_t s0,
+                 const Taps& tap) {
     if (!h->blob) return fail(VTTS_ERR_STATE, "forward() before pack()/bind_packed()");
     if (B <= 0 || T <= 0) return fail(VTTS_ERR_INVALID, "B and T must be positive (got B=%d, T=%d)", B, T);
     if (int rc = check_pass_size(h, B, T)) return rc;
-    size_t need = 0;
-    vtts_hifigan_workspace_bytes(h, B, T, &need);
-    if (ws_bytes < need || !ws) return fail(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", ws_bytes, need);
+    const PassPlan p = plan_pass(h, B, T);
+    if (ws_bytes < p.bytes() || !ws) return fail(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", ws_bytes, p.bytes());
     if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return fail(VTTS_ERR_INVALID, "workspace must be 256-B aligned");
-
     {
         hipError_t e = hipSetDevice(h->device);  // side streams / events are created lazily: on THIS handle's device
         if (e != hipSuccess) return fail(VTTS_ERR_HIP, "hipSetDevice(%d) failed: %s", h->device, hipGetErrorString(e));
     }
-    if (h->dtype == VTTS_BF16) {
-        const int rc = forward_bf16(h, mel, B, T, wav, ws, s, tap);
-        if (rc) (void)join_streams(h, num_streams(h, B, T), s);  // a failed launch must not leave forked side streams un-joined
-        return rc;
-    }
-
-    const vtts_hifigan_cfg& c = h->cfg;
-    const int mb = pick_microbatch(h, B, T);
-    const size_t per = align_up(max_act_elems(h, T) * (size_t)mb * sizeof(float), 256);
-    const int nstr = num_streams(h, B, T);
+    const Engine& e = h->dtype == VTTS_BF16 ? ENGINE_BF16 : ENGINE_F32;
+    const bool tail = h->dtype == VTTS_BF16 && !tap.name && tail_fused_bf16(h);
     hipStream_t streams[4];
-    hipStream_t s0 = s;
-    int rc0 = fork_streams(h, nstr, s0, streams);
-    if (rc0) return rc0;
-    const int nk = c.num_kernels;
-    const long wav_len = (long)h->hop * T;
-    const bool par = chains_parallel(h, B, T);
-
-    for (int b0 = 0; b0 < B; b0 += mb) {
-        const int si = (b0 / mb) % nstr;
-        hipStream_t s = streams[si];
-        char* wsb = static_cast<char*>(ws) + (size_t)si * 4 * per;
-        float* bufX = reinterpret_cast<float*>(wsb + 0 * per);   // stage input x (ups output)
-        float* bufT = reinterpret_cast<float*>(wsb + 1 * per);   // xt inside a ResBlock pair
-        float* bufC = reinterpret_cast<float*>(wsb + 2 * per);   // running x inside a ResBlock
-        float* bufS = reinterpret_cast<float*>(wsb + 3 * per);   // MRF accumulator xs / stage output
-        if (par) bufS = reinterpret_cast<float*>(wsb + 1 * per);  // parallel ResBlocks: [X | S | (T, C, Y) per ResBlock] (one micro-batch, si == 0)
-        const int nb = std::min(mb, B - b0);
+    int rc = fork_streams(h, p.nstr, s0, streams);
+    for (int b0 = 0; b0 < B && !rc; b0 += p.mb) {
+        const int si = (b0 / p.mb) % p.nstr;
+        const MicroBatch m{b0, std::min(p.mb, B - b0), streams[si], p.buffers(ws, si, h->cfg.num_kernels), p.par, wav + (size_t)b0 * h->hop * T, tail};
         h->cur_b0 = b0;
-        int rc;
-        // conv_pre (model.py:110): mel [nb][T][num_mels] NWC -> S [nb][C0][T]
-        {
-            const Layer& l = h->layers[h->idx_pre];
-            Act x{mel + (long)b0 * T * c.num_mels, (long)T * c.num_mels, 1, c.num_mels};
-            rc = run_layer(h, l, x, nb, T, 1.0f, nullptr, bufS, ACC_STORE, 1.f, 0, nullptr, s);
-            if (rc) { (void)join_streams(h, nstr, s0); return rc; }
-            if (tap.name && !strcmp(tap.name, "conv_pre"))
-                HIP_TRY(hipMemcpyAsync(tap.out + (size_t)b0 * l.cout * T, bufS, (size_t)nb * l.cout * T * sizeof(float),
-                                       hipMemcpyDeviceToDevice, s));
-        }
-        long L = T;
-        for (int i = 0; i < c.num_upsamples; ++i) {
-            const Layer& up = h->layers[h->idx_ups[i]];
-            // x = ups_i(leaky_relu(x, 0.1))   (model.py:112-114)
-            Act xin{bufS, (long)up.cin * L, L, 1};
-            rc = run_layer(h, up, xin, nb, (int)L, 0.1f, nullptr, bufX, ACC_STORE, 1.f, 0, nullptr, s);
-            if (rc) { (void)join_streams(h, nstr, s0); return rc; }
-            L *= up.stride;
-            const int C = up.cout;
-            const long CL = (long)C * L;
-            if (tap.name && !strncmp(tap.name, "ups_", 4) && atoi(tap.name + 4) == i)
-                HIP_TRY(hipMemcpyAsync(tap.out + (size_t)b0 * CL, bufX, (size_t)nb * CL * sizeof(float), hipMemcpyDeviceToDevice, s));
-            // one ResBlock of the MRF: X -> (T, C scratch) -> out with the given accumulate mode, on stream cs
-            auto run_chain = [&](int j, float* tT, float* tC, float* out, int mode, float div, hipStream_t cs) -> int {
-                const int base = h->idx_res[i * nk + j];
-                const float* cur = bufX;
-                int rcc = VTTS_OK;
-                if (c.resblock == 2) {
-                    // ResBlock2: x = c_z(leaky_relu(x, 0.1)) + x, z = 0, 1 (model.py:69-74); the MRF sum / mean in the last epilogue
-                    for (int z = 0; z < 2 && !rcc; ++z) {
-                        const Layer& cz = h->layers[base + z];
-                        if (z == 0) {
-                            rcc = run_layer(h, cz, Act{cur, CL, L, 1}, nb, (int)L, 0.1f, cur, tC, ACC_STORE, 1.f, 0, nullptr, cs);
-                            cur = tC;
-                        } else {
-                            rcc = run_layer(h, cz, Act{cur, CL, L, 1}, nb, (int)L, 0.1f, cur, out, mode, div, 0, nullptr, cs);
-                        }
-                    }
-                    return rcc;
-                }
-                if (resblock_x3_wanted(h, &h->layers[base], (int)L))  // VTTS_BF16X3, narrow stages: the whole ResBlock X -> out in one launch
-                    return run_resblock_x3(h, &h->layers[base], cur, nb, (int)L, out, mode, div, cs);
-                if (pair_x3_wanted(h, h->layers[base], h->layers[base + 1], (int)L) && pair_x3_wanted(h, h->layers[base + 2], h->layers[base + 3], (int)L) &&
-                    pair_x3_wanted(h, h->layers[base + 4], h->layers[base + 5], (int)L)) {
-                    // VTTS_BF16X3: X -> T -> C -> out as the fused fp32 pairs below
-                    if ((rcc = run_pair_x3(h, h->layers[base + 0], h->layers[base + 1], cur, nb, (int)L, tT, ACC_STORE, 1.f, cs))) return rcc;
-                    if ((rcc = run_pair_x3(h, h->layers[base + 2], h->layers[base + 3], tT, nb, (int)L, tC, ACC_STORE, 1.f, cs))) return rcc;
-                    return run_pair_x3(h, h->layers[base + 4], h->layers[base + 5], tC, nb, (int)L, out, mode, div, cs);
-                }
-                if (pair_f32_wanted(h, h->layers[base], h->layers[base + 1], (int)L) && pair_f32_wanted(h, h->layers[base + 2], h->layers[base + 3], (int)L) &&
-                    pair_f32_wanted(h, h->layers[base + 4], h->layers[base + 5], (int)L)) {
-                    // fused pairs cannot run in place (a neighbour tile's halo would see updated columns): X -> T -> C -> out
-                    if ((rcc = run_pair_f32(h, h->layers[base + 0], h->layers[base + 1], cur, nb, (int)L, tT, ACC_STORE, 1.f, cs))) return rcc;
-                    if ((rcc = run_pair_f32(h, h->layers[base + 2], h->layers[base + 3], tT, nb, (int)L, tC, ACC_STORE, 1.f, cs))) return rcc;
-                    return run_pair_f32(h, h->layers[base + 4], h->layers[base + 5], tC, nb, (int)L, out, mode, div, cs);
-                }
-                for (int z = 0; z < 3 && !rcc; ++z) {
-                    const Layer& c1 = h->layers[base + 2 * z];
-                    const Layer& c2 = h->layers[base + 2 * z + 1];
-                    // xt = c1(leaky_relu(x, 0.1))                       (model.py:46-47)
-                    rcc = run_layer(h, c1, Act{cur, CL, L, 1}, nb, (int)L, 0.1f, nullptr, tT, ACC_STORE, 1.f, 0, nullptr, cs);
-                    if (rcc) break;
-                    // x = c2(leaky_relu(xt, 0.1)) + x                  (model.py:48-50)
-                    if (z < 2) {
-                        rcc = run_layer(h, c2, Act{tT, CL, L, 1}, nb, (int)L, 0.1f, cur, tC, ACC_STORE, 1.f, 0, nullptr, cs);
-                        cur = tC;
-                    } else {
-                        // last pair of the ResBlock: its output (sequential schedule: the MRF sum / mean folded into the epilogue, model.py:115-121)
-                        rcc = run_layer(h, c2, Act{tT, CL, L, 1}, nb, (int)L, 0.1f, cur, out, mode, div, 0, nullptr, cs);
-                    }
-                }
-                return rcc;
-            };
-            if (par) {
-                // the ResBlocks side by side on nk streams, each into its own buffers; ((y0 + y1) + y2) / nk afterwards: same additions, same order
-                hipStream_t cs[4];
-                rc = fork_streams(h, nk, s, cs);
-                if (rc) { (void)join_streams(h, nstr, s0); return rc; }
-                float* ys[3] = {nullptr, nullptr, nullptr};
-                for (int j = 0; j < nk; ++j) {
-                    float* cb = reinterpret_cast<float*>(wsb + (size_t)(2 + 3 * j) * per);
-                    float* tT = cb;
-                    float* tC = reinterpret_cast<float*>(wsb + (size_t)(3 + 3 * j) * per);
-                    ys[j] = reinterpret_cast<float*>(wsb + (size_t)(4 + 3 * j) * per);
-                    rc = run_chain(j, tT, tC, ys[j], ACC_STORE, 1.f, cs[j]);
-                    if (rc) { (void)join_streams(h, nk, s); (void)join_streams(h, nstr, s0); return rc; }
-                }
-                rc = join_streams(h, nk, s);
-                if (rc) { (void)join_streams(h, nstr, s0); return rc; }
-                const size_t n = (size_t)nb * CL;
-                hipLaunchKernelGGL(mrf_mean_k, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, ys[0], ys[1], ys[2], bufS, n, (float)nk);
-                if (hipGetLastError() != hipSuccess) { (void)join_streams(h, nstr, s0); return fail(VTTS_ERR_HIP, "mrf_mean launch failed"); }
-            } else {
-                for (int j = 0; j < nk; ++j) {
-                    const int mode = (j == 0) ? ACC_STORE : (j == nk - 1 ? ACC_MEAN : ACC_ADD);
-                    rc = run_chain(j, bufT, bufC, bufS, mode, (float)nk, s);
-                    if (rc) { (void)join_streams(h, nstr, s0); return rc; }
-                }
-            }
-            if (nk == 1) {
-                // a single-kernel MRF still divides by num_kernels == 1: identity, nothing to do
-            }
-            if (tap.name && !strncmp(tap.name, "mrf_", 4) && atoi(tap.name + 4) == i)
-                HIP_TRY(hipMemcpyAsync(tap.out + (size_t)b0 * CL, bufS, (size_t)nb * CL * sizeof(float), hipMemcpyDeviceToDevice, s));
-        }
-        // tail: tanh(conv_post(leaky_relu(x)))  — slope 0.01, the jax default (model.py:122-124)
-        {
-            const Layer& l = h->layers[h->idx_post];
-            float* pre = (tap.name && !strcmp(tap.name, "pre_tanh")) ? tap.out + (size_t)b0 * wav_len : nullptr;
-            rc = run_layer(h, l, Act{bufS, (long)l.cin * L, L, 1}, nb, (int)L, 0.01f, nullptr, wav + (size_t)b0 * wav_len,
-                           ACC_STORE, 1.f, 1, pre, s);
-            if (rc) { (void)join_streams(h, nstr, s0); return rc; }
-        }
+        rc = run_micro_batch(h, e, m, mel, T, tap);
     }
-    return join_streams(h, nstr, s0);
+    // the only exit after the fork: a failed launch must not leave forked side streams un-joined
+    const int rj = join_streams(h, p.nstr, s0);
+    return rc ? rc : rj;
 }
 
 }  // namespace
@@ -1414,7 +1278,7 @@ VTTS_API int vtts_hifigan_pack(vtts_hifigan* h, void* dev_blob, size_t blob_byte
             const Layer& c1 = h->layers[i];
             if (!c1.has_pair) continue;
             const Layer& c2 = h->layers[i + 1];
-            const BPackGeom pg = pair_pack_geom(c1.cin, c1.k);
+            const BPackGeom pg = pair_g_pack_geom(c1.cin, c1.k);
             const size_t half = bf16_packed_bytes(pg);
             bf16_pack(c1.w.data(), c1.cin, pg, reinterpret_cast<unsigned short*>(host.data() + c1.off_pw));
             bf16_pack(c2.w.data(), c2.cin, pg, reinterpret_cast<unsigned short*>(host.data() + c1.off_pw + half));
@@ -1468,10 +1332,7 @@ VTTS_API int vtts_hifigan_workspace_bytes(const vtts_hifigan* h, int B, int T, s
     if (!h || !bytes) return fail(VTTS_ERR_INVALID, "null argument");
     if (B <= 0 || T <= 0) return fail(VTTS_ERR_INVALID, "B and T must be positive");
     if (int rc = check_pass_size(h, B, T)) return rc;
-    const int mb = pick_microbatch(h, B, T);
-    const size_t es = h->dtype == VTTS_BF16 ? 2 : sizeof(float);
-    const size_t per = align_up(max_act_elems(h, T) * (size_t)mb * es, 256);
-    *bytes = chains_parallel(h, B, T) ? (size_t)pass_buffers(h, B, T) * per : (size_t)num_streams(h, B, T) * 4 * per;
+    *bytes = plan_pass(h, B, T).bytes();
     return VTTS_OK;
 }
 
@@ -1484,7 +1345,7 @@ constexpr int GRAPH_SLOTS = 8;
 constexpr int GRAPH_AFTER = 8;  // capture + instantiate cost about a millisecond, once: only a key that keeps coming back pays it
 int forward_maybe_graphed(vtts_hifigan* h, const float* mel, int B, int T, float* wav, void* ws, size_t ws_bytes, hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (!h->opt_graph || h->opt_profile || B <= 0 || T <= 0 || !h->blob || !chains_parallel(h, B, T) ||
+    if (!h->opt_graph || h->opt_profile || B <= 0 || T <= 0 || !h->blob || !plan_pass(h, B, T).par ||
         hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone)  // inside the CALLER's capture: just enqueue
         return forward_impl(h, mel, B, T, wav, ws, ws_bytes, s, Taps{});
     if (hipSetDevice(h->device) != hipSuccess) return fail(VTTS_ERR_HIP, "hipSetDevice(%d) failed", h->device);  // graph launches too run on THIS handle's device
@@ -1605,7 +1466,6 @@ VTTS_API int vtts_hifigan_forward_tap(vtts_hifigan* h, const float* mel_dev, int
     Taps t;
     t.name = tap;
     t.out = tap_dev;
-    t.Bfull = B;
     return forward_impl(h, mel_dev, B, T, wav_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream), t);
 }
 
@@ -1673,14 +1533,13 @@ VTTS_API int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const fl
     if (!h->blob) return fail(VTTS_ERR_STATE, "run_pair() before pack()/bind_packed()");
     if (B <= 0 || L <= 0) return fail(VTTS_ERR_INVALID, "B and L must be positive");
     Layer* l = find_layer(h, key_c1);
-    if (h->x3 && l && l + 1 < h->layers.data() + h->layers.size() && pair_x3_wanted(h, *l, *(l + 1), L))
-        return run_pair_x3(h, *l, *(l + 1), x_dev, B, L, y_dev, ACC_STORE, 1.f, static_cast<hipStream_t>(stream));
+    const Layer* c2 = l && l + 1 < h->layers.data() + h->layers.size() ? l + 1 : nullptr;
     if (h->dtype == VTTS_F32) {
-        // fp32 handle: x_dev / y_dev are [B, C, L] channel-major (the fp32 engine's layout); asynchronous on `stream`
-        if (!l || l + 1 >= h->layers.data() + h->layers.size() || !l->has_wp || !(l + 1)->has_wp || (l + 1)->k != l->k || (l + 1)->dil != 1 ||
-            (l + 1)->cin != l->cin || l->cin != l->cout || !pair_f32_supported(l->cin, l->k, l->dil, L))
+        // fp32 / bf16x3 handle: x_dev / y_dev are [B, C, L] channel-major (the fp32 engine's layout); asynchronous on `stream`
+        const bool x3 = c2 && pair_x3_wanted(h, *l, *c2, L);
+        if (!x3 && (!c2 || !pair_f32_fusable(*l, *c2, L)))
             return fail(VTTS_ERR_INVALID, "'%s' is not the first convolution of a ResBlock pair the fused fp32 kernel covers (C in {32, 64, 128}, L a multiple of 4)", key_c1);
-        return run_pair_f32(h, *l, *(l + 1), x_dev, B, L, y_dev, ACC_STORE, 1.f, static_cast<hipStream_t>(stream));
+        return run_pair_f32(h, *l, *c2, x3, x_dev, B, L, y_dev, ACC_STORE, 1.f, static_cast<hipStream_t>(stream));
     }
     if (!l || !l->has_pair) return fail(VTTS_ERR_INVALID, "'%s' is not the first convolution of a fused ResBlock pair", key_c1);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1769,7 +1628,7 @@ VTTS_API int vtts_hifigan_get_option(const vtts_hifigan* h, const char* name, in
     else if (!strcmp(name, "max_frames_per_pass")) {
         // the smallest T check_pass_size() refuses (one utterance's largest activation must stay below 2^31 bytes; max_act_elems is linear
         // in T): callers route longer utterances through the chunk scheduler — ONE rule, here
-        const size_t per = max_act_elems(h, 1) * (h->dtype == VTTS_BF16 ? 2 : sizeof(float));
+        const size_t per = max_act_elems(h, 1) * elem_bytes(h);
         *value = (int64_t)((((size_t)1 << 31) + per - 1) / per);
     }
     else if (!strcmp(name, "pass_frames")) *value = pass_frames(h);

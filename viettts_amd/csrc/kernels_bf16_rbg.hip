@@ -716,8 +716,5 @@ const char* pair_g_kernel_name(int C, int K) {
 bool pair_bf16_supported(int C, int K, int dil) {
     return (C == 256 || C == 128 || C == 64 || C == 32) && (K == 3 || K == 7 || K == 11) && dil >= 1 && dil <= 5;
 }
-BPackGeom pair_pack_geom(int C, int K) { return pair_g_pack_geom(C, K); }
-hipError_t launch_pair_bf16(int C, int K, const BConvArgs& a, hipStream_t s) { return launch_pair_g_bf16(C, K, a, s); }
-const char* pair_kernel_name(int C, int K) { return pair_g_kernel_name(C, K); }
 
 }  // namespace vtts

@@ -23,7 +23,6 @@
 //   C = 32 : W = 512, waves 1 x 4, wave tile 32 x 128      used for k = 3 (k = 7, 11 exist; the pair kernel wins there)
 //   C = 64 : W = 256, waves 1 x 4, wave tile 64 x 64       used for k = 3
 //   C = 128: W = 128, waves 2 x 2, wave tile 64 x 64       exists for k = 3; the pair kernel wins there
-#include <stdio.h>
 #include <string.h>
 
 #include <type_traits>
@@ -513,12 +512,6 @@ hipError_t launch_resblock_bf16(int C, int K, const BConvArgs& a, hipStream_t s)
     }
     if (C == 128 && K == 3) return launch_rb<RB128<3>>(a, s);
     return hipErrorInvalidValue;
-}
-
-const char* resblock_kernel_name(int C, int K) {
-    static thread_local char buf[64];
-    snprintf(buf, sizeof(buf), "resblock_bf16_k<RBTile<%d, %d,", C, K);
-    return buf;
 }
 
 }  // namespace vtts

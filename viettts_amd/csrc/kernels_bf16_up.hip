@@ -15,7 +15,6 @@
 //     from LDS with one row address + swizzle term per tap (the lean addressing of the pair kernel); no workgroup
 //     synchronisation after the tile is staged;
 //   * the epilogue packs to bf16 and stores 16 bytes per lane straight from the accumulator layout (v_permlane32_swap).
-#include <stdio.h>
 #include <string.h>
 
 #include <type_traits>
@@ -343,13 +342,6 @@ BPackGeom convt_g_pack_geom(int cls) {
         case BCLS_PRE: return BPackGeom{128, 128, 512, 7, 512, 1};  // the plain convolution's 7 taps, input channels padded 80 -> 128 with zeros
     }
     return BPackGeom{0, 0, 0, 0, 0, 0};
-}
-
-const char* convt_g_kernel_name(int cls) {
-    static thread_local char buf[64];
-    if (cls == BCLS_PRE) snprintf(buf, sizeof(buf), "convt_g_bf16_k<UTile<128, 512,");
-    else snprintf(buf, sizeof(buf), "convt_g_bf16_k<UTile<%d,", cls == BCLS_UP0 ? 512 : cls == BCLS_UP1 ? 256 : cls == BCLS_UP2 ? 128 : 64);
-    return buf;
 }
 
 }  // namespace vtts

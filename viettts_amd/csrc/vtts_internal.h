@@ -158,14 +158,11 @@ BPackGeom bf16_pack_geom(int cls, int K);
 const char* bf16_kernel_name(int cls, int K);
 size_t bf16_packed_bytes(const BPackGeom& g);
 void bf16_pack(const float* Wc, int cin_real, const BPackGeom& g, unsigned short* out);
-// fused ResBlock1 pair (c1 -> lrelu -> c2 -> + x): kernels_bf16_rbg.hip.  a.wp = [c1 fragments][c2 fragments],
-// a.bias = [b1 (C)][b2 (C)], a.x = raw pair input (also the residual), a.dil/a.pad = c1's rate / pad.
+// fused ResBlock1 pair (c1 -> lrelu -> c2 -> + x): kernels_bf16_rbg.hip, weights straight from L2 into register rings, no workgroup
+// sync in the main loops.  a.wp = [c1 fragments][c2 fragments] (each packed with pair_g_pack_geom), a.bias = [b1 (C)][b2 (C)],
+// a.x = raw pair input (also the residual), a.dil/a.pad = c1's rate / pad.
 bool pair_bf16_supported(int C, int K, int dil);
-BPackGeom pair_pack_geom(int C, int K);
-hipError_t launch_pair_bf16(int C, int K, const BConvArgs& a, hipStream_t s);
 bool pair_tail_bf16_supported(int C, int K, int post_cin, int post_cout, int post_k);
-const char* pair_kernel_name(int C, int K);
-// kernels_bf16_rbg.hip: weights straight from L2 into register rings, no workgroup sync in the main loops
 hipError_t launch_pair_g_bf16(int C, int K, const BConvArgs& a, hipStream_t s);
 BPackGeom pair_g_pack_geom(int C, int K);
 const char* pair_g_kernel_name(int C, int K);
@@ -173,12 +170,10 @@ const char* pair_g_kernel_name(int C, int K);
 bool resblock_bf16_supported(int C, int K, const int* dils);
 bool resblock_bf16_preferred(int C, int K);
 hipError_t launch_resblock_bf16(int C, int K, const BConvArgs& a, hipStream_t s);
-const char* resblock_kernel_name(int C, int K);
 // the four transposed convolutions on the register-streamed structure (kernels_bf16_up.hip): cls = BCLS_UP0..3,
 // a.wp = the 3-tap polyphase form's weights packed with convt_g_pack_geom(cls) (bf16_pack)
 hipError_t launch_convt_g_bf16(int cls, const BConvArgs& a, hipStream_t s);
 BPackGeom convt_g_pack_geom(int cls);
-const char* convt_g_kernel_name(int cls);
 hipError_t launch_conv_post_bf16(const BConvArgs& a, float* wav, float* pre_act, hipStream_t s);
 hipError_t launch_bf16_to_f32(const void* in, float* out, size_t n, hipStream_t s);
 hipError_t launch_f32_to_bf16(const float* in, void* out, size_t n, hipStream_t s);
