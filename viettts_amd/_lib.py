@@ -88,6 +88,28 @@ NAT_EXPORTS = (
     "vtts_nat_acoustic_forward_from_encoder",
 )
 
+# Every symbol include/vtts_mel.h declares.
+MEL_EXPORTS = (
+    "vtts_mel_create",
+    "vtts_mel_destroy",
+    "vtts_mel_num_frames",
+    "vtts_mel_filterbank",
+    "vtts_mel_packed_bytes",
+    "vtts_mel_pack",
+    "vtts_mel_bind_packed",
+    "vtts_mel_workspace_bytes",
+    "vtts_mel_forward",
+)
+
+VTTS_MEL_F32 = 0
+VTTS_MEL_PCM16 = 1
+MEL_FRAMES_PER_BLOCK = 8  # include/vtts_mel.h: VTTS_MEL_FRAMES_PER_BLOCK
+MEL_MIN_SAMPLES = 385  # include/vtts_mel.h: VTTS_MEL_MIN_SAMPLES
+
+
+class MelCfg(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
+
 
 class NatDurationCfg(C.Structure):
     _fields_ = [("vocab_size", C.c_int32), ("lstm_dim", C.c_int32)]
@@ -225,6 +247,15 @@ def load(path=None) -> C.CDLL:
         "vtts_nat_acoustic_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
         "vtts_nat_acoustic_forward_from_encoder": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp, C.c_int,
                                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "vtts_mel_create": (C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
+        "vtts_mel_destroy": (None, [vp]),
+        "vtts_mel_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
+        "vtts_mel_filterbank": (C.c_int, [vp, fp]),
+        "vtts_mel_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+        "vtts_mel_pack": (C.c_int, [vp, vp, sz, vp]),
+        "vtts_mel_bind_packed": (C.c_int, [vp, vp, sz]),
+        "vtts_mel_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+        "vtts_mel_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, i64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported

@@ -1,0 +1,102 @@
+"""Analysis -> resynthesis on the GPU: waveform -> log-mel (``MelFilter``, include/vtts_mel.h) -> waveform (``Generator``), the
+standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
+computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
+
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3]
+
+reads PCM16 mono, uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
+``FileNotFoundError`` without them.
+"""
+from __future__ import annotations
+
+import argparse
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import wavio
+from .nat.config import FLAGS as NAT_FLAGS
+from .nat.dsp import MelFilter
+
+_FILTERS: dict = {}
+
+
+def default_mel_filter(device) -> MelFilter:
+    """The reference's configuration (vietTTS/nat/config.py:43-47): 16 kHz, n_fft 1024, 80 bands, 0 .. 8000 Hz; one per device."""
+    device = torch.device(device)
+    f = _FILTERS.get(device)
+    if f is None:
+        f = _FILTERS[device] = MelFilter(NAT_FLAGS.sample_rate, 1024, 80, 0.0, 8000, device=device)
+    return f
+
+
+def _on_device(wav, device) -> torch.Tensor:
+    if isinstance(wav, torch.Tensor):
+        return wav.to(device)
+    wav = np.asarray(wav)
+    if wav.dtype != np.int16:
+        wav = wav.astype(np.float32, copy=False)
+    return torch.from_numpy(np.ascontiguousarray(wav)).to(device)
+
+
+def wav2mel(wav, lengths=None, mel_filter: Optional[MelFilter] = None, device=None, out=None) -> torch.Tensor:
+    """``wav [N, S]`` (float32 or int16 PCM; torch tensor or numpy array) -> ``[N, T, 80]`` float32 log-mel on the device."""
+    if mel_filter is None:
+        if device is None:
+            device = wav.device if isinstance(wav, torch.Tensor) and wav.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        mel_filter = default_mel_filter(device)
+    return mel_filter(_on_device(wav, mel_filter.device), lengths=lengths, out=out)
+
+
+def resynthesize(wav, generator, lengths=None, mel_filter: Optional[MelFilter] = None) -> torch.Tensor:
+    """``generator.forward_ragged(MelFilter(wav), frames)``: ``[N, 256 * T]`` float32, row b's first ``256 * (lengths[b] // 256)``
+    samples valid and the rest zero."""
+    mf = mel_filter or default_mel_filter(generator.device)
+    y = _on_device(wav, generator.device)
+    mel = mf(y, lengths=lengths)
+    lens = [y.shape[1]] * y.shape[0] if lengths is None else [int(v) for v in lengths]
+    return generator.forward_ragged(mel, [mf.num_frames(n) for n in lens])
+
+
+def log_mel_l1(a, b, lengths=None, mel_filter: Optional[MelFilter] = None) -> float:
+    """Mean absolute log-mel difference of two waveform batches of one shape (over each row's own frames)."""
+    if mel_filter is None:
+        dev = a.device if isinstance(a, torch.Tensor) and a.is_cuda else (b.device if isinstance(b, torch.Tensor) and b.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        mel_filter = default_mel_filter(dev)
+    ma = wav2mel(a, lengths, mel_filter)
+    mb = wav2mel(b, lengths, mel_filter)
+    if ma.shape != mb.shape:
+        raise ValueError(f"the two batches differ in shape: {tuple(ma.shape)} vs {tuple(mb.shape)}")
+    d = (ma - mb).abs()
+    if lengths is None:
+        return float(d.mean())
+    frames = torch.tensor([mel_filter.num_frames(int(n)) for n in lengths], device=d.device)
+    valid = (torch.arange(d.shape[1], device=d.device)[None, :] < frames[:, None]).to(d.dtype)
+    return float((d.sum(dim=2) * valid).sum() / (valid.sum() * d.shape[2]))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="wav -> log-mel -> wav through the HiFi-GAN generator on the GPU")
+    ap.add_argument("--input", required=True, help="PCM16 mono .wav at the model's sample rate")
+    ap.add_argument("--output", required=True)
+    ap.add_argument("--dtype", default="f32", choices=("f32", "bf16", "bf16x3"))
+    return ap
+
+
+def main(argv=None) -> None:
+    from .hifigan.mel2wave import _generator
+
+    a = build_parser().parse_args(argv)
+    gen = _generator(a.dtype)  # FileNotFoundError without config / checkpoint, before the input is touched
+    sr, pcm = wavio.read_wav(a.input)
+    if sr != NAT_FLAGS.sample_rate:
+        raise ValueError(f"{a.input}: {sr} Hz, the model runs at {NAT_FLAGS.sample_rate} Hz")
+    wav = resynthesize(pcm.astype(np.int16)[None, :], gen)
+    n = 256 * (len(pcm) // 256)
+    wavio.write_wav(a.output, wav[0, :n].cpu().numpy(), sr)
+    print(f"wrote {a.output}: {n} samples, log-mel L1 against the input {log_mel_l1(wav[:, :n], pcm[None, :n].astype(np.int16)):.4f}")
+
+
+if __name__ == "__main__":
+    main()
