@@ -159,6 +159,36 @@ int vtts_nat_acoustic_forward_groups(vtts_nat_acoustic* h, const int32_t* tokens
                                      const float* durations_dev, const int32_t* nframes_dev, int B, int Lmax, int Fmax,
                                      const uint8_t* keep_dev, float* mel_dev, void* workspace, size_t workspace_bytes, void* stream,
                                      int ngroups, const int32_t* group_row0, const int32_t* group_frames);
+/*
+ * The TEACHER-FORCED pass: AcousticModel(is_training=False).__call__, vietTTS/nat/model.py:146-169 — what vietTTS/nat/gta.py:28-40 runs over a
+ * corpus to dump ground-truth-aligned mels for the vocoder's fine-tuning.  tokens / lengths / durations (FRAMES, fp32, not rounded) / nframes as
+ * for forward(), and
+ *   mels_dev     [B, Fmax, mel_dim] fp32, 16-byte aligned: the TARGET mels; frame f is fed mels[f - 1] (a zero frame first: gta.py:34-36 happens inside)
+ *   keep_dev     [B, Fmax, 2, prenet_dim] bytes, 4-byte aligned: the prenet's keep masks as for forward(), or NULL for no dropout
+ *   zone_dev     [B, Fmax, 4, decoder_dim] bytes: zoneout (model.py:154-166 — on with is_training=False too), 1 = keep the PREVIOUS state, in the
+ *                order layer 0 h, layer 0 c, layer 1 h, layer 1 c; or NULL for no zoneout.  The decoder's output is not zoned out, only the state.
+ *   mel_dev      [B, Fmax, mel_dim] fp32: the mel with the postnet residual (the reference's second return value, what gta.py saves)
+ *   mel_pre_dev  the same shape, or NULL: the mel before the postnet (the first return value)
+ * Rows past nframes[b] are zero in both.  With explicit masks a row's result does not depend on the batch it is in; every sum is a fixed-order
+ * chain.  The prenet, its share of the gates and the projection are GEMMs over all frames ahead of / behind the frame loop, which is two launches
+ * per frame.  `lengths` follows this library's rule (tokens past a row's length do not exist); the reference's corpus run treats the padded
+ * columns of a batch as tokens — pass lengths = Lmax and nframes = Fmax for every row to reproduce that.
+ * fp32 products only: with the option "bf16x3" set the call returns VTTS_ERR_INVALID.  Workspace: forward_teacher_workspace_bytes().
+ */
+int vtts_nat_acoustic_forward_teacher_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, size_t* bytes);
+int vtts_nat_acoustic_forward_teacher(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
+                                      const int32_t* nframes_dev, int B, int Lmax, int Fmax, const float* mels_dev, const uint8_t* keep_dev,
+                                      const uint8_t* zone_dev, float* mel_dev, float* mel_pre_dev, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * keep_dev and zone_dev of forward_teacher() as the REFERENCE draws them from the checkpoint's rng (model.py:149 -> :95-100, :162-165): with
+ * (K_n, S_n) = jax.random.split(K_{n-1}), S_1 and S_2 are the prenet's two dropouts, each ONE draw uniform(S, (B, F, prenet_dim)) < 0.5, and
+ * S_3 .. S_6 are bernoulli(S, 0.1, (B, F, decoder_dim)) for layer 0 h, layer 0 c, layer 1 h, layer 1 c.  Each draw covers the whole tensor, so a
+ * row's masks depend on B, F and its row index (unlike inference, where every sentence gets the same per-frame masks).  threefry_partitionable as
+ * for keep_masks_haiku_mode: 0 = jax.random's classic layout, 1 = the unpinned restatement of JAX >= 0.5's default.
+ * Restatement: tests/_gta_oracle.py::haiku_teacher_masks.
+ */
+int vtts_nat_acoustic_teacher_masks_haiku(const vtts_nat_acoustic* h, uint32_t rng_key0, uint32_t rng_key1, int threefry_partitionable, int B, int F,
+                                          uint8_t* keep_dev, uint8_t* zone_dev, void* stream);
 /* Valid for the groups of the handle's LAST forward_groups() call (VTTS_ERR_STATE otherwise). */
 int vtts_nat_acoustic_wait_group(vtts_nat_acoustic* h, int group, void* stream);
 /*

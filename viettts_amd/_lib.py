@@ -67,6 +67,9 @@ NAT_EXPORTS = (
     "vtts_nat_duration_bind_packed",
     "vtts_nat_duration_workspace_bytes",
     "vtts_nat_duration_forward",
+    "vtts_nat_acoustic_forward_teacher_workspace_bytes",
+    "vtts_nat_acoustic_forward_teacher",
+    "vtts_nat_acoustic_teacher_masks_haiku",
     "vtts_nat_acoustic_create",
     "vtts_nat_acoustic_destroy",
     "vtts_nat_acoustic_set_param",
@@ -247,6 +250,9 @@ def load(path=None) -> C.CDLL:
         "vtts_nat_acoustic_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
         "vtts_nat_acoustic_forward_from_encoder": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp, C.c_int,
                                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "vtts_nat_acoustic_forward_teacher_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
+        "vtts_nat_acoustic_forward_teacher": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "vtts_nat_acoustic_teacher_masks_haiku": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "vtts_mel_create": (C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
         "vtts_mel_destroy": (None, [vp]),
         "vtts_mel_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),

@@ -121,8 +121,8 @@ struct NatModel {
     // an hk.LSTM's [K][4H] matrix in MFMA A-fragment order for nat_dec_lstm_k: [slice = 8 units][K/8][lane][4],
     // element i of lane = W[hrow(8*kb + 4*(lane/32) + i)][gate*H + 8*slice + unit], (unit, gate) = ((lane%32)/4, (lane%32)%4);
     // hrow maps a row of the kernel's state order to the row of the Haiku matrix (identity unless the caller permutes)
-    void add_lstm_mfma(const std::string& mod, int K, int H, std::function<int(int)> hrow = nullptr) {
-        add_extra(mod + "#mfma", (size_t)K * 4 * H * sizeof(float), [mod, K, H, hrow](const NatModel& m, float* out) {
+    void add_lstm_mfma(const std::string& mod, int K, int H, std::function<int(int)> hrow = nullptr, const char* key = "#mfma") {
+        add_extra(mod + key, (size_t)K * 4 * H * sizeof(float), [mod, K, H, hrow](const NatModel& m, float* out) {
             const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
             const int NIT = K / 8;
             for (int sl = 0; sl < H / 8; ++sl)
@@ -339,13 +339,18 @@ __global__ __launch_bounds__(256) void nat_conv_bn_act_k(const float* __restrict
 // Now the 64 + K - 1 rows x 32 channels of a step are staged ONCE (coalesced float4 loads along the channels, next step's in flight under this
 // step's MFMAs, two LDS buffers, one barrier per step), the taps are shifted views of the tile, and a fragment is one ds_read_b32 per lane
 // (row stride 33 floats: 32 consecutive frames of one channel hit 32 banks).  The fmaf chains are the old ones, in the old order: same bits.
-template <int K, int MR>
+// TF (the teacher-forced pass's GEMMs, compile-time, 0 everywhere else): NAT_TF_SHIFT = row t reads x[t - 1], a zero row first (the target mels become
+// the decoder's inputs without a shifted copy); NAT_TF_KEEP = hk.dropout(0.5) after the activation, v = keep[b][t][co] ? 2 v : 0 with keep rows 2 * Cout
+// bytes apart (the prenet's [B][F][2][PN] masks, the pointer already at the layer's half); NAT_TF_ACC = y += the result, the previous value read
+// through y itself (res is not used: y is the only pointer to that array).
+enum : int { NAT_TF_SHIFT = 1, NAT_TF_KEEP = 2, NAT_TF_ACC = 4 };
+template <int K, int MR, int TF = 0>
 __global__ __launch_bounds__(256, 2) void nat_conv_mfma_k(const float* __restrict__ x, const int* __restrict__ lengths, const float4* __restrict__ wpk,
                                                        const float* __restrict__ bias, const float* __restrict__ inv, const float* __restrict__ mean,
                                                        const float* __restrict__ offset, const float* __restrict__ res, float* __restrict__ y, int Lmax,
-                                                       int Cin, int Cout, int act, int tile0) {
+                                                       int Cin, int Cout, int act, int tile0, const unsigned char* __restrict__ keep = nullptr) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
-    constexpr int NR = 2, PL = (K - 1) / 2, ROWS = 64 + K - 1, RS = 33, UNITS = ROWS * 8, UPT = (UNITS + 255) / 256;
+    constexpr int NR = 2, PL = (K - 1) / 2 + ((TF & NAT_TF_SHIFT) ? 1 : 0), ROWS = 64 + K - 1, RS = 33, UNITS = ROWS * 8, UPT = (UNITS + 255) / 256;
     __shared__ float xs[2][ROWS * RS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int b = blockIdx.z, t0 = (blockIdx.x + tile0) * 64;  // tile0: a launch may cover the 64-frame tiles [tile0, tile0 + gridDim.x) only
@@ -488,7 +493,14 @@ __global__ __launch_bounds__(256, 2) void nat_conv_mfma_k(const float* __restric
                     if (act == NAT_ACT_RELU) v[i] = fmaxf(v[i], 0.0f);
                     else if (act == NAT_ACT_TANH) v[i] = tanhf(v[i]);
                 }
-                if (res) {
+                if constexpr ((TF & NAT_TF_KEEP) != 0) {
+                    const uchar4 k4 = *reinterpret_cast<const uchar4*>(keep + ((size_t)b * Lmax + t) * 2 * Cout + co);
+                    v[0] = k4.x ? v[0] * 2.0f : 0.0f; v[1] = k4.y ? v[1] * 2.0f : 0.0f; v[2] = k4.z ? v[2] * 2.0f : 0.0f; v[3] = k4.w ? v[3] * 2.0f : 0.0f;
+                }
+                if constexpr ((TF & NAT_TF_ACC) != 0) {
+                    const float4 r = *reinterpret_cast<const float4*>(y + o);
+                    v[0] = r.x + v[0]; v[1] = r.y + v[1]; v[2] = r.z + v[2]; v[3] = r.w + v[3];
+                } else if (res) {
                     const float4 r = *reinterpret_cast<const float4*>(res + o);
                     v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
                 }
@@ -1197,7 +1209,7 @@ __global__ __launch_bounds__(256) void nat_enc_gather_k(const float* __restrict_
 // the 64 output bits are the keep flags of 64 consecutive prenet columns (P(keep) = 1/2 = 1 - rate, model.py:97,99).
 // This is a stream of our own (one seed per sentence, for batches of unrelated sentences); the reference's schedule from the
 // checkpoint's rng is nat_keep_masks_haiku_k below.
-__device__ __forceinline__ void threefry2x32_20(unsigned k0, unsigned k1, unsigned& x0, unsigned& x1) {
+__host__ __device__ __forceinline__ void threefry2x32_20(unsigned k0, unsigned k1, unsigned& x0, unsigned& x1) {
     const unsigned ks[3] = {k0, k1, 0x1BD11BDAu ^ k0 ^ k1};
     const int R[8] = {13, 15, 26, 6, 17, 29, 16, 24};
     x0 += ks[0];
@@ -1418,6 +1430,193 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
 // (Round 6 cut the projection + prenet step along its WEIGHTS — a workgroup = a 32-sentence tile x a slice of a matrix, two launches per frame over 64-workgroup
 //  grids, every load requested before the first wait — and measured it SLOWER: 6.7 + 24.0 us per frame against this kernel's 15.2, the acoustic model 17.0 ms against
 //  12.5 (profiles/r06_c_nat_proj_prenet_findings.md).)
+// ---- the TEACHER-FORCED pass: AcousticModel.__call__ (model.py:146-169), the forward vietTTS/nat/gta.py:28-40 runs to dump ground-truth-aligned mels ----
+// The previous mel of every frame is the (shifted) TARGET mel, known before the loop.  So besides the conditioning's share of the gates, the prenet
+// (two bias-free GEMMs over all B x F rows), the prenet's share of both LSTMs' gates (G_l += p @ W_l[E : E + PN]) and the mel projection leave the
+// frame loop — all on nat_conv_mfma_k with one tap — and a frame is TWO launches of the step kernel below: K = H for layer 1 (its own state) and
+// 2H for layer 2 (layer 1's fresh output, then its own state); the inference loop has PN + H and PN + 2H there, plus the projection / prenet launch.
+// New in the step is zoneout, applied by the reference with is_training=False too (model.py:154-166): state = m * prev + (1 - m) * new for h and c of
+// both layers (m in {0, 1}: a select), while the decoder OUTPUT [h1_new ; h2_new] — what layer 2 and the projection see — is not zoned out.
+//
+// nat_tf_lstm_k: nat_dec_lstm_k's tiling, operand order, K split and in-register cell update (the sums are the same chains in the same order: see the
+// comments there), one operand set, SL = 1.  Its epilogue writes the un-zoned h to hseq [B][Fmax][2H] (the projection GEMM's input) and, for layer 1,
+// to `hfresh` in state layout (layer 2's first H rows of this frame), and the zoned h / c to the recurrent state (h ping-pong by frame parity: the
+// other workgroups of this launch still read the previous one).  Hidden state buffers are [H / 4][Bp][4] (nat_zidx), cell states [H][Bp].
+// zone [B][Fmax][4][H] bytes (l0.h, l0.c, l1.h, l1.c; 1 = keep the previous state), nullptr = no zoneout.
+struct NatTfOps {
+    const float* inA;           // KA state rows (layer 2: layer 1's un-zoned output of this frame), then
+    const float* inB;           // KB = H rows: the layer's own zoned hidden state of the previous frame
+    const float4* wpk;          // [slice][K/8][lane][4]
+    float* cst;                 // zoned cell state [H][Bp]
+    float* hstate;              // zoned hidden state of this frame
+    float* hfresh;              // un-zoned hidden state in state layout, or nullptr (layer 2: nobody reads it)
+    float* hseq;                // un-zoned hidden state, [B][Fmax][2H] + layer * H
+    const float* gin;           // this frame's hoisted gate pre-activations, accumulator order (NatLstmOps::gin)
+    size_t gpitch;
+    const unsigned char* zone;  // [B][Fmax][4][H] + 2 * layer * H, or nullptr
+};
+template <int NT, int KW>
+__global__ __launch_bounds__(64 * KW) void nat_tf_lstm_k(NatTfOps ops, int KA, int KB, const int* __restrict__ nframes, int f, int B, int Bp, int H, int Fmax) {
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    static_assert(KW == 2 || KW == 4 || KW == 8, "the K shares meet in LDS");
+    __shared__ float red[KW][NT][16][64];
+    const float* __restrict__ inA = ops.inA;
+    const float* __restrict__ inB = ops.inB;
+    const float4* __restrict__ wpk = ops.wpk;
+    float* __restrict__ cst = ops.cst;
+    const int lane = threadIdx.x & 63, kw = threadIdx.x >> 6, l31 = lane & 31, lh = lane >> 5;
+    const int slice0 = blockIdx.x, b0 = blockIdx.y * 32 * NT;
+    const int NIT = (KA + KB) / 8, NWMAX = (NIT + KW - 1) / KW, it_lo = kw * NWMAX;
+    const int NW = it_lo >= NIT ? 0 : (NIT - it_lo < NWMAX ? NIT - it_lo : NWMAX);
+    // this wave's cell-update blocks: previous cell and hidden state and the zoneout bytes are requested a kernel's length before they are needed
+    constexpr int NBLK = (NT * 4 + KW - 1) / KW;
+    float cold[NBLK], hold[NBLK];
+    unsigned char zh[NBLK], zc[NBLK];
+#pragma unroll
+    for (int q = 0; q < NBLK; ++q) {
+        const int blk = kw + q * KW, nt = (blk / 4) % NT, rq = blk % 4;
+        const bool in = blk < NT * 4;
+        const int u = 8 * slice0 + 2 * rq + lh, b = b0 + 32 * nt + l31;
+        cold[q] = in ? cst[(size_t)u * Bp + b] : 0.0f;
+        hold[q] = in ? inB[nat_zidx(u, b, Bp)] : 0.0f;
+        const unsigned char* __restrict__ zp = ops.zone ? ops.zone + ((size_t)(b < B ? b : B - 1) * Fmax + f) * 4 * H + u : nullptr;
+        zh[q] = (in && zp) ? zp[0] : (unsigned char)0;
+        zc[q] = (in && zp) ? zp[H] : (unsigned char)0;
+    }
+    f32x16 acc[NT][2];
+    if (kw == 0) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int b = b0 + 32 * nt + l31;
+            const float4* __restrict__ gp = reinterpret_cast<const float4*>(ops.gin + (size_t)(b < B ? b : B - 1) * ops.gpitch + (size_t)(2 * slice0 + lh) * 16);
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const float4 g4 = gp[rq];
+                acc[nt][0][4 * rq + 0] = g4.x;
+                acc[nt][0][4 * rq + 1] = g4.y;
+                acc[nt][0][4 * rq + 2] = g4.z;
+                acc[nt][0][4 * rq + 3] = g4.w;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[nt][1][4 * rq + i] = 0.0f;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                acc[nt][0][r] = 0.0f;
+                acc[nt][1][r] = 0.0f;
+            }
+    }
+    float4 wv[NAT_DEC_PD];
+    float4 xv[NAT_DEC_PD][NT];
+    const float4* __restrict__ wsl = wpk + (size_t)slice0 * NIT * 64 + lane;
+    auto load_it = [&](int it, int slot) {
+        if (it >= NIT) it = NIT - 1;  // tail: an in-bounds re-read, never used
+        wv[slot] = wsl[(size_t)it * 64];
+        const int k0 = it * 8;
+        const float* __restrict__ xr = (k0 < KA ? inA + (size_t)k0 * Bp : inB + (size_t)(k0 - KA) * Bp) + ((size_t)lh * Bp + b0 + l31) * 4;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) xv[slot][nt] = *reinterpret_cast<const float4*>(xr + (size_t)(32 * nt) * 4);
+    };
+#pragma unroll
+    for (int j = 0; j < NAT_DEC_PD; ++j) load_it(it_lo + j, j);
+    bool live[NT];
+    bool any = false;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int b = b0 + 32 * nt + l31;
+        live[nt] = b < B && f < nframes[b < B ? b : B - 1];
+        any = any || live[nt];
+    }
+    if (__ballot(any) == 0ull) return;  // every sentence of these tiles has all its frames (same for all waves)
+#pragma nounroll
+    for (int it0 = 0; it0 < NW; it0 += NAT_DEC_PD) {
+#pragma unroll
+        for (int j = 0; j < NAT_DEC_PD; ++j) {
+            if (it0 + j >= NW) break;  // wave-uniform
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[nt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[j].x, xv[j][nt].x, acc[nt][0], 0, 0, 0);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[nt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[j].y, xv[j][nt].y, acc[nt][1], 0, 0, 0);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[nt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[j].z, xv[j][nt].z, acc[nt][0], 0, 0, 0);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[nt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[j].w, xv[j][nt].w, acc[nt][1], 0, 0, 0);
+            const int nx = it0 + j + NAT_DEC_PD;
+            load_it(nx < NW ? it_lo + nx : NIT, j);
+        }
+    }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[kw][nt][r][lane] = acc[nt][0][r] + acc[nt][1][r];
+    __syncthreads();
+#pragma unroll
+    for (int blk = 0; blk < NT * 4; ++blk) {
+        if (blk % KW != kw) continue;  // wave-uniform
+        const int nt = (blk / 4) % NT, rq = blk % 4, q = blk / KW;
+        float gs[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float v = red[0][nt][4 * rq + i][lane];
+#pragma unroll
+            for (int w = 1; w < KW; ++w) v += red[w][nt][4 * rq + i][lane];
+            gs[i] = v;
+        }
+        if (!live[nt]) continue;  // frames past the sentence's last: neither state nor output is touched
+        const int b = b0 + 32 * nt + l31, u = 8 * slice0 + 2 * rq + lh;
+        const float cn = sigmoidf_(gs[2] + 1.0f) * cold[q] + sigmoidf_(gs[0]) * tanhf(gs[1]);
+        const float hn = sigmoidf_(gs[3]) * tanhf(cn);
+        ops.hseq[((size_t)b * Fmax + f) * 2 * H + u] = hn;
+        if (ops.hfresh) ops.hfresh[nat_zidx(u, b, Bp)] = hn;
+        cst[(size_t)u * Bp + b] = zc[q] ? cold[q] : cn;
+        ops.hstate[nat_zidx(u, b, Bp)] = zh[q] ? hold[q] : hn;
+    }
+}
+
+// The masks of the teacher-forced pass as the REFERENCE draws them (model.py:149 -> :95-100, :162-165): six subkeys S_1 .. S_6 of the chain
+// (K_n, S_n) = split(K_{n-1}) from the checkpoint's rng (walked on the host: 12 ciphers), each ONE draw over a whole [B][F][D] tensor — S_1, S_2
+// the prenet's keep masks (uniform < 0.5, D = PN), S_3 .. S_6 bernoulli(0.1) for l0.h, l0.c, l1.h, l1.c (D = H).  Element i of n = B F D (row-major)
+// in jax.random's classic layout: word x0 of the counter pair (i, i + half) for i < half = n / 2, else word x1 of (i - half, i); jax pads an odd n
+// with one zero count, which cannot occur here (PN and H are multiples of 32).  uniform = bitcast((word >> 9) | 0x3F800000) - 1.0f, compared in fp32 as jax does.  A row's masks therefore depend
+// on B, F and its row index.  mode 1 = jax_threefry_partitionable (word = y0 ^ y1 of the cipher on the 64-bit index; unpinned, as in
+// nat_keep_masks_haiku_k).  One thread per mask byte.
+struct NatTeacherKeys {
+    unsigned k[6][2];
+};
+__global__ void nat_teacher_masks_k(NatTeacherKeys keys, int mode, unsigned char* __restrict__ keep, unsigned char* __restrict__ zone, int B, int F, int PN, int H) {
+    const size_t rows = (size_t)B * F, per = 2 * (size_t)PN + 4 * (size_t)H, total = rows * per;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t row = idx / per;
+        int r = (int)(idx % per), d, c, D;
+        unsigned char* dst;
+        if (r < 2 * PN) {
+            d = r / PN, c = r % PN, D = PN;
+            dst = keep + row * 2 * PN + r;
+        } else {
+            r -= 2 * PN;
+            d = 2 + r / H, c = r % H, D = H;
+            dst = zone + row * 4 * H + r;
+        }
+        const size_t n = rows * D, i = row * D + c;
+        unsigned word;
+        if (mode == 0) {
+            const size_t half = n / 2, j = i < half ? i : i - half;  // n is even (D is a multiple of 32: create()), so jax's zero pad of an odd count never occurs
+            unsigned x0 = (unsigned)j, x1 = (unsigned)(j + half);
+            threefry2x32_20(keys.k[d][0], keys.k[d][1], x0, x1);
+            word = i < half ? x0 : x1;
+        } else {
+            unsigned x0 = (unsigned)(i >> 32), x1 = (unsigned)i;
+            threefry2x32_20(keys.k[d][0], keys.k[d][1], x0, x1);
+            word = x0 ^ x1;
+        }
+        const float u = __builtin_bit_cast(float, (word >> 9) | 0x3F800000u) - 1.0f;
+        *dst = (unsigned char)(u < (d < 2 ? 0.5f : 0.1f) ? 1 : 0);
+    }
+}
+
 // ---- shared host-side sequence: TokenEncoder of `m` under module prefix `te` -> enc [B][Lmax][2D] ------------------
 // scratch of the two encoder LSTMs: XT[2][Lmax], HS[2][Lmax + 1] slabs of [D][Bp] and the two cell states
 size_t nat_enc_lstm_floats(int D, int B, int Lmax) {
@@ -1714,6 +1913,37 @@ VTTS_API int vtts_nat_acoustic_create(const vtts_nat_acoustic_cfg* cfg, int devi
             for (int cp = 0; cp < G4; ++cp) out[cp] = 0.0f;
         });
     }
+    // The teacher-forced pass (nat_acoustic_run with a NatTeacher): the step multiplies the recurrent rows only — "#tf" = Haiku rows E + PN + r, [h1] for
+    // layer 1 and [h1 ; h2] for layer 2, in the step kernel's order — and everything known ahead of the loop is a one-tap nat_conv_mfma_k GEMM:
+    // "#pre" = the prenet's rows [E, E + PN) of the LSTM matrices with the columns in accumulator order (as "#cond"), "linear_1#mfma" / "linear_2#mfma" the
+    // prenet's own matrices and "linear#mfma" the mel projection, columns as they are.
+    h->add_lstm_mfma("lstm/linear", H, H, [E, PN](int zr) { return E + PN + zr; }, "#tf");
+    h->add_lstm_mfma("lstm_1/linear", 2 * H, H, [E, PN](int zr) { return E + PN + zr; }, "#tf");
+    auto add_gemm = [h](const std::string& key, const std::string& mod, int row0, int cin, int cout, int ncols, std::function<int(int)> col) {
+        const int MB = (cout + 31) / 32, NCS = (cin + 31) / 32;
+        h->add_extra(key, (size_t)MB * NCS * 64 * 16 * sizeof(float), [mod, row0, cin, cout, ncols, col, MB, NCS](const NatModel& m, float* out) {
+            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
+            for (int mb = 0; mb < MB; ++mb)
+                for (int cs = 0; cs < NCS; ++cs)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int e = 0; e < 16; ++e) {
+                            const int c = 32 * cs + 16 * (lane >> 5) + e, co = 32 * mb + (lane & 31);
+                            out[(((size_t)mb * NCS + cs) * 64 + lane) * 16 + e] = (c < cin && co < cout) ? W[(size_t)(row0 + c) * ncols + (col ? col(co) : co)] : 0.0f;
+                        }
+        });
+    };
+    {
+        const int G4 = 4 * H;
+        auto hcol = [H](int cp) { return (cp & 3) * H + 8 * (cp >> 5) + 2 * ((cp >> 2) & 3) + ((cp >> 4) & 1); };  // accumulator-order column -> Haiku column
+        add_gemm("lstm/linear#pre", "lstm/linear", E, PN, G4, G4, hcol);
+        add_gemm("lstm_1/linear#pre", "lstm_1/linear", E, PN, G4, G4, hcol);
+        add_gemm("linear_1#mfma", "linear_1", 0, MEL, PN, PN, nullptr);
+        add_gemm("linear_2#mfma", "linear_2", 0, PN, PN, PN, nullptr);
+        add_gemm("linear#mfma", "linear", 0, 2 * H, MEL, MEL, nullptr);
+        h->add_extra("prenet#zerob", (size_t)PN * sizeof(float), [PN](const NatModel&, float* out) {
+            for (int c = 0; c < PN; ++c) out[c] = 0.0f;
+        });
+    }
     h->layout();
     *out = h;
     return VTTS_OK;
@@ -1779,6 +2009,16 @@ VTTS_API int vtts_nat_acoustic_workspace_bytes(const vtts_nat_acoustic* h, int B
              + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256);                                    // encoder LSTMs' scratch
     return VTTS_OK;
 }
+// what the teacher-forced pass needs beyond forward()'s layout: the prenet's two layers, the hidden sequence, the recurrent state
+static size_t nat_teacher_extra_bytes(const vtts_nat_acoustic_cfg& c, int B, int Fmax) {
+    const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, BF = (size_t)B * Fmax;
+    return 2 * align_up(BF * c.prenet_dim * 4, 256) + align_up(BF * 2 * H * 4, 256) + align_up(7 * H * Bp * 4, 256);
+}
+VTTS_API int vtts_nat_acoustic_forward_teacher_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, size_t* bytes) {
+    if (int rc = vtts_nat_acoustic_workspace_bytes(h, B, Lmax, Fmax, bytes)) return rc;
+    *bytes += nat_teacher_extra_bytes(h->cfg, B, Fmax);
+    return VTTS_OK;
+}
 VTTS_API int vtts_nat_acoustic_keep_masks(const vtts_nat_acoustic* h, const uint64_t* seeds_dev, int B, int Fmax, uint8_t* keep_dev, void* stream) {
     if (!h || !seeds_dev || !keep_dev) return failf(VTTS_ERR_INVALID, "null argument");
     if (B <= 0 || Fmax <= 0) return failf(VTTS_ERR_INVALID, "B and Fmax must be positive (got %d, %d)", B, Fmax);
@@ -1808,18 +2048,57 @@ VTTS_API int vtts_nat_acoustic_keep_masks_haiku(const vtts_nat_acoustic* h, uint
                                                 void* stream) {
     return vtts_nat_acoustic_keep_masks_haiku_mode(h, rng_key0, rng_key1, 0, B, Fmax, keep_dev, stream);
 }
+VTTS_API int vtts_nat_acoustic_teacher_masks_haiku(const vtts_nat_acoustic* h, uint32_t rng_key0, uint32_t rng_key1, int threefry_partitionable, int B, int F,
+                                                   uint8_t* keep_dev, uint8_t* zone_dev, void* stream) {
+    if (!h || !keep_dev || !zone_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (B <= 0 || F <= 0) return failf(VTTS_ERR_INVALID, "B and F must be positive (got %d, %d)", B, F);
+    if (threefry_partitionable != 0 && threefry_partitionable != 1) return failf(VTTS_ERR_INVALID, "threefry_partitionable must be 0 (classic layout) or 1");
+    const int PN = h->cfg.prenet_dim, H = h->cfg.decoder_dim;
+    if ((size_t)B * F * (size_t)(PN > H ? PN : H) >= ((size_t)1 << 31)) return failf(VTTS_ERR_INVALID, "a mask draw of %d x %d frames exceeds 2^31 elements", B, F);
+    NatTeacherKeys keys;
+    unsigned ka = rng_key0, kb = rng_key1;
+    for (int n = 0; n < 6; ++n) {  // (K_n, S_n) = jax.random.split(K_{n-1}): as nat_keep_masks_haiku_k walks it
+        unsigned a0, b0, a1, b1;
+        if (threefry_partitionable == 0) {
+            a0 = 0u, b0 = 2u, a1 = 1u, b1 = 3u;
+            threefry2x32_20(ka, kb, a0, b0);
+            threefry2x32_20(ka, kb, a1, b1);
+            keys.k[n][0] = b0, keys.k[n][1] = b1;
+            ka = a0, kb = a1;
+        } else {
+            a0 = 0u, b0 = 0u, a1 = 0u, b1 = 1u;
+            threefry2x32_20(ka, kb, a0, b0);
+            threefry2x32_20(ka, kb, a1, b1);
+            keys.k[n][0] = a1, keys.k[n][1] = b1;
+            ka = a0, kb = b0;
+        }
+    }
+    const size_t total = (size_t)B * F * (2 * (size_t)PN + 4 * (size_t)H);
+    const int blocks = (int)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535);
+    hipLaunchKernelGGL(nat_teacher_masks_k, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), keys, threefry_partitionable, keep_dev, zone_dev, B, F, PN, H);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "teacher-mask launch failed: %s", hipGetErrorString(e));
+    return VTTS_OK;
+}
+// forward_teacher()'s extra operands (nullptr for the inference entry points)
+struct NatTeacher {
+    const float* mels;    // [B][Fmax][MEL] target mels (the one-frame shift happens here)
+    const uint8_t* zone;  // [B][Fmax][4][H] or nullptr
+    float* mel_pre;       // optional: the decoder's mel before the postnet residual
+};
 // forward() and forward_groups(): ngroups = 0 is the plain call (the postnet on the caller's stream after the last frame)
 // enc_pre: the token encoder's output [B][Lmax][2D] computed ahead by vtts_nat_acoustic_encode() (tokens_dev is not read then), or nullptr
 static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
                             const int32_t* nframes_dev, int B, int Lmax, int Fmax, const uint8_t* keep_dev, float* mel_dev, void* workspace,
                             size_t workspace_bytes, void* stream, int ngroups, const int32_t* group_row0, const int32_t* group_frames,
-                            const float* enc_pre = nullptr) {
+                            const float* enc_pre = nullptr, const NatTeacher* tf = nullptr) {
     if (!h || (!tokens_dev && !enc_pre) || !lengths_dev || !durations_dev || !nframes_dev || !mel_dev) return failf(VTTS_ERR_INVALID, "null argument");
     if (!h->blob) return failf(VTTS_ERR_STATE, "forward() before pack()/bind_packed()");
     size_t need = 0;
-    int rc = vtts_nat_acoustic_workspace_bytes(h, B, Lmax, Fmax, &need);
+    int rc = tf ? vtts_nat_acoustic_forward_teacher_workspace_bytes(h, B, Lmax, Fmax, &need) : vtts_nat_acoustic_workspace_bytes(h, B, Lmax, Fmax, &need);
     if (rc) return rc;
     if (!workspace || workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    if (tf && h->x3) return failf(VTTS_ERR_INVALID, "forward_teacher() has fp32 products only: clear the option bf16x3 (there is no split-operand teacher-forced step)");
     if (Lmax > 2048) return failf(VTTS_ERR_INVALID, "at most 2048 tokens per sentence (upsampling weights live in LDS)");
     h->groups_valid = 0;
     if (ngroups > 0) {
@@ -1903,7 +2182,78 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
             cur = dst;
         }
     };
-    {  // autoregressive decoder (:134-150): per frame LSTM1, LSTM2, projection + next frame's prenet, all sentences at once
+    if (tf) {  // teacher-forced decoder (model.py:146-167): everything but the two LSTMs' recurrent products ahead of the frame loop
+        const int Bp = (B + 63) / 64 * 64;
+        const size_t BF = (size_t)B * Fmax, HB = (size_t)H * Bp;
+        float* P1 = take(BF * PN * 4);
+        float* P2 = take(BF * PN * 4);
+        float* hseq = take(BF * 2 * H * 4);
+        float* tstate = take(7 * HB * 4);
+        float* hz1[2] = {tstate, tstate + HB};  // zoned h1, ping-pong by frame parity
+        float* hz2[2] = {tstate + 2 * HB, tstate + 3 * HB};
+        float* hf1 = tstate + 4 * HB;           // layer 1's un-zoned output of the frame in flight
+        float* c1 = tstate + 5 * HB;
+        float* c2 = tstate + 6 * HB;
+        if (G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: the gate mix wants 4 * decoder_dim in multiples of 1024", H);
+        HIP_TRYN(hipMemsetAsync(tstate, 0, 7 * HB * 4, s));
+        HIP_TRYN(hipMemsetAsync(mel0, 0, BF * MEL * 4, s));
+        // one-tap nat_conv_mfma_k = a GEMM over a sentence's frames: y[b][f] = epilogue(act(x[b][f] @ W + bias)), epilogue TF as described at the kernel;
+        // rows past nframes are not computed
+        auto gemm = [&](auto tfc, const float* x, const int32_t* rows, int L, const std::string& key, const float* bias, float* y, int cin, int cout, int act,
+                        const uint8_t* kp = nullptr) {
+            constexpr int TF = decltype(tfc)::value;
+            const int MB = (cout + 31) / 32;
+            const float4* w = reinterpret_cast<const float4*>(h->extra(key));
+            if (MB >= 8)
+                hipLaunchKernelGGL((nat_conv_mfma_k<1, 2, TF>), dim3((L + 63) / 64, (MB + 7) / 8, B), dim3(256), 0, s, x, rows, w, bias, nullptr, nullptr, nullptr, nullptr, y,
+                                   L, cin, cout, act, 0, kp);
+            else
+                hipLaunchKernelGGL((nat_conv_mfma_k<1, 1, TF>), dim3((L + 63) / 64, (MB + 3) / 4, B), dim3(256), 0, s, x, rows, w, bias, nullptr, nullptr, nullptr, nullptr, y,
+                                   L, cin, cout, act, 0, kp);
+        };
+        using TfNone = std::integral_constant<int, 0>;
+        using TfShift = std::integral_constant<int, NAT_TF_SHIFT>;
+        using TfShiftKeep = std::integral_constant<int, NAT_TF_SHIFT | NAT_TF_KEEP>;
+        using TfKeep = std::integral_constant<int, NAT_TF_KEEP>;
+        using TfAcc = std::integral_constant<int, NAT_TF_ACC>;
+        // G_l = b_l + cond @ W_l[0:E] for every frame: forward()'s token-rows GEMM and mix
+        gemm(TfNone{}, enc, lengths_dev, Lmax, "lstm/linear#cond", h->extra("lstm/linear#zerob"), EG1, E, G4, (int)NAT_ACT_NONE);
+        gemm(TfNone{}, enc, lengths_dev, Lmax, "lstm_1/linear#cond", h->extra("lstm_1/linear#zerob"), EG2, E, G4, (int)NAT_ACT_NONE);
+        const size_t mlds = ((size_t)(Lmax + 3) / 4 * 4 + (size_t)Lmax * NAT_MIX_FT) * sizeof(float);
+        if (mlds > 48 * 1024)
+            HIP_TRYN(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_gates_mix_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
+        hipLaunchKernelGGL(nat_gates_mix_k, dim3((Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT, 2 * (G4 / 1024), B), dim3(256), mlds, s, EG1, EG2, h->extra("lstm/linear#condb"),
+                           h->extra("lstm_1/linear#condb"), lengths_dev, durations_dev, nframes_dev, G1, G2, Lmax, Fmax, G4, 0);
+        // prenet(inp_mels) over all frames (:149, :95-100), the one-frame shift of the target mels (gta.py:34-36) in the first GEMM's staging, relu and the
+        // dropout's keep x 2 in both epilogues
+        const float* zb = h->extra("prenet#zerob");
+        if (keep_dev) {
+            gemm(TfShiftKeep{}, tf->mels, nframes_dev, Fmax, "linear_1#mfma", zb, P1, MEL, PN, (int)NAT_ACT_RELU, keep_dev);
+            gemm(TfKeep{}, P1, nframes_dev, Fmax, "linear_2#mfma", zb, P2, PN, PN, (int)NAT_ACT_RELU, keep_dev + PN);
+        } else {
+            gemm(TfShift{}, tf->mels, nframes_dev, Fmax, "linear_1#mfma", zb, P1, MEL, PN, (int)NAT_ACT_RELU);
+            gemm(TfNone{}, P1, nframes_dev, Fmax, "linear_2#mfma", zb, P2, PN, PN, (int)NAT_ACT_RELU);
+        }
+        // G_l += p @ W_l[E : E + PN], onto the mix's output
+        gemm(TfAcc{}, P2, nframes_dev, Fmax, "lstm/linear#pre", h->extra("lstm/linear#zerob"), G1, PN, G4, (int)NAT_ACT_NONE);
+        gemm(TfAcc{}, P2, nframes_dev, Fmax, "lstm_1/linear#pre", h->extra("lstm_1/linear#zerob"), G2, PN, G4, (int)NAT_ACT_NONE);
+        const float4* w1 = reinterpret_cast<const float4*>(h->extra("lstm/linear#tf"));
+        const float4* w2 = reinterpret_cast<const float4*>(h->extra("lstm_1/linear#tf"));
+        const bool wide = B > 32;
+        const dim3 lgrid(H / 8, wide ? Bp / 64 : 1);
+        auto step = [&](const NatTfOps& o, int KA, int f) {
+            if (wide) hipLaunchKernelGGL((nat_tf_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, H, nframes_dev, f, B, Bp, H, Fmax);
+            else hipLaunchKernelGGL((nat_tf_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, H, nframes_dev, f, B, Bp, H, Fmax);
+        };
+        const size_t gp = (size_t)Fmax * G4;
+        for (int f = 0; f < Fmax; ++f) {
+            const int cur = f & 1, prv = cur ^ 1;
+            step(NatTfOps{hz1[prv], hz1[prv], w1, c1, hz1[cur], hf1, hseq, G1 + (size_t)f * G4, gp, tf->zone}, 0, f);
+            step(NatTfOps{hf1, hz2[prv], w2, c2, hz2[cur], nullptr, hseq + H, G2 + (size_t)f * G4, gp, tf->zone ? tf->zone + 2 * (size_t)H : nullptr}, H, f);
+        }
+        gemm(TfNone{}, hseq, nframes_dev, Fmax, "linear#mfma", h->dev("linear", "b"), mel0, 2 * H, MEL, (int)NAT_ACT_NONE);  // :167
+        if (tf->mel_pre) HIP_TRYN(hipMemcpyAsync(tf->mel_pre, mel0, BF * MEL * 4, hipMemcpyDeviceToDevice, s));
+    } else {  // autoregressive decoder (:134-150): per frame LSTM1, LSTM2, projection + next frame's prenet, all sentences at once
         const int Bp = (B + 63) / 64 * 64, ZW = PN + 2 * H;
         float* Z[2] = {dstate, dstate + (size_t)ZW * Bp};
         float* c1 = dstate + 2 * (size_t)ZW * Bp;
@@ -2023,6 +2373,18 @@ VTTS_API int vtts_nat_acoustic_forward_groups(vtts_nat_acoustic* h, const int32_
     if (ngroups < 1) return failf(VTTS_ERR_INVALID, "forward_groups() needs at least one group (got %d)", ngroups);
     return nat_acoustic_run(h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, stream,
                             ngroups, group_row0, group_frames);
+}
+
+// The teacher-forced pass (AcousticModel.__call__, model.py:146-169): the token encoder, forward()'s postnet, and the decoder fed with the target mels
+VTTS_API int vtts_nat_acoustic_forward_teacher(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
+                                               const int32_t* nframes_dev, int B, int Lmax, int Fmax, const float* mels_dev, const uint8_t* keep_dev,
+                                               const uint8_t* zone_dev, float* mel_dev, float* mel_pre_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!tokens_dev || !mels_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if ((uintptr_t)mels_dev % 16 != 0 || (uintptr_t)keep_dev % 4 != 0)
+        return failf(VTTS_ERR_INVALID, "forward_teacher() reads mels_dev in 16-byte and keep_dev in 4-byte units: align them so");
+    const NatTeacher tf{mels_dev, zone_dev, mel_pre_dev};
+    return nat_acoustic_run(h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, stream, 0, nullptr,
+                            nullptr, nullptr, &tf);
 }
 
 // The token encoder alone, ahead of forward_from_encoder(): it needs the tokens only, so a pipeline can run it while the host still turns the

@@ -152,6 +152,124 @@ class AcousticModel:
                                                                                   _ptr(keep), C.c_void_p(stream.cuda_stream)))
         return keep
 
+    def device_teacher_masks_haiku(self, rng_key, B: int, F: int, partitionable: Optional[bool] = None):
+        """The masks of :meth:`teacher_forced` as the REFERENCE draws them from the checkpoint's ``rng`` (model.py:149, :162-165; include/vtts_nat.h:
+        vtts_nat_acoustic_teacher_masks_haiku): ``(keep [B, F, 2, prenet_dim], zone [B, F, 4, decoder_dim])`` uint8 on the device.  Each of the six
+        draws covers the whole ``(B, F, D)`` tensor, so a row's masks depend on ``B``, ``F`` and its row index.  ``partitionable`` as for
+        :meth:`device_keep_masks_haiku` (mode 1 is the same unpinned restatement)."""
+        if partitionable is None:
+            partitionable = os.environ.get("VTTS_JAX_THREEFRY_PARTITIONABLE", "0") not in ("", "0")
+        _log_stream_once(bool(partitionable))
+        k = np.asarray(rng_key, dtype=np.uint32).reshape(2)
+        keep = torch.empty((int(B), int(F), 2, self.prenet_dim), dtype=torch.uint8, device=self.device)
+        zone = torch.empty((int(B), int(F), 4, int(self.cfg.decoder_dim)), dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib, self.lib.vtts_nat_acoustic_teacher_masks_haiku(self._h, int(k[0]), int(k[1]), int(bool(partitionable)), int(B), int(F), _ptr(keep),
+                                                                                _ptr(zone), C.c_void_p(stream.cuda_stream)))
+        return keep, zone
+
+    def _mask_tensor(self, m, B: int, Fmax: int, inner: tuple) -> torch.Tensor:
+        """A mask argument (device tensor, host array, or one host array per row) as a contiguous uint8 ``[B, Fmax, *inner]`` device tensor."""
+        if isinstance(m, torch.Tensor):
+            if tuple(m.shape) != (B, Fmax) + inner or m.device != self.device:
+                raise ValueError(f"mask tensor must be [{B}, {Fmax}, {inner[0]}, {inner[1]}] on {self.device} (got {tuple(m.shape)} on {m.device})")
+            return m.to(torch.uint8).contiguous()
+        host = np.zeros((B, Fmax) + inner, dtype=np.uint8)
+        if len(m) != B:
+            raise ValueError("one mask per row")
+        for i, row in enumerate(m):
+            row = np.asarray(row)
+            if row.shape[1:] != inner or row.shape[0] > Fmax:
+                raise ValueError(f"row {i}: mask shape {row.shape}, expected [<= {Fmax}, {inner[0]}, {inner[1]}]")
+            host[i, : row.shape[0]] = row.astype(bool)
+        return torch.from_numpy(host).to(self.device)
+
+    def teacher_forced(self, sentences: Sequence[Sequence[int]], durations_frames: Sequence[np.ndarray], mels, n_frames: Optional[Sequence[int]] = None,
+                       rng=None, masks=None, to_host: bool = True, return_pre: bool = False):
+        """The TEACHER-FORCED pass, ``AcousticModel(is_training=False).__call__`` of the reference (vietTTS/nat/model.py:146-169; what
+        vietTTS/nat/gta.py runs to dump ground-truth-aligned mels): per row token ids, per-token durations in FRAMES (fp32, not rounded) and the
+        TARGET mel — ``mels`` is a float32 ``[B, F, mel_dim]`` device tensor or host array, or one ``[F_row, mel_dim]`` host array per row; the
+        one-frame shift happens in the library.  ``n_frames``: frames per row (default: ``F`` / each row's own).
+
+        Dropout and zoneout (both on in the reference with ``is_training=False``): ``rng`` (the checkpoint's jax PRNGKey, uint32[2]) draws the
+        reference's own six masks on the GPU at ``(B, F)``; ``masks = (keep [B, F, 2, prenet_dim], zone [B, F, 4, decoder_dim])`` (device tensors,
+        host arrays or per-row host arrays; zone = 1 keeps the previous state) makes them explicit — with them a row's result does not depend on
+        its batch; neither = no dropout and no zoneout.
+
+        A row's tokens past ``len(sentences[i])`` do not exist (this library's rule everywhere).  The reference's corpus run treats the padded
+        columns of its batch as tokens: pass every row padded (token 0, duration 0) to the common length and ``n_frames = F`` to reproduce it.
+
+        Returns the mel with the postnet residual (the reference's second value; per-row host arrays ``[n_frames, mel_dim]``, or with
+        ``to_host=False`` the device tensor ``[B, F, mel_dim]``, rows past ``n_frames`` zero); ``return_pre=True`` returns ``(pre, mel)``."""
+        if self._blob is None:
+            raise RuntimeError("no parameters loaded")
+        if rng is not None and masks is not None:
+            raise ValueError("rng draws the masks: give rng or masks, not both")
+        B = len(sentences)
+        lens = [len(s) for s in sentences]
+        if B == 0 or min(lens) < 1:
+            raise ValueError("empty batch or token sequence")
+        if isinstance(mels, (torch.Tensor, np.ndarray)):
+            if mels.ndim != 3 or mels.shape[0] != B or mels.shape[2] != self.mel_dim:
+                raise ValueError(f"mels must be [{B}, F, {self.mel_dim}] (got {tuple(mels.shape)})")
+            Fmax = int(mels.shape[1])
+            if isinstance(mels, np.ndarray):
+                mels = torch.from_numpy(np.ascontiguousarray(mels, dtype=np.float32))
+            if mels.dtype != torch.float32:
+                raise ValueError("mels must be float32")
+            mel_d = mels.to(self.device).contiguous()
+            n_frames = [Fmax] * B if n_frames is None else [int(n) for n in n_frames]
+        else:
+            rows = [np.asarray(m, dtype=np.float32) for m in mels]
+            if len(rows) != B or any(r.ndim != 2 or r.shape[1] != self.mel_dim for r in rows):
+                raise ValueError(f"mels: one [F_row, {self.mel_dim}] array per row")
+            n_frames = [r.shape[0] for r in rows] if n_frames is None else [int(n) for n in n_frames]
+            Fmax = max(r.shape[0] for r in rows)
+            host = np.zeros((B, Fmax, self.mel_dim), dtype=np.float32)
+            for i, r in enumerate(rows):
+                host[i, : r.shape[0]] = r
+            mel_d = torch.from_numpy(host).to(self.device)
+        if len(n_frames) != B or min(n_frames) < 1 or max(n_frames) > Fmax:
+            raise ValueError(f"n_frames: one count in 1 .. {Fmax} per row")
+        Lmax = max(lens)
+        tok = np.zeros((B, Lmax), dtype=np.int32)
+        dur = np.zeros((B, Lmax), dtype=np.float32)
+        for i, s in enumerate(sentences):
+            tok[i, : lens[i]] = np.asarray(s, dtype=np.int32)
+            dur[i, : lens[i]] = np.asarray(durations_frames[i], dtype=np.float32).reshape(-1)
+        keep_d = zone_d = None
+        if rng is not None:
+            keep_d, zone_d = self.device_teacher_masks_haiku(rng, B, Fmax)
+        elif masks is not None:
+            keep_d = None if masks[0] is None else self._mask_tensor(masks[0], B, Fmax, (2, self.prenet_dim))
+            zone_d = None if masks[1] is None else self._mask_tensor(masks[1], B, Fmax, (4, int(self.cfg.decoder_dim)))
+        tok_d = torch.from_numpy(tok).to(self.device)
+        dur_d = torch.from_numpy(dur).to(self.device)
+        len_d = torch.tensor(lens, dtype=torch.int32, device=self.device)
+        nf_d = torch.tensor(n_frames, dtype=torch.int32, device=self.device)
+        out = torch.empty((B, Fmax, self.mel_dim), dtype=torch.float32, device=self.device)
+        pre = torch.empty_like(out) if return_pre else None
+        n = C.c_size_t(0)
+        _lib.check(self.lib, self.lib.vtts_nat_acoustic_forward_teacher_workspace_bytes(self._h, B, Lmax, Fmax, C.byref(n)))
+        if self._ws is None or self._ws.numel() < n.value:
+            self._ws = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(
+                self.lib,
+                self.lib.vtts_nat_acoustic_forward_teacher(self._h, _ptr(tok_d), _ptr(len_d), _ptr(dur_d), _ptr(nf_d), B, Lmax, Fmax, _ptr(mel_d), _ptr(keep_d),
+                                                           _ptr(zone_d), _ptr(out), _ptr(pre), _ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream)),
+            )
+        if not to_host:
+            return (pre, out) if return_pre else out
+        host = out.cpu().numpy()
+        res = [host[i, : n_frames[i]].copy() for i in range(B)]
+        if not return_pre:
+            return res
+        hpre = pre.cpu().numpy()
+        return [hpre[i, : n_frames[i]].copy() for i in range(B)], res
+
     def set_option(self, key: str, value: int) -> None:
         """``"bf16x3"``: 1 = the postnet's matrix products as three bf16 x bf16 terms on the bf16 matrix pipe (include/vtts_nat.h); 0 = fp32 (default)."""
         _lib.check(self.lib, self.lib.vtts_nat_acoustic_set_option(self._h, key.encode(), int(value)))
