@@ -92,6 +92,7 @@ int vtts_nat_acoustic_param_info(const vtts_nat_acoustic* h, int i, const char**
 int vtts_nat_acoustic_packed_bytes(const vtts_nat_acoustic* h, size_t* bytes);
 int vtts_nat_acoustic_pack(vtts_nat_acoustic* h, void* dev_blob, size_t blob_bytes, void* stream);
 int vtts_nat_acoustic_bind_packed(vtts_nat_acoustic* h, void* dev_blob, size_t blob_bytes);
+/* (Independent of the options: a workspace sized once serves every path.) */
 int vtts_nat_acoustic_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, size_t* bytes);
 /* Options (defaults in brackets):
  *   "bf16x3" [0]  1 = the matrix products of the decoder's LSTM steps, of the gate GEMM and of the postnet as three bf16 x bf16 terms on the
@@ -100,9 +101,33 @@ int vtts_nat_acoustic_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lma
  *                 by ~1e-5 of its range (tests/test_gpu_nat.py) and the acoustic model runs a third faster.  The default keeps every
  *                 product in fp32 — the mode the parity tests against the reference pin at 5e-5.  For callers whose vocoder is
  *                 bf16-class anyway.  The token encoders and the duration model are fp32 in both modes (integer frame counts).
+ *   "resident" [0]  1 = forward() and forward_from_encoder(ngroups = 0) run the decoder's frame loop as ONE resident kernel (nat_dec_resident_k: a
+ *                 cooperative launch of one workgroup per CU that keeps the two LSTMs' recurrent weights in registers for all Fmax frames and
+ *                 exchanges the state through agent-scope stores and loads between grid barriers, five per frame) instead of three launches per
+ *                 frame — the low-latency path for one to four sentences.  It is taken when ALL of these hold: 1 <= B <= 4; "bf16x3" is 0; the
+ *                 stream is not being captured; decoder_dim = 512, prenet_dim = 256 (the reference's; the kernel is built for them); the runtime
+ *                 accepts the cooperative launch.  In every other case (B > 4, forward_groups(), ngroups >= 1, bf16x3, capture, other dimensions,
+ *                 hipErrorCooperativeLaunchTooLarge, forward_teacher()) the call takes the per-frame launches, silently.  fp32 throughout; a row's
+ *                 mel does not depend on its batch and runs repeat bit for bit, but the sums' order is this kernel's own: against the default path
+ *                 the mel differs by fp32 rounding (both are pinned to the oracle by the same bar, tests/test_gpu_nat_resident.py).
+ *                 Every wait inside the kernel is bounded (100 ms): see vtts_nat_acoustic_resident_status().
+ *   "resident_grid" [0]  workgroups of the resident kernel: 64, 128 or 256; 0 = the library's default, halved
+ *                 until it fits the device's CU count.  The result does not depend on it, bit for bit.  For measurements.
+ *   "resident_used"  read-only (get_option): 1 if the handle's last forward took the resident kernel, else 0.
+ *   "stage_times" [0]  1 = forward() / forward_from_encoder(ngroups = 0) record timing events on the stream in front of the gate GEMM, of the decoder's
+ *                 frame loop, of the postnet and behind it; after the caller has synchronised, get_option reads "stage_gates_us" (token-rows GEMM + mix;
+ *                 on the default path only the first 64 frames' mix, the rest runs beside the loop), "stage_decoder_us" and "stage_postnet_us" of the
+ *                 last such call in whole microseconds (VTTS_ERR_STATE if there was none).  For tools/latency_bench.py.
  * Unknown keys and out-of-range values return VTTS_ERR_INVALID. */
 int vtts_nat_acoustic_set_option(vtts_nat_acoustic* h, const char* key, int value);
 int vtts_nat_acoustic_get_option(const vtts_nat_acoustic* h, const char* key, int* value);
+/*
+ * After the caller has synchronised the stream of a forward that took the resident kernel: *timed_out = 1 if a wait inside the handle's last
+ * resident launch exceeded its budget (100 ms of the device's wall clock, four orders of magnitude above a barrier) — every workgroup then
+ * left the kernel and the frames not produced are zero in mel_dev — else 0.  A synchronous 8-byte copy from the workspace of that call, which
+ * must still be allocated.  VTTS_ERR_STATE if the handle has not launched the resident kernel.
+ */
+int vtts_nat_acoustic_resident_status(vtts_nat_acoustic* h, int* timed_out);
 /*
  *   tokens_dev    [B, Lmax] int32, lengths_dev [B] int32                       as for the duration model
  *   durations_dev [B, Lmax] fp32, in FRAMES (text2mel.py:78: seconds * sample_rate / hop)

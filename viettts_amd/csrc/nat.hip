@@ -253,12 +253,21 @@ struct vtts_nat_acoustic : NatModel {
     hipEvent_t ev_fork = nullptr, ev_gates = nullptr;
     std::vector<hipEvent_t> ev_dec, ev_done;  // per group: decoder frames complete (recorded on the caller's stream) / mel rows complete (on `side`)
     int groups_valid = 0;
+    // option "resident": the decoder's frame loop of a call with 1 <= B <= 4 as one resident kernel (nat_resident.hip)
+    int resident = 0, resident_grid = 0, resident_used = 0;
+    int cu_count = 0;               // of the device the first forward() ran on
+    unsigned* res_sync = nullptr;   // [arrivals | abort word] of the last resident launch, in that call's workspace
+    // option "stage_times": timing events on the caller's stream in front of the gate GEMM, the decoder loop, the postnet, and behind it
+    int stage_times = 0, stage_valid = 0;
+    hipEvent_t ev_stage[4] = {nullptr, nullptr, nullptr, nullptr};
     ~vtts_nat_acoustic() {
         for (hipEvent_t e : ev_dec) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_done) (void)hipEventDestroy(e);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_gates) (void)hipEventDestroy(ev_gates);
         if (side) (void)hipStreamDestroy(side);
+        for (hipEvent_t e : ev_stage)
+            if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -732,6 +741,7 @@ __global__ void nat_duration_head_k(const float* __restrict__ enc, const int* __
 // 16-byte broadcast reads per token), a thread's 4 columns x NAT_MIX_FT frames in registers, EG rows streamed from L2 (coalesced float4).
 // Sums in token order, weights from the sentence's own durations: a row does not depend on its batch.
 constexpr int NAT_MIX_FT = 16;
+constexpr int NAT_RES_DEFAULT_GRID = 128;  // workgroups of the resident decoder (64, 128 or 256): DESIGN.md section 6g
 __global__ __launch_bounds__(256) void nat_gates_mix_k(const float* __restrict__ eg1, const float* __restrict__ eg2, const float* __restrict__ bias1,
                                                        const float* __restrict__ bias2, const int* __restrict__ lengths, const float* __restrict__ dur,
                                                        const int* __restrict__ nframes, float* __restrict__ G1, float* __restrict__ G2, int Lmax, int Fmax,
@@ -1949,6 +1959,7 @@ VTTS_API int vtts_nat_acoustic_create(const vtts_nat_acoustic_cfg* cfg, int devi
     return VTTS_OK;
 }
 VTTS_API void vtts_nat_acoustic_destroy(vtts_nat_acoustic* h) { delete h; }
+static const char* const NAT_ACOUSTIC_OPTIONS = "bf16x3, resident, resident_grid, resident_used, stage_times, stage_gates_us, stage_decoder_us, stage_postnet_us";
 VTTS_API int vtts_nat_acoustic_set_option(vtts_nat_acoustic* h, const char* key, int value) {
     if (!h || !key) return failf(VTTS_ERR_INVALID, "null argument");
     if (!strcmp(key, "bf16x3")) {
@@ -1956,7 +1967,24 @@ VTTS_API int vtts_nat_acoustic_set_option(vtts_nat_acoustic* h, const char* key,
         h->x3 = value;
         return VTTS_OK;
     }
-    return failf(VTTS_ERR_INVALID, "unknown option '%s' (known: bf16x3)", key);
+    if (!strcmp(key, "resident")) {
+        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "resident must be 0 or 1 (got %d)", value);
+        h->resident = value;
+        return VTTS_OK;
+    }
+    if (!strcmp(key, "resident_grid")) {
+        if (value != 0 && value != 64 && value != 128 && value != 256) return failf(VTTS_ERR_INVALID, "resident_grid must be 0, 64, 128 or 256 (got %d)", value);
+        h->resident_grid = value;
+        return VTTS_OK;
+    }
+    if (!strcmp(key, "stage_times")) {
+        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "stage_times must be 0 or 1 (got %d)", value);
+        h->stage_times = value;
+        h->stage_valid = 0;
+        return VTTS_OK;
+    }
+    if (!strcmp(key, "resident_used") || !strncmp(key, "stage_", 6)) return failf(VTTS_ERR_INVALID, "%s is read-only", key);
+    return failf(VTTS_ERR_INVALID, "unknown option '%s' (known: %s)", key, NAT_ACOUSTIC_OPTIONS);
 }
 VTTS_API int vtts_nat_acoustic_get_option(const vtts_nat_acoustic* h, const char* key, int* value) {
     if (!h || !key || !value) return failf(VTTS_ERR_INVALID, "null argument");
@@ -1964,7 +1992,38 @@ VTTS_API int vtts_nat_acoustic_get_option(const vtts_nat_acoustic* h, const char
         *value = h->x3;
         return VTTS_OK;
     }
-    return failf(VTTS_ERR_INVALID, "unknown option '%s' (known: bf16x3)", key);
+    if (!strcmp(key, "resident") || !strcmp(key, "resident_grid") || !strcmp(key, "resident_used")) {
+        *value = !strcmp(key, "resident") ? h->resident : !strcmp(key, "resident_grid") ? h->resident_grid : h->resident_used;
+        return VTTS_OK;
+    }
+    if (!strcmp(key, "stage_times")) {
+        *value = h->stage_times;
+        return VTTS_OK;
+    }
+    const int stage = !strcmp(key, "stage_gates_us") ? 0 : !strcmp(key, "stage_decoder_us") ? 1 : !strcmp(key, "stage_postnet_us") ? 2 : -1;
+    if (stage >= 0) {
+        if (!h->stage_valid) return failf(VTTS_ERR_STATE, "%s: no forward() with the option stage_times set has run", key);
+        float ms = 0.0f;
+        HIP_TRYN(hipEventElapsedTime(&ms, h->ev_stage[stage], h->ev_stage[stage + 1]));  // (hipErrorNotReady before the caller has synchronised)
+        *value = (int)(ms * 1000.0f + 0.5f);
+        return VTTS_OK;
+    }
+    return failf(VTTS_ERR_INVALID, "unknown option '%s' (known: %s)", key, NAT_ACOUSTIC_OPTIONS);
+}
+VTTS_API int vtts_nat_acoustic_resident_status(vtts_nat_acoustic* h, int* timed_out) {
+    if (!h || !timed_out) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h->res_sync) return failf(VTTS_ERR_STATE, "resident_status(): this handle has not launched the resident decoder");
+    unsigned words[2 + 2 * 10] = {};
+    HIP_TRYN(hipMemcpy(words, h->res_sync, VTTS_TIMELINE ? sizeof(words) : 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    *timed_out = words[1] != 0u;
+#if VTTS_TIMELINE  // kernel-development builds: the phase clocks of workgroup 0 (10 ns ticks, summed over the frames)
+    unsigned long long tl[10];
+    memcpy(tl, words + 2, sizeof(tl));
+    fprintf(stderr, "nat_dec_resident_k timeline [wait1 lstm1 wait2 lstm2 wait3 proj wait4 prenet1 wait5 prenet2] x 10 ns:");
+    for (int i = 0; i < 10; ++i) fprintf(stderr, " %llu", tl[i]);
+    fprintf(stderr, "\n");
+#endif
+    return VTTS_OK;
 }
 VTTS_API int vtts_nat_acoustic_num_params(const vtts_nat_acoustic* h, int* n) {
     if (!h || !n) return failf(VTTS_ERR_INVALID, "null argument");
@@ -1992,6 +2051,10 @@ VTTS_API int vtts_nat_acoustic_bind_packed(vtts_nat_acoustic* h, void* dev_blob,
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     return h->bind(dev_blob, blob_bytes);
 }
+// the resident decoder's share of the workspace (whether the option is set or not: a workspace sized once serves both paths): 256 bytes of polled
+// words (arrival counter, abort word; development builds' phase clocks) in front, then the exchange buffer
+constexpr size_t NAT_RES_WS_BYTES = 256 + (size_t)vtts::NAT_RES_XCH_ELEMS * 4 * sizeof(float);
+static_assert(NAT_RES_WS_BYTES % 256 == 0, "workspace blocks are 256-byte aligned");
 static size_t nat_dec_state_floats(const vtts_nat_acoustic_cfg& c, int B) {
     const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, ZW = 2 * H + c.prenet_dim;  // rows [p | h1 | h2]
     return (2 * ZW + 2 * H) * Bp;
@@ -2006,7 +2069,8 @@ VTTS_API int vtts_nat_acoustic_workspace_bytes(const vtts_nat_acoustic* h, int B
              + 2 * align_up((size_t)B * Fmax * PD * 4, 256)                                                // postnet ping-pong
              + align_up(nat_dec_state_floats(h->cfg, B) * 4, 256)                                          // decoder state Z[2], c1, c2
              + 2 * align_up((size_t)B * Fmax * 4 * h->cfg.decoder_dim * 4, 256)                           // hoisted gate pre-activations G1, G2
-             + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256);                                    // encoder LSTMs' scratch
+             + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256)                                     // encoder LSTMs' scratch
+             + NAT_RES_WS_BYTES;                                                                           // resident decoder: counters, exchange buffer
     return VTTS_OK;
 }
 // what the teacher-forced pass needs beyond forward()'s layout: the prenet's two layers, the hidden sequence, the recurrent state
@@ -2144,6 +2208,9 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
     float* G1 = take((size_t)B * Fmax * G4 * 4);
     float* G2 = take((size_t)B * Fmax * G4 * 4);
     float* lstm_ws = take(nat_enc_lstm_floats(D, B, Lmax) * 4);
+    unsigned* res_sync = reinterpret_cast<unsigned*>(take(NAT_RES_WS_BYTES));
+    float* res_xch = reinterpret_cast<float*>(res_sync + 64);
+    h->resident_used = 0;
     if (enc_pre) {
         enc = const_cast<float*>(enc_pre);  // read only from here on
     } else {
@@ -2264,6 +2331,13 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
         // frames [0, 64) here and for the rest beside the first 64 steps
         const int MBG = G4 / 32;
         if (G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: the gate mix wants 4 * decoder_dim in multiples of 1024", H);
+        const bool stamps = h->stage_times && ngroups == 0;
+        h->stage_valid = 0;
+        if (stamps) {
+            for (hipEvent_t& e : h->ev_stage)
+                if (!e) HIP_TRYN(hipEventCreate(&e));
+            HIP_TRYN(hipEventRecord(h->ev_stage[0], s));
+        }
         for (int l = 0; l < 2; ++l) {
             const std::string mod = l ? "lstm_1/linear" : "lstm/linear";
             if (h->x3)
@@ -2278,7 +2352,23 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
         const size_t mlds = ((size_t)(Lmax + 3) / 4 * 4 + (size_t)Lmax * NAT_MIX_FT) * sizeof(float);
         if (mlds > 48 * 1024)
             HIP_TRYN(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_gates_mix_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        const int mtiles = (Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT, mfirst = 64 / NAT_MIX_FT < mtiles ? 64 / NAT_MIX_FT : mtiles;
+        // option "resident": 1 <= B <= 4, fp32 products, the reference's decoder dimensions, no hand-over, a stream that is not being captured
+        // and a grid the device can hold; in every other case the call takes the per-frame launches below
+        int res_grid = 0;
+        if (h->resident && ngroups == 0 && B <= 4 && !h->x3 && H == vtts::NAT_RES_H && PN == vtts::NAT_RES_PN && MEL <= vtts::NAT_RES_MELMAX) {
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            HIP_TRYN(hipStreamIsCapturing(s, &cap));
+            if (!h->cu_count) {
+                int dev = 0;
+                HIP_TRYN(hipGetDevice(&dev));
+                HIP_TRYN(hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, dev));
+            }
+            // at most one workgroup per CU: the default grid where the device has that many CUs, else the next smaller one
+            res_grid = h->resident_grid ? h->resident_grid : NAT_RES_DEFAULT_GRID;
+            while (res_grid > h->cu_count && res_grid > 64) res_grid /= 2;
+            if (cap != hipStreamCaptureStatusNone || res_grid > h->cu_count) res_grid = 0;
+        }
+        const int mtiles = (Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT, mfirst = res_grid ? mtiles : (64 / NAT_MIX_FT < mtiles ? 64 / NAT_MIX_FT : mtiles);
         auto gates = [&](int tile0, int ntiles, hipStream_t gs) {
             hipLaunchKernelGGL(nat_gates_mix_k, dim3(ntiles, 2 * (G4 / 1024), B), dim3(256), mlds, gs, EG1, EG2, h->extra("lstm/linear#condb"),
                                h->extra("lstm_1/linear#condb"), lengths_dev, durations_dev, nframes_dev, G1, G2, Lmax, Fmax, G4, tile0);
@@ -2325,8 +2415,25 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
             if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, nframes_dev, f, B, Bp, H);
             else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, nframes_dev, f, B, Bp, H);
         };
-        for (int f = 0; f < Fmax; ++f) {
-            if (f == 64) HIP_TRYN(hipStreamWaitEvent(s, h->ev_gates, 0));
+        if (stamps) HIP_TRYN(hipEventRecord(h->ev_stage[1], s));
+        if (res_grid) {  // every frame's gates are on `s` already (mfirst = mtiles)
+            HIP_TRYN(hipMemsetAsync(res_sync, 0, 256, s));
+            const size_t e4 = (size_t)E * G4;  // Haiku rows [E, ...): the state's rows
+            const vtts::NatResidentArgs ra{h->dev("lstm/linear", "w") + e4, h->dev("lstm_1/linear", "w") + e4, h->dev("linear", "w"), bp, h->dev("linear_1", "w"),
+                                           h->dev("linear_2", "w"), G1, G2, nframes_dev, keep_dev, mel0, res_xch, res_sync,
+                                           reinterpret_cast<unsigned long long*>(res_sync + 2), Fmax, MEL};
+            const hipError_t le = vtts::launch_nat_dec_resident(ra, B, res_grid, s);
+            if (le == hipSuccess) {
+                h->resident_used = 1;
+                h->res_sync = res_sync;
+            } else if (le == hipErrorCooperativeLaunchTooLarge) {
+                (void)hipGetLastError();  // the runtime cannot hold the grid resident: the launches below take over
+            } else {
+                return failf(VTTS_ERR_HIP, "resident decoder launch failed: %s", hipGetErrorString(le));
+            }
+        }
+        for (int f = 0; f < Fmax && !h->resident_used; ++f) {
+            if (f == 64 && mtiles > mfirst) HIP_TRYN(hipStreamWaitEvent(s, h->ev_gates, 0));
             float* zc = Z[f & 1];
             float* zp = Z[(f + 1) & 1];
             if (dx3) {
@@ -2352,7 +2459,13 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
         for (int g = 0; g < ngroups; ++g) HIP_TRYN(hipStreamWaitEvent(s, h->ev_done[g], 0));  // stream order for the caller: mel_dev is complete after this call on `s`
         h->groups_valid = ngroups;
     } else {
+        const bool stamps = !tf && h->stage_times;
+        if (stamps) HIP_TRYN(hipEventRecord(h->ev_stage[2], s));
         postnet(0, B, Fmax, s);
+        if (stamps) {
+            HIP_TRYN(hipEventRecord(h->ev_stage[3], s));
+            h->stage_valid = 1;
+        }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(VTTS_ERR_HIP, "acoustic model launch failed: %s", hipGetErrorString(e));

@@ -178,4 +178,29 @@ hipError_t launch_conv_post_bf16(const BConvArgs& a, float* wav, float* pre_act,
 hipError_t launch_bf16_to_f32(const void* in, float* out, size_t n, hipStream_t s);
 hipError_t launch_f32_to_bf16(const float* in, void* out, size_t n, hipStream_t s);
 
+
+// ---- the NAT acoustic decoder's frame loop as one resident kernel for 1 <= B <= 4 sentences (nat_resident.hip; option "resident" of vtts_nat.h) ----
+// Built for the reference's decoder (decoder_dim 512, prenet_dim 256: the recurrent weights' share per thread is a compile-time register array).
+constexpr int NAT_RES_H = 512, NAT_RES_PN = 256, NAT_RES_MELMAX = 128;
+constexpr int NAT_RES_XCH_ELEMS = NAT_RES_MELMAX + 2 * NAT_RES_PN + 2 * NAT_RES_H;  // [mel | p1 | p | h1 | h2], 4 sentences per element
+struct NatResidentArgs {
+    const float* w1;   // "lstm/linear" w from Haiku row E on: [PN + H][4H]
+    const float* w2;   // "lstm_1/linear" w from Haiku row E on: [PN + 2H][4H]
+    const float* wp;   // "linear" w [2H][MEL], bp its bias
+    const float* bp;
+    const float* f1;   // "linear_1" w [MEL][PN]
+    const float* f2;   // "linear_2" w [PN][PN]
+    const float* G1;   // hoisted gates [B][Fmax][4H] in the step kernel's accumulator order, all frames
+    const float* G2;
+    const int* nframes;
+    const unsigned char* keep;  // [B][Fmax][2][PN] or nullptr
+    float* mel0;       // [B][Fmax][MEL], cleared by the caller
+    float* xch;        // [NAT_RES_XCH_ELEMS][4] exchange buffer
+    unsigned* sync;    // [0] arrivals, [1] abort word; 8-byte aligned, zeroed on the stream before the launch
+    unsigned long long* timeline;  // -DVTTS_TIMELINE builds: 10 phase clocks of workgroup 0 (wall_clock64 ticks); unused otherwise
+    int Fmax, MEL;
+};
+// cooperative launch on `grid` in {64, 128, 256} workgroups; the runtime's error (hipErrorCooperativeLaunchTooLarge ...) is returned as it is
+hipError_t launch_nat_dec_resident(const NatResidentArgs& a, int B, int grid, hipStream_t s);
+
 }  // namespace vtts

@@ -271,13 +271,28 @@ class AcousticModel:
         return [hpre[i, : n_frames[i]].copy() for i in range(B)], res
 
     def set_option(self, key: str, value: int) -> None:
-        """``"bf16x3"``: 1 = the postnet's matrix products as three bf16 x bf16 terms on the bf16 matrix pipe (include/vtts_nat.h); 0 = fp32 (default)."""
+        """``"bf16x3"``: 1 = the postnet's matrix products as three bf16 x bf16 terms on the bf16 matrix pipe (include/vtts_nat.h); 0 = fp32 (default).
+        ``"resident"``: 1 = calls with one to four sentences run the decoder's frame loop as one resident kernel instead of three launches per
+        frame (the low-latency path; fp32, same oracle bar, rounding of its own; every other call takes the launches as before — see
+        :attr:`resident_used`); 0 = the launches (default).  ``"resident_grid"``: 0 / 64 / 128 / 256 workgroups for it (0 = the library's default)."""
         _lib.check(self.lib, self.lib.vtts_nat_acoustic_set_option(self._h, key.encode(), int(value)))
 
     def get_option(self, key: str) -> int:
         v = C.c_int(0)
         _lib.check(self.lib, self.lib.vtts_nat_acoustic_get_option(self._h, key.encode(), C.byref(v)))
         return int(v.value)
+
+    @property
+    def resident_used(self) -> bool:
+        """Whether the last call ran the decoder loop as the resident kernel (option ``"resident"``)."""
+        return bool(self.get_option("resident_used"))
+
+    def resident_status(self) -> bool:
+        """After a synchronisation: True if a wait inside the last resident launch ran out of its 100 ms budget (the kernel then gave up and the
+        frames it did not produce are zero).  ``VttsError`` (VTTS_ERR_STATE) if this model has not launched the resident kernel."""
+        v = C.c_int(0)
+        _lib.check(self.lib, self.lib.vtts_nat_acoustic_resident_status(self._h, C.byref(v)))
+        return bool(v.value)
 
     def wait_group(self, group: int, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Make ``stream`` (default: torch's current stream) wait until the rows of ``group`` of the last ``group_row0`` call are complete."""
@@ -398,4 +413,6 @@ class AcousticModel:
         if not to_host:
             return out
         host = out.cpu().numpy()
+        if self.resident_used and self.resident_status():
+            raise RuntimeError("the resident decoder kernel gave up: a wait between its workgroups exceeded 100 ms (the mel is incomplete)")
         return [host[i, : n_frames[i]].copy() for i in range(B)]

@@ -170,12 +170,29 @@ def predict_duration(tokens: Sequence[int]) -> np.ndarray:
 
 
 _ACOUSTIC_MODEL = None
+_LOW_LATENCY = False
 
 
 def set_acoustic_model(model) -> None:
     """Install a loaded :class:`viettts_amd.nat.acoustic.AcousticModel` for :func:`predict_mel`."""
     global _ACOUSTIC_MODEL
     _ACOUSTIC_MODEL = model
+    if model is not None and _LOW_LATENCY:
+        model.set_option("resident", 1)
+
+
+def set_low_latency(flag: bool) -> None:
+    """(extension) ``True``: :func:`predict_mel` / :func:`text2mel` run the acoustic decoder's frame loop as one resident kernel (option
+    ``"resident"`` of include/vtts_nat.h: one sentence per call is exactly its regime) instead of three launches per frame.  Off by default.
+    Only the flag is stored here; it is applied to the cached acoustic model when that is created or installed, and at once if there is one."""
+    global _LOW_LATENCY
+    _LOW_LATENCY = bool(flag)
+    if _ACOUSTIC_MODEL is not None:
+        _ACOUSTIC_MODEL.set_option("resident", int(_LOW_LATENCY))
+
+
+def get_low_latency() -> bool:
+    return _LOW_LATENCY
 
 
 def load_acoustic_checkpoint(path=None, with_rng: bool = False):
@@ -207,6 +224,8 @@ def predict_mel(tokens: Sequence[int], durations: np.ndarray, dropout_seed: Opti
         m = AcousticModel()
         m.load_params(params, state)
         m.checkpoint_rng = rng
+        if _LOW_LATENCY:
+            m.set_option("resident", 1)
         _ACOUSTIC_MODEL = m
     if dropout_rng is None:
         dropout_rng = getattr(_ACOUSTIC_MODEL, "checkpoint_rng", None)

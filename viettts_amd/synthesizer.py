@@ -5,7 +5,8 @@ reference's order (:21-31).  Unlike the reference this module has a ``main()`` (
 reference runs the whole pipeline at import time).  One addition:
 ``--mel-file`` synthesises from a saved ``[T, 80]`` / ``[1, T, 80]`` float32 mel (.npy) so the
 mel->waveform path can be driven on its own (the text path runs the NAT duration and acoustic models of
-``viettts_amd/nat`` like the reference's).
+``viettts_amd/nat`` like the reference's), and ``--low-latency`` runs the acoustic decoder's frame loop as one resident kernel
+(``viettts_amd.nat.text2mel.set_low_latency``).
 
     python -m viettts_amd.synthesizer --text "..." --output clip.wav --lexicon-file assets/infore/lexicon.txt
 """
@@ -46,6 +47,7 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--silence-duration", default=-1, type=float)
     p.add_argument("--lexicon-file", default=None)
     p.add_argument("--mel-file", default=None, type=Path, help="(extension) synthesise from a saved mel instead of text")
+    p.add_argument("--low-latency", action="store_true", help="(extension) run the acoustic decoder's frame loop as one resident kernel")
     return p
 
 
@@ -61,8 +63,10 @@ def main(argv=None) -> int:
     else:
         if args.text is None:
             raise SystemExit("--text (or --mel-file) is required")
-        from .nat.text2mel import text2mel
+        from .nat.text2mel import set_low_latency, text2mel
 
+        if args.low_latency:
+            set_low_latency(True)
         text = nat_normalize_text(args.text)
         print("Normalized text input:", text)
         mel = text2mel(text, args.lexicon_file, args.silence_duration)
