@@ -105,6 +105,29 @@ MEL_EXPORTS = (
     "vtts_mel_forward",
 )
 
+# Every symbol include/vtts_disc.h declares.
+DISC_EXPORTS = (
+    "vtts_disc_create",
+    "vtts_disc_destroy",
+    "vtts_disc_num_params",
+    "vtts_disc_param_info",
+    "vtts_disc_set_param",
+    "vtts_disc_packed_bytes",
+    "vtts_disc_pack",
+    "vtts_disc_bind_packed",
+    "vtts_disc_workspace_bytes",
+    "vtts_disc_num_fmaps",
+    "vtts_disc_fmap_info",
+    "vtts_disc_forward",
+    "vtts_disc_losses",
+)
+# include/vtts_disc.h: the loss buffer's layout
+DISC_NUM_FMAPS = 54
+DISC_NUM_DISCS = 8
+DISC_MIN_SAMPLES = 11
+DISC_LOSS_REAL, DISC_LOSS_FAKE, DISC_LOSS_GEN, DISC_LOSS_TOTALS, DISC_LOSS_RESULTS = 54, 62, 70, 78, 128
+DISC_LOSS_FLOATS = DISC_LOSS_RESULTS + 2 * (DISC_NUM_FMAPS + 3 * DISC_NUM_DISCS) * 64
+
 VTTS_MEL_F32 = 0
 VTTS_MEL_PCM16 = 1
 MEL_FRAMES_PER_BLOCK = 8  # include/vtts_mel.h: VTTS_MEL_FRAMES_PER_BLOCK
@@ -264,6 +287,19 @@ def load(path=None) -> C.CDLL:
         "vtts_mel_bind_packed": (C.c_int, [vp, vp, sz]),
         "vtts_mel_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
         "vtts_mel_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, i64, vp, vp]),
+        "vtts_disc_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+        "vtts_disc_destroy": (None, [vp]),
+        "vtts_disc_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "vtts_disc_param_info": (C.c_int, [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.POINTER(i64), C.POINTER(C.c_int)]),
+        "vtts_disc_set_param": (C.c_int, [vp, cp, cp, vp, C.POINTER(i64), C.c_int]),
+        "vtts_disc_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+        "vtts_disc_pack": (C.c_int, [vp, vp, sz, vp]),
+        "vtts_disc_bind_packed": (C.c_int, [vp, vp, sz]),
+        "vtts_disc_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+        "vtts_disc_num_fmaps": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "vtts_disc_fmap_info": (C.c_int, [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "vtts_disc_forward": (C.c_int, [vp, vp, C.c_int, i64, vp, vp, vp, vp]),
+        "vtts_disc_losses": (C.c_int, [vp, vp, vp, C.c_int, i64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported

@@ -1,0 +1,87 @@
+"""Score a vocoder checkpoint with the objective HiFi-GAN optimises, on the GPU: wav -> log-mel (``MelFilter``) -> generator ->
+(y, y_hat) through the discriminators (``Discriminators``, include/vtts_disc.h), segment by segment.
+
+    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192]
+
+prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
+MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono at the model's sample rate, the
+generator as ``mel2wave`` reads it (``assets/hifigan/config.json`` + a Haiku pickle) and upstream's ``do_*`` file; raises
+``FileNotFoundError`` without them, before any input is touched.  Forward only: nothing is trained.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import wavio
+from .nat.config import FLAGS as NAT_FLAGS
+
+MEL_WEIGHT = 45.0
+
+
+def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None) -> dict:
+    """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction."""
+    from .resynth import default_mel_filter, log_mel_l1
+
+    mf = mel_filter or default_mel_filter(generator.device)
+    y_hat = generator(mf(y))[:, : y.shape[1]].contiguous()
+    L = discriminators.losses(y, y_hat)
+    mel = log_mel_l1(y_hat, y, mel_filter=mf)
+    return {"adv": L.gen, "fm": L.feature, "mel": mel, "total": L.gen + L.feature + MEL_WEIGHT * mel, "disc": L.disc}
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="adversarial, feature-matching and mel terms of a HiFi-GAN checkpoint on the GPU")
+    ap.add_argument("--wav", nargs="+", required=True, help="PCM16 mono .wav files at the model's sample rate")
+    ap.add_argument("--generator", required=True, help="the generator's Haiku pickle (hk_hifi.pickle)")
+    ap.add_argument("--discriminator", required=True, help="upstream's do_* checkpoint (keys mpd, msd)")
+    ap.add_argument("--config", default="assets/hifigan/config.json")
+    ap.add_argument("--segment", type=int, default=8192, help="samples per scored segment (a multiple of 256)")
+    ap.add_argument("--batch", type=int, default=16, help="segments per pass")
+    return ap
+
+
+def main(argv=None) -> None:
+    a = build_parser().parse_args(argv)
+    for path, what in ((a.generator, "generator checkpoint"), (a.discriminator, "discriminator checkpoint"), (a.config, "generator config")):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{what} {path} not found")
+    if a.segment < 512 or a.segment % 256:
+        raise ValueError("--segment must be a multiple of 256, at least 512")
+    if not torch.cuda.is_available():
+        raise RuntimeError("vocoder_eval needs an MI355X visible to PyTorch-ROCm; there is no CPU path")
+    from .hifigan.config import HifiganConfig
+    from .hifigan.discriminators import Discriminators
+    from .hifigan.generator import Generator
+    from .hifigan.weights import load_haiku_pickle
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    gen = Generator(HifiganConfig.from_json(a.config), device=dev)
+    gen.load_params(load_haiku_pickle(a.generator))
+    disc = Discriminators.from_checkpoint(a.discriminator, device=dev)
+    segs = []
+    for path in a.wav:
+        sr, pcm = wavio.read_wav(path)
+        if sr != NAT_FLAGS.sample_rate:
+            raise ValueError(f"{path}: {sr} Hz, the model runs at {NAT_FLAGS.sample_rate} Hz")
+        x = pcm.astype(np.float32) / 32768.0
+        segs += [x[i : i + a.segment] for i in range(0, len(x) - a.segment + 1, a.segment)]
+    if not segs:
+        raise ValueError(f"no input holds a whole segment of {a.segment} samples")
+    tot, n = {}, 0
+    for i in range(0, len(segs), a.batch):
+        y = torch.from_numpy(np.stack(segs[i : i + a.batch])).to(dev)
+        r = score_segments(y, gen, disc)
+        for k, v in r.items():
+            tot[k] = tot.get(k, 0.0) + v * y.shape[0]
+        n += y.shape[0]
+    m = {k: v / n for k, v in tot.items()}
+    print(f"{n} segments of {a.segment} samples: adversarial {m['adv']:.4f}  feature matching {m['fm']:.4f}  log-mel L1 {m['mel']:.4f}  "
+          f"adv + fm + {MEL_WEIGHT:g} * mel = {m['total']:.4f}  (discriminator loss {m['disc']:.4f})")
+
+
+if __name__ == "__main__":
+    main()
