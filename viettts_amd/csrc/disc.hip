@@ -21,7 +21,6 @@
 //   loss_stage1_k / loss_stage2_k   every loss in one fixed-order two-stage reduction (double accumulators, no atomics).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -33,7 +32,7 @@
 #include "../../include/vtts_hifigan.h"
 #include "vtts_internal.h"
 
-#define VTTS_API extern "C" __attribute__((visibility("default")))
+using vtts::failf;
 
 namespace {
 
@@ -45,15 +44,6 @@ constexpr int NDISC = VTTS_DISC_NUM_DISCS, NCONV = VTTS_DISC_NUM_CONVS, NPART = 
 constexpr int NRED = VTTS_DISC_NUM_FMAPS + 3 * NDISC;  // tensors the loss pass reduces
 constexpr int PERIODS[5] = {2, 3, 5, 7, 11};
 constexpr int64_t MAX_T = 1 << 23;  // keeps one row of any feature map (128 T floats at most) inside 32-bit indexing
-
-int failf(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return vtts::set_error(code, buf);
-}
 
 enum Kind : int { K_MPD_FIRST, K_MSD_FIRST, K_GEMM, K_POST };
 

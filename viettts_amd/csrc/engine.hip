@@ -19,13 +19,13 @@
 
 using namespace vtts;
 
-#define VTTS_API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 thread_local std::string g_last_error;
 
-int fail(int code, const char* fmt, ...) {
+}  // namespace
+
+int vtts::failf(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -35,22 +35,7 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-}  // namespace
-
-// shared with nat.hip: record the calling thread's last error, return the status code
-int vtts::set_error(int code, const char* msg) {
-    g_last_error = msg;
-    return code;
-}
-
 namespace {
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(VTTS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 enum Kind { KIND_CONV = 0, KIND_CONVT = 1 };
 
@@ -84,8 +69,6 @@ struct Layer {
     bool has_x3 = false;
     size_t off_x3 = 0;
 };
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
@@ -197,8 +180,8 @@ int build_layers_bf16(vtts_hifigan* h) {
         const bool is_pre = (&l == &h->layers[h->idx_pre]), is_post = (&l == &h->layers[h->idx_post]);
         l.bcls = classify_bf16(h, l, is_pre, is_post);
         if (l.bcls == BCLS_NONE)
-            return fail(VTTS_ERR_INVALID, "dtype bf16: no kernel for module %s (%d->%d, k=%d): the bf16 path covers the HiFi-GAN V1 shapes",
-                        l.key.c_str(), l.cin, l.cout, l.k);
+            return failf(VTTS_ERR_INVALID, "dtype bf16: no kernel for module %s (%d->%d, k=%d): the bf16 path covers the HiFi-GAN V1 shapes",
+                         l.key.c_str(), l.cin, l.cout, l.k);
         l.coutp = (l.kind == KIND_CONVT) ? l.cout * l.stride : l.cout;
         l.off_b = off;
         off = align_up(off + (size_t)l.coutp * sizeof(float), 256);
@@ -408,7 +391,7 @@ int launch_timed(vtts_hifigan* h, const Layer& l, int convs, int B, int L, hipSt
         HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].first, s));
     }
     const hipError_t e = launch();
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "%s for %s failed: %s", what, l.key.c_str(), hipGetErrorString(e));
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "%s for %s failed: %s", what, l.key.c_str(), hipGetErrorString(e));
     if (prof) {
         HIP_TRY(hipEventRecord(h->prof_events[h->prof_used].second, s));
         h->prof_used++;
@@ -730,9 +713,9 @@ int pick_microbatch(const vtts_hifigan* h, int B, int T) {
 int check_pass_size(const vtts_hifigan* h, int B, int T) {
     const size_t bytes = max_act_elems(h, T) * elem_bytes(h);
     if (bytes >= ((size_t)1 << 31))
-        return fail(VTTS_ERR_INVALID, "T=%d frames is too long for one pass (%zu activation bytes per utterance, limit 2^31): synthesize it in chunks",
-                    T, bytes);
-    if (pick_microbatch(h, B, T) > 65535) return fail(VTTS_ERR_INVALID, "at most 65535 utterances per pass (got %d)", B);
+        return failf(VTTS_ERR_INVALID, "T=%d frames is too long for one pass (%zu activation bytes per utterance, limit 2^31): synthesize it in chunks",
+                     T, bytes);
+    if (pick_microbatch(h, B, T) > 65535) return failf(VTTS_ERR_INVALID, "at most 65535 utterances per pass (got %d)", B);
     return VTTS_OK;
 }
 
@@ -856,7 +839,7 @@ struct MicroBatch {
 int tap_copy(const vtts_hifigan* h, const MicroBatch& m, const void* src, float* dst, size_t n) {
     const hipError_t e = h->dtype == VTTS_BF16 ? launch_bf16_to_f32(src, dst, n, m.s)
                                                : hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, m.s);
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "tap copy failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "tap copy failed: %s", hipGetErrorString(e));
     return VTTS_OK;
 }
 
@@ -936,7 +919,7 @@ int mrf_f32(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
     const size_t n = (size_t)m.nb * CL;
     hipLaunchKernelGGL(mrf_mean_k, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, m.s, ys[0], ys[1], ys[2], f32(m.buf.S),
                        n, (float)nk);
-    if (hipGetLastError() != hipSuccess) return fail(VTTS_ERR_HIP, "mrf_mean launch failed");
+    if (hipGetLastError() != hipSuccess) return failf(VTTS_ERR_HIP, "mrf_mean launch failed");
     return VTTS_OK;
 }
 
@@ -1018,7 +1001,7 @@ int mrf_bf16(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
     // after every addition): those kernels are chained by events in the sequential order rb_0 -> rb_1 -> rb_2, so every sample sees the
     // same additions and roundings as one-after-the-other — the same bits.
     auto hip_rc = [&](hipError_t e, const char* what) -> int {
-        return e == hipSuccess ? VTTS_OK : fail(VTTS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return e == hipSuccess ? VTTS_OK : failf(VTTS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     };
     return run_chains_parallel(h, nk, m.s, [&](int j, hipStream_t cs) -> int {
         int rc = run_chain(j, cs, [&]() -> int {
@@ -1043,7 +1026,7 @@ int conv_post_bf16(vtts_hifigan* h, const MicroBatch& m, int L, float* pre_act) 
     a.L = L;
     set_ragged(h, a, L);
     hipError_t e = launch_conv_post_bf16(a, m.wav, pre_act, m.s);
-    if (e != hipSuccess) return fail(VTTS_ERR_HIP, "conv_post launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "conv_post launch failed: %s", hipGetErrorString(e));
     return VTTS_OK;
 }
 
@@ -1079,15 +1062,15 @@ int run_micro_batch(vtts_hifigan* h, const Engine& e, const MicroBatch& m, const
 
 int forward_impl(vtts_hifigan* h, const float* mel, int B, int T, float* wav, void* ws, size_t ws_bytes, hipStream_t s0,
                  const Taps& tap) {
-    if (!h->blob) return fail(VTTS_ERR_STATE, "forward() before pack()/bind_packed()");
-    if (B <= 0 || T <= 0) return fail(VTTS_ERR_INVALID, "B and T must be positive (got B=%d, T=%d)", B, T);
+    if (!h->blob) return failf(VTTS_ERR_STATE, "forward() before pack()/bind_packed()");
+    if (B <= 0 || T <= 0) return failf(VTTS_ERR_INVALID, "B and T must be positive (got B=%d, T=%d)", B, T);
     if (int rc = check_pass_size(h, B, T)) return rc;
     const PassPlan p = plan_pass(h, B, T);
-    if (ws_bytes < p.bytes() || !ws) return fail(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", ws_bytes, p.bytes());
-    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return fail(VTTS_ERR_INVALID, "workspace must be 256-B aligned");
+    if (ws_bytes < p.bytes() || !ws) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", ws_bytes, p.bytes());
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return failf(VTTS_ERR_INVALID, "workspace must be 256-B aligned");
     {
         hipError_t e = hipSetDevice(h->device);  // side streams / events are created lazily: on THIS handle's device
-        if (e != hipSuccess) return fail(VTTS_ERR_HIP, "hipSetDevice(%d) failed: %s", h->device, hipGetErrorString(e));
+        if (e != hipSuccess) return failf(VTTS_ERR_HIP, "hipSetDevice(%d) failed: %s", h->device, hipGetErrorString(e));
     }
     const Engine& e = h->dtype == VTTS_BF16 ? ENGINE_BF16 : ENGINE_F32;
     const bool tail = h->dtype == VTTS_BF16 && !tap.name && tail_fused_bf16(h);
@@ -1112,34 +1095,34 @@ VTTS_API int vtts_abi_version(void) { return VTTS_ABI_VERSION; }
 VTTS_API const char* vtts_last_error(void) { return g_last_error.c_str(); }
 
 VTTS_API int vtts_hifigan_create(const vtts_hifigan_cfg* cfg, int device, int dtype, vtts_hifigan** out) {
-    if (!cfg || !out) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!cfg || !out) return failf(VTTS_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (dtype != VTTS_F32 && dtype != VTTS_BF16 && dtype != VTTS_BF16X3) return fail(VTTS_ERR_INVALID, "unknown dtype %d", dtype);
+    if (dtype != VTTS_F32 && dtype != VTTS_BF16 && dtype != VTTS_BF16X3) return failf(VTTS_ERR_INVALID, "unknown dtype %d", dtype);
     if (cfg->num_upsamples < 1 || cfg->num_upsamples > VTTS_MAX_UPSAMPLES)
-        return fail(VTTS_ERR_INVALID, "num_upsamples %d out of range", cfg->num_upsamples);
+        return failf(VTTS_ERR_INVALID, "num_upsamples %d out of range", cfg->num_upsamples);
     if (cfg->num_kernels < 1 || cfg->num_kernels > VTTS_MAX_KERNELS)
-        return fail(VTTS_ERR_INVALID, "num_kernels %d out of range", cfg->num_kernels);
+        return failf(VTTS_ERR_INVALID, "num_kernels %d out of range", cfg->num_kernels);
     if (cfg->num_mels < 1 || cfg->upsample_initial_channel < 1)
-        return fail(VTTS_ERR_INVALID, "num_mels / upsample_initial_channel must be positive");
+        return failf(VTTS_ERR_INVALID, "num_mels / upsample_initial_channel must be positive");
     if (cfg->upsample_initial_channel % (1 << cfg->num_upsamples) != 0)
-        return fail(VTTS_ERR_INVALID, "upsample_initial_channel %d not divisible by 2^%d", cfg->upsample_initial_channel,
-                    cfg->num_upsamples);
+        return failf(VTTS_ERR_INVALID, "upsample_initial_channel %d not divisible by 2^%d", cfg->upsample_initial_channel,
+                     cfg->num_upsamples);
     for (int i = 0; i < cfg->num_upsamples; ++i)
         if (cfg->upsample_rates[i] < 1 || cfg->upsample_kernel_sizes[i] < cfg->upsample_rates[i])
-            return fail(VTTS_ERR_INVALID, "bad upsample stage %d (rate %d, kernel %d)", i, cfg->upsample_rates[i],
-                        cfg->upsample_kernel_sizes[i]);
+            return failf(VTTS_ERR_INVALID, "bad upsample stage %d (rate %d, kernel %d)", i, cfg->upsample_rates[i],
+                         cfg->upsample_kernel_sizes[i]);
     for (int j = 0; j < cfg->num_kernels; ++j) {
         if (cfg->resblock_kernel_sizes[j] < 1 || cfg->resblock_kernel_sizes[j] % 2 == 0)
-            return fail(VTTS_ERR_INVALID, "resblock kernel size %d must be odd", cfg->resblock_kernel_sizes[j]);
+            return failf(VTTS_ERR_INVALID, "resblock kernel size %d must be odd", cfg->resblock_kernel_sizes[j]);
         for (int z = 0; z < (cfg->resblock == 2 ? 2 : 3); ++z)
-            if (cfg->resblock_dilation_sizes[j][z] < 1) return fail(VTTS_ERR_INVALID, "dilation must be >= 1");
+            if (cfg->resblock_dilation_sizes[j][z] < 1) return failf(VTTS_ERR_INVALID, "dilation must be >= 1");
     }
     if (cfg->resblock != 0 && cfg->resblock != 1 && cfg->resblock != 2)
-        return fail(VTTS_ERR_INVALID, "resblock must be 1 (ResBlock1) or 2 (ResBlock2), got %d", cfg->resblock);
-    if (device < 0) return fail(VTTS_ERR_INVALID, "device %d out of range", device);
+        return failf(VTTS_ERR_INVALID, "resblock must be 1 (ResBlock1) or 2 (ResBlock2), got %d", cfg->resblock);
+    if (device < 0) return failf(VTTS_ERR_INVALID, "device %d out of range", device);
     // the device itself is first touched in pack()/bind_packed(): planning needs no GPU
     auto* h = new (std::nothrow) vtts_hifigan();
-    if (!h) return fail(VTTS_ERR_NOMEM, "host allocation failed");
+    if (!h) return failf(VTTS_ERR_NOMEM, "host allocation failed");
     h->cfg = *cfg;
     if (h->cfg.resblock == 0) h->cfg.resblock = 1;
     h->device = device;
@@ -1182,15 +1165,15 @@ VTTS_API void vtts_hifigan_destroy(vtts_hifigan* h) {
 }
 
 VTTS_API int vtts_hifigan_num_params(const vtts_hifigan* h, int* n) {
-    if (!h || !n) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !n) return failf(VTTS_ERR_INVALID, "null argument");
     *n = 2 * (int)h->layers.size();
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_param_info(const vtts_hifigan* h, int i, const char** key, const char** which, int64_t shape[3],
                                      int* ndim) {
-    if (!h || !key || !which || !shape || !ndim) return fail(VTTS_ERR_INVALID, "null argument");
-    if (i < 0 || i >= 2 * (int)h->layers.size()) return fail(VTTS_ERR_INVALID, "parameter index %d out of range", i);
+    if (!h || !key || !which || !shape || !ndim) return failf(VTTS_ERR_INVALID, "null argument");
+    if (i < 0 || i >= 2 * (int)h->layers.size()) return failf(VTTS_ERR_INVALID, "parameter index %d out of range", i);
     const Layer& l = h->layers[i / 2];
     *key = l.key.c_str();
     if (i % 2 == 0) {
@@ -1210,38 +1193,38 @@ VTTS_API int vtts_hifigan_param_info(const vtts_hifigan* h, int i, const char** 
 
 VTTS_API int vtts_hifigan_set_param(vtts_hifigan* h, const char* key, const char* which, const float* host,
                                     const int64_t* shape, int ndim) {
-    if (!h || !key || !which || !host || !shape) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !key || !which || !host || !shape) return failf(VTTS_ERR_INVALID, "null argument");
     Layer* l = find_layer(h, key);
-    if (!l) return fail(VTTS_ERR_INVALID, "unknown parameter module '%s'", key);
+    if (!l) return failf(VTTS_ERR_INVALID, "unknown parameter module '%s'", key);
     if (!strcmp(which, "w")) {
         const int64_t d1 = (l->kind == KIND_CONV) ? l->cin : l->cout;
         const int64_t d2 = (l->kind == KIND_CONV) ? l->cout : l->cin;
         if (ndim != 3 || shape[0] != l->k || shape[1] != d1 || shape[2] != d2)
-            return fail(VTTS_ERR_SHAPE, "%s/w: expected [%d,%lld,%lld]", key, l->k, (long long)d1, (long long)d2);
+            return failf(VTTS_ERR_SHAPE, "%s/w: expected [%d,%lld,%lld]", key, l->k, (long long)d1, (long long)d2);
         l->w.assign(host, host + (size_t)l->k * l->cin * l->cout);
         l->have_w = true;
     } else if (!strcmp(which, "b")) {
-        if (ndim != 1 || shape[0] != l->cout) return fail(VTTS_ERR_SHAPE, "%s/b: expected [%d]", key, l->cout);
+        if (ndim != 1 || shape[0] != l->cout) return failf(VTTS_ERR_SHAPE, "%s/b: expected [%d]", key, l->cout);
         l->b.assign(host, host + l->cout);
         l->have_b = true;
     } else {
-        return fail(VTTS_ERR_INVALID, "parameter name must be \"w\" or \"b\", got \"%s\"", which);
+        return failf(VTTS_ERR_INVALID, "parameter name must be \"w\" or \"b\", got \"%s\"", which);
     }
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_packed_bytes(const vtts_hifigan* h, size_t* bytes) {
-    if (!h || !bytes) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
     *bytes = h->blob_bytes;
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_pack(vtts_hifigan* h, void* dev_blob, size_t blob_bytes, vtts_stream stream) {
-    if (!h || !dev_blob) return fail(VTTS_ERR_INVALID, "null argument");
-    if (blob_bytes < h->blob_bytes) return fail(VTTS_ERR_NOMEM, "blob too small: %zu < %zu", blob_bytes, h->blob_bytes);
-    if ((reinterpret_cast<uintptr_t>(dev_blob) & 255) != 0) return fail(VTTS_ERR_INVALID, "blob must be 256-B aligned");
+    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
+    if (blob_bytes < h->blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu", blob_bytes, h->blob_bytes);
+    if ((reinterpret_cast<uintptr_t>(dev_blob) & 255) != 0) return failf(VTTS_ERR_INVALID, "blob must be 256-B aligned");
     for (auto& l : h->layers)
-        if (!l.have_w || !l.have_b) return fail(VTTS_ERR_MISSING, "parameter %s/%s was never set", l.key.c_str(), l.have_w ? "b" : "w");
+        if (!l.have_w || !l.have_b) return failf(VTTS_ERR_MISSING, "parameter %s/%s was never set", l.key.c_str(), l.have_w ? "b" : "w");
     std::vector<char> host(h->blob_bytes, 0);
     if (h->dtype == VTTS_BF16) {
         for (auto& l : h->layers) {
@@ -1320,17 +1303,17 @@ VTTS_API int vtts_hifigan_pack(vtts_hifigan* h, void* dev_blob, size_t blob_byte
 }
 
 VTTS_API int vtts_hifigan_bind_packed(vtts_hifigan* h, void* dev_blob, size_t blob_bytes) {
-    if (!h || !dev_blob) return fail(VTTS_ERR_INVALID, "null argument");
-    if (blob_bytes < h->blob_bytes) return fail(VTTS_ERR_NOMEM, "blob too small: %zu < %zu", blob_bytes, h->blob_bytes);
-    if ((reinterpret_cast<uintptr_t>(dev_blob) & 255) != 0) return fail(VTTS_ERR_INVALID, "blob must be 256-B aligned");
+    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
+    if (blob_bytes < h->blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu", blob_bytes, h->blob_bytes);
+    if ((reinterpret_cast<uintptr_t>(dev_blob) & 255) != 0) return failf(VTTS_ERR_INVALID, "blob must be 256-B aligned");
     h->blob = static_cast<char*>(dev_blob);
     ++h->epoch;  // captured graphs hold the old blob's addresses
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_workspace_bytes(const vtts_hifigan* h, int B, int T, size_t* bytes) {
-    if (!h || !bytes) return fail(VTTS_ERR_INVALID, "null argument");
-    if (B <= 0 || T <= 0) return fail(VTTS_ERR_INVALID, "B and T must be positive");
+    if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
+    if (B <= 0 || T <= 0) return failf(VTTS_ERR_INVALID, "B and T must be positive");
     if (int rc = check_pass_size(h, B, T)) return rc;
     *bytes = plan_pass(h, B, T).bytes();
     return VTTS_OK;
@@ -1348,7 +1331,7 @@ int forward_maybe_graphed(vtts_hifigan* h, const float* mel, int B, int T, float
     if (!h->opt_graph || h->opt_profile || B <= 0 || T <= 0 || !h->blob || !plan_pass(h, B, T).par ||
         hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone)  // inside the CALLER's capture: just enqueue
         return forward_impl(h, mel, B, T, wav, ws, ws_bytes, s, Taps{});
-    if (hipSetDevice(h->device) != hipSuccess) return fail(VTTS_ERR_HIP, "hipSetDevice(%d) failed", h->device);  // graph launches too run on THIS handle's device
+    if (hipSetDevice(h->device) != hipSuccess) return failf(VTTS_ERR_HIP, "hipSetDevice(%d) failed", h->device);  // graph launches too run on THIS handle's device
     vtts_hifigan::GraphEntry* e = nullptr;
     for (auto& g : h->graphs)
         if (g.mel == mel && g.wav == wav && g.ws == ws && g.B == B && g.T == T) e = &g;
@@ -1417,14 +1400,14 @@ int forward_maybe_graphed(vtts_hifigan* h, const float* mel, int B, int T, float
 
 VTTS_API int vtts_hifigan_forward(vtts_hifigan* h, const float* mel_dev, int B, int T, float* wav_dev, void* workspace,
                                   size_t workspace_bytes, vtts_stream stream) {
-    if (!h || !mel_dev || !wav_dev) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !mel_dev || !wav_dev) return failf(VTTS_ERR_INVALID, "null argument");
     return forward_maybe_graphed(h, mel_dev, B, T, wav_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 VTTS_API int vtts_hifigan_forward_ragged(vtts_hifigan* h, const float* mel_dev, const int32_t* frames_dev, int B, int T, float* wav_dev,
                                          void* workspace, size_t workspace_bytes, vtts_stream stream) {
-    if (!h || !mel_dev || !frames_dev || !wav_dev) return fail(VTTS_ERR_INVALID, "null argument");
-    if (B <= 0 || T <= 0) return fail(VTTS_ERR_INVALID, "B and T must be positive (got B=%d, T=%d)", B, T);
+    if (!h || !mel_dev || !frames_dev || !wav_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (B <= 0 || T <= 0) return failf(VTTS_ERR_INVALID, "B and T must be positive (got B=%d, T=%d)", B, T);
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(wav_dev, 0, (size_t)B * h->hop * T * sizeof(float), s));  // samples past an utterance's end
     h->cur_lens = frames_dev;
@@ -1436,7 +1419,7 @@ VTTS_API int vtts_hifigan_forward_ragged(vtts_hifigan* h, const float* mel_dev, 
 }
 
 VTTS_API int vtts_hifigan_tap_elems(const vtts_hifigan* h, const char* tap, int B, int T, size_t* elems) {
-    if (!h || !tap || !elems) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !tap || !elems) return failf(VTTS_ERR_INVALID, "null argument");
     const vtts_hifigan_cfg& c = h->cfg;
     if (!strcmp(tap, "pre_tanh")) {
         *elems = (size_t)B * h->hop * T;
@@ -1448,18 +1431,18 @@ VTTS_API int vtts_hifigan_tap_elems(const vtts_hifigan* h, const char* tap, int 
     }
     if (!strncmp(tap, "ups_", 4) || !strncmp(tap, "mrf_", 4)) {
         const int i = atoi(tap + 4);
-        if (i < 0 || i >= c.num_upsamples) return fail(VTTS_ERR_INVALID, "tap stage %d out of range", i);
+        if (i < 0 || i >= c.num_upsamples) return failf(VTTS_ERR_INVALID, "tap stage %d out of range", i);
         long L = T;
         for (int q = 0; q <= i; ++q) L *= c.upsample_rates[q];
         *elems = (size_t)B * (c.upsample_initial_channel >> (i + 1)) * L;
         return VTTS_OK;
     }
-    return fail(VTTS_ERR_INVALID, "unknown tap '%s'", tap);
+    return failf(VTTS_ERR_INVALID, "unknown tap '%s'", tap);
 }
 
 VTTS_API int vtts_hifigan_forward_tap(vtts_hifigan* h, const float* mel_dev, int B, int T, float* wav_dev, void* workspace,
                                       size_t workspace_bytes, vtts_stream stream, const char* tap, float* tap_dev) {
-    if (!h || !mel_dev || !wav_dev || !tap || !tap_dev) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !mel_dev || !wav_dev || !tap || !tap_dev) return failf(VTTS_ERR_INVALID, "null argument");
     size_t n = 0;
     int rc = vtts_hifigan_tap_elems(h, tap, B, T, &n);
     if (rc) return rc;
@@ -1479,16 +1462,16 @@ struct DevBuf {
 
 VTTS_API int vtts_hifigan_run_module(vtts_hifigan* h, const char* key, const float* x_dev, int B, int L, float slope_in,
                                      const float* res_dev, float* y_dev, vtts_stream stream) {
-    if (!h || !key || !x_dev || !y_dev) return fail(VTTS_ERR_INVALID, "null argument");
-    if (!h->blob) return fail(VTTS_ERR_STATE, "run_module() before pack()/bind_packed()");
-    if (B <= 0 || L <= 0) return fail(VTTS_ERR_INVALID, "B and L must be positive");
+    if (!h || !key || !x_dev || !y_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h->blob) return failf(VTTS_ERR_STATE, "run_module() before pack()/bind_packed()");
+    if (B <= 0 || L <= 0) return failf(VTTS_ERR_INVALID, "B and L must be positive");
     Layer* l = find_layer(h, key);
-    if (!l) return fail(VTTS_ERR_INVALID, "unknown module '%s'", key);
+    if (!l) return failf(VTTS_ERR_INVALID, "unknown module '%s'", key);
     const bool is_pre = (l == &h->layers[h->idx_pre]);
     const bool is_post = (l == &h->layers[h->idx_post]);
     if (h->dtype == VTTS_BF16) {
         // the bf16 kernels form LeakyReLU as max(v, slope * v) (bf16_common.h: lrelu_f), valid for slopes in (0, 1]: the model's are 0.1 and 0.01
-        if (!(slope_in > 0.0f && slope_in <= 1.0f)) return fail(VTTS_ERR_INVALID, "run_module(): slope_in must lie in (0, 1] on a bf16 handle (got %g)", slope_in);
+        if (!(slope_in > 0.0f && slope_in <= 1.0f)) return failf(VTTS_ERR_INVALID, "run_module(): slope_in must lie in (0, 1] on a bf16 handle (got %g)", slope_in);
         // test hook: fp32 channels-last in/out, converted through temporary bf16 buffers
         hipStream_t st = static_cast<hipStream_t>(stream);
         const size_t nx = (size_t)B * L * l->cin, ny = (size_t)B * L * (l->kind == KIND_CONVT ? l->stride : 1) * l->cout;
@@ -1497,7 +1480,7 @@ VTTS_API int vtts_hifigan_run_module(vtts_hifigan* h, const char* key, const flo
         int rc = VTTS_OK;
         if (is_post) {
             HIP_TRY(hipMalloc(&xb, nx * 2));
-            if (launch_f32_to_bf16(x_dev, xb, nx, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conversion launch failed");
+            if (launch_f32_to_bf16(x_dev, xb, nx, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
             BConvArgs a;
             memset(&a, 0, sizeof(a));
             a.x = xb;
@@ -1505,22 +1488,22 @@ VTTS_API int vtts_hifigan_run_module(vtts_hifigan* h, const char* key, const flo
             a.bias = reinterpret_cast<const float*>(h->blob + l->off_b);
             a.B = B;
             a.L = L;
-            if (!rc && launch_conv_post_bf16(a, y_dev, nullptr, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conv_post launch failed");
+            if (!rc && launch_conv_post_bf16(a, y_dev, nullptr, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conv_post launch failed");
         } else {
             HIP_TRY(hipMalloc(&yb, ny * 2));
             if (!is_pre) {
                 HIP_TRY(hipMalloc(&xb, nx * 2));
-                if (launch_f32_to_bf16(x_dev, xb, nx, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conversion launch failed");
+                if (launch_f32_to_bf16(x_dev, xb, nx, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
             }
             if (res_dev) {
                 HIP_TRY(hipMalloc(&rb, ny * 2));
-                if (launch_f32_to_bf16(res_dev, rb, ny, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conversion launch failed");
+                if (launch_f32_to_bf16(res_dev, rb, ny, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
             }
             if (!rc) rc = run_layer_bf16(h, *l, is_pre ? static_cast<const void*>(x_dev) : xb, l->cin, l->cin, B, L, slope_in, 1.0f, rb, yb, 0, 1.f, st);
-            if (!rc && launch_bf16_to_f32(yb, y_dev, ny, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conversion launch failed");
+            if (!rc && launch_bf16_to_f32(yb, y_dev, ny, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
         }
         hipError_t e = hipStreamSynchronize(st);
-        if (!rc && e != hipSuccess) rc = fail(VTTS_ERR_HIP, "run_module failed: %s", hipGetErrorString(e));
+        if (!rc && e != hipSuccess) rc = failf(VTTS_ERR_HIP, "run_module failed: %s", hipGetErrorString(e));
         return rc;
     }
     Act x = is_pre ? Act{x_dev, (long)L * l->cin, 1, l->cin} : Act{x_dev, (long)l->cin * L, L, 1};
@@ -1529,19 +1512,19 @@ VTTS_API int vtts_hifigan_run_module(vtts_hifigan* h, const char* key, const flo
 }
 
 VTTS_API int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const float* x_dev, int B, int L, float* y_dev, vtts_stream stream) {
-    if (!h || !key_c1 || !x_dev || !y_dev) return fail(VTTS_ERR_INVALID, "null argument");
-    if (!h->blob) return fail(VTTS_ERR_STATE, "run_pair() before pack()/bind_packed()");
-    if (B <= 0 || L <= 0) return fail(VTTS_ERR_INVALID, "B and L must be positive");
+    if (!h || !key_c1 || !x_dev || !y_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h->blob) return failf(VTTS_ERR_STATE, "run_pair() before pack()/bind_packed()");
+    if (B <= 0 || L <= 0) return failf(VTTS_ERR_INVALID, "B and L must be positive");
     Layer* l = find_layer(h, key_c1);
     const Layer* c2 = l && l + 1 < h->layers.data() + h->layers.size() ? l + 1 : nullptr;
     if (h->dtype == VTTS_F32) {
         // fp32 / bf16x3 handle: x_dev / y_dev are [B, C, L] channel-major (the fp32 engine's layout); asynchronous on `stream`
         const bool x3 = c2 && pair_x3_wanted(h, *l, *c2, L);
         if (!x3 && (!c2 || !pair_f32_fusable(*l, *c2, L)))
-            return fail(VTTS_ERR_INVALID, "'%s' is not the first convolution of a ResBlock pair the fused fp32 kernel covers (C in {32, 64, 128}, L a multiple of 4)", key_c1);
+            return failf(VTTS_ERR_INVALID, "'%s' is not the first convolution of a ResBlock pair the fused fp32 kernel covers (C in {32, 64, 128}, L a multiple of 4)", key_c1);
         return run_pair_f32(h, *l, *c2, x3, x_dev, B, L, y_dev, ACC_STORE, 1.f, static_cast<hipStream_t>(stream));
     }
-    if (!l || !l->has_pair) return fail(VTTS_ERR_INVALID, "'%s' is not the first convolution of a fused ResBlock pair", key_c1);
+    if (!l || !l->has_pair) return failf(VTTS_ERR_INVALID, "'%s' is not the first convolution of a fused ResBlock pair", key_c1);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t n = (size_t)B * L * l->cin;
     DevBuf xbuf, ybuf;
@@ -1549,16 +1532,16 @@ VTTS_API int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const fl
     HIP_TRY(hipMalloc(&xb, n * 2));
     HIP_TRY(hipMalloc(&yb, n * 2));
     int rc = VTTS_OK;
-    if (launch_f32_to_bf16(x_dev, xb, n, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conversion launch failed");
+    if (launch_f32_to_bf16(x_dev, xb, n, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
     if (!rc) rc = run_pair_bf16(h, *l, xb, B, L, 1.0f, yb, 0, 1.f, st);
-    if (!rc && launch_bf16_to_f32(yb, y_dev, n, st) != hipSuccess) rc = fail(VTTS_ERR_HIP, "conversion launch failed");
+    if (!rc && launch_bf16_to_f32(yb, y_dev, n, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
     hipError_t e = hipStreamSynchronize(st);
-    if (!rc && e != hipSuccess) rc = fail(VTTS_ERR_HIP, "run_pair failed: %s", hipGetErrorString(e));
+    if (!rc && e != hipSuccess) rc = failf(VTTS_ERR_HIP, "run_pair failed: %s", hipGetErrorString(e));
     return rc;
 }
 
 VTTS_API int vtts_hifigan_set_option(vtts_hifigan* h, const char* name, int64_t value) {
-    if (!h || !name) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !name) return failf(VTTS_ERR_INVALID, "null argument");
     {  // setting a WRITABLE option to the value it has changes nothing: captured graphs stay valid (read-only and unknown names fall through to their errors)
         static const char* const writable[] = {"kernels", "microbatch", "fuse", "streams", "graph", "zigzag", "chains", "tiles", "tail", "stage"};
         for (const char* w : writable) {
@@ -1568,47 +1551,47 @@ VTTS_API int vtts_hifigan_set_option(vtts_hifigan* h, const char* name, int64_t 
     }
     ++h->epoch;  // a captured launch sequence reflects the options it was captured under
     if (!strcmp(name, "kernels")) {
-        if (value != 0 && value != 1) return fail(VTTS_ERR_INVALID, "kernels must be 0 (auto) or 1 (generic)");
+        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "kernels must be 0 (auto) or 1 (generic)");
         h->opt_kernels = value;
     } else if (!strcmp(name, "microbatch")) {
-        if (value < 0) return fail(VTTS_ERR_INVALID, "microbatch must be >= 0");
+        if (value < 0) return failf(VTTS_ERR_INVALID, "microbatch must be >= 0");
         h->opt_microbatch = value;
     } else if (!strcmp(name, "fuse")) {
-        if (value < 0 || value > 3) return fail(VTTS_ERR_INVALID, "fuse must be 0 (per convolution), 1 (pairs), 2 (bf16: pairs + whole ResBlocks where faster; fp32: pairs at C <= 64) or 3 (... wherever supported)");
+        if (value < 0 || value > 3) return failf(VTTS_ERR_INVALID, "fuse must be 0 (per convolution), 1 (pairs), 2 (bf16: pairs + whole ResBlocks where faster; fp32: pairs at C <= 64) or 3 (... wherever supported)");
         h->opt_fuse = value;
     } else if (!strcmp(name, "streams")) {
-        if (value < 0 || value > 4) return fail(VTTS_ERR_INVALID, "streams must be 1..4 (0 = the engine's default)");
+        if (value < 0 || value > 4) return failf(VTTS_ERR_INVALID, "streams must be 1..4 (0 = the engine's default)");
         h->opt_streams = value;
     } else if (!strcmp(name, "graph")) {
-        if (value != 0 && value != 1) return fail(VTTS_ERR_INVALID, "graph must be 0 (always eager) or 1 (small launches replay a captured hipGraph)");
+        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "graph must be 0 (always eager) or 1 (small launches replay a captured hipGraph)");
         h->opt_graph = value;
     } else if (!strcmp(name, "zigzag")) {
-        if (value != 0 && value != 1) return fail(VTTS_ERR_INVALID, "zigzag must be 0 or 1");
+        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "zigzag must be 0 or 1");
         h->opt_zigzag = value;
     } else if (!strcmp(name, "chains")) {
-        if (value < 0 || value > 2) return fail(VTTS_ERR_INVALID, "chains must be 0 (ResBlocks of a stage one after the other), 1 (side by side on small fp32 launches) or 2 (... on every single-micro-batch launch)");
+        if (value < 0 || value > 2) return failf(VTTS_ERR_INVALID, "chains must be 0 (ResBlocks of a stage one after the other), 1 (side by side on small fp32 launches) or 2 (... on every single-micro-batch launch)");
         h->opt_chains = value;
     } else if (!strcmp(name, "tiles")) {
-        if (value < 0 || value > 2) return fail(VTTS_ERR_INVALID, "tiles must be 0 (auto), 1 (wide) or 2 (narrow)");
+        if (value < 0 || value > 2) return failf(VTTS_ERR_INVALID, "tiles must be 0 (auto), 1 (wide) or 2 (narrow)");
         h->opt_tiles = value;
     } else if (!strcmp(name, "tail")) {
-        if (value != 0 && value != 1) return fail(VTTS_ERR_INVALID, "tail must be 0 or 1");
+        if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "tail must be 0 or 1");
         h->opt_tail = value;
     } else if (!strcmp(name, "stage")) {  // kept for callers that still set it: 0 is the only path there is
-        if (value != 0) return fail(VTTS_ERR_INVALID, "stage must be 0: the whole-stage kernel was removed (it measured slower, profiles/r06_a_stage_kernel_findings.md)");
+        if (value != 0) return failf(VTTS_ERR_INVALID, "stage must be 0: the whole-stage kernel was removed (it measured slower, profiles/r06_a_stage_kernel_findings.md)");
     } else if (!strcmp(name, "profile")) {
         h->opt_profile = value ? 1 : 0;
     } else if (!strcmp(name, "hop") || !strcmp(name, "pass_frames") || !strcmp(name, "max_frames_per_pass") || !strcmp(name, "graphs_cached") ||
                !strcmp(name, "profile_C") || !strcmp(name, "profile_K")) {
-        return fail(VTTS_ERR_INVALID, "option '%s' is read-only", name);
+        return failf(VTTS_ERR_INVALID, "option '%s' is read-only", name);
     } else {
-        return fail(VTTS_ERR_INVALID, "unknown option '%s'", name);
+        return failf(VTTS_ERR_INVALID, "unknown option '%s'", name);
     }
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_get_option(const vtts_hifigan* h, const char* name, int64_t* value) {
-    if (!h || !name || !value) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h || !name || !value) return failf(VTTS_ERR_INVALID, "null argument");
     if (!strcmp(name, "kernels")) *value = h->opt_kernels;
     else if (!strcmp(name, "microbatch")) *value = h->opt_microbatch;
     else if (!strcmp(name, "profile")) *value = h->opt_profile;
@@ -1634,13 +1617,13 @@ VTTS_API int vtts_hifigan_get_option(const vtts_hifigan* h, const char* name, in
     else if (!strcmp(name, "pass_frames")) *value = pass_frames(h);
     else if (!strcmp(name, "profile_C")) *value = h->prof_C;
     else if (!strcmp(name, "profile_K")) *value = h->prof_K;
-    else return fail(VTTS_ERR_INVALID, "unknown option '%s'", name);
+    else return failf(VTTS_ERR_INVALID, "unknown option '%s'", name);
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_profile_read(vtts_hifigan* h, double* resblock_ms, int64_t* launches, double* resblock_flops,
                                        int reset) {
-    if (!h) return fail(VTTS_ERR_INVALID, "null argument");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     double ms = 0.0;
     for (size_t i = 0; i < h->prof_used; ++i) {
         float t = 0.f;

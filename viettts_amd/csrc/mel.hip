@@ -25,7 +25,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -35,7 +34,7 @@
 #include "../../include/vtts_mel.h"
 #include "vtts_internal.h"
 
-#define VTTS_API extern "C" __attribute__((visibility("default")))
+using vtts::failf;
 
 namespace {
 
@@ -59,15 +58,6 @@ constexpr int OFF_SPW = OFF_BAND + 3 * MAX_MELS;          // [MAX_NNZ] the bands
 constexpr int BLOB_FLOATS = OFF_SPW + MAX_NNZ + 2;
 
 constexpr size_t LDS_BYTES = (size_t)(SPAN + FPB * 2 * XBUF + MAX_NNZ) * sizeof(float);
-
-int failf(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return vtts::set_error(code, buf);
-}
 
 struct MelRows {
     int len[ROWS_PER_LAUNCH];  // samples of each row of this launch

@@ -25,226 +25,22 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/vtts_hifigan.h"
 #include "bf16_common.h"
+#include "nat_model.h"
 #include "vtts_internal.h"
 
-#define VTTS_API extern "C" __attribute__((visibility("default")))
-
-namespace {
-
-int failf(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return vtts::set_error(code, buf);
-}
-
-#define HIP_TRYN(expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess)                                                                            \
-            return failf(VTTS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-struct Arr {
-    std::string module, name;
-    std::vector<int64_t> shape;
-    std::vector<float> host;
-    bool have = false;
-    size_t off = 0;  // byte offset in the packed blob
-    size_t elems() const {
-        size_t n = 1;
-        for (auto d : shape) n *= (size_t)d;
-        return n;
-    }
-};
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Arrays a model takes from the checkpoint (Haiku module tail + array name), their place in the packed device blob, and
-// the derived per-BatchNorm vectors inv = scale * rsqrt(var + eps) appended behind them.
-struct NatModel {
-    const char* what = "model";
-    int device = 0;
-    std::vector<Arr> arrs;
-    std::vector<std::pair<std::string, int>> bns;  // (BatchNorm module tail, channels)
-    std::vector<size_t> bn_off;
-    struct Extra {  // a kernel-private re-layout of checkpoint arrays, built at pack() time behind the plain arrays
-        std::string key;
-        size_t bytes = 0, off = 0;
-        std::function<void(const NatModel&, float*)> fill;
-    };
-    std::vector<Extra> extras;
-    size_t blob_bytes = 0;
-    char* blob = nullptr;
-
-    void add(const std::string& m, const char* n, std::vector<int64_t> shp) {
-        Arr a;
-        a.module = m;
-        a.name = n;
-        a.shape = std::move(shp);
-        arrs.push_back(a);
-    }
-    void add_bn(const std::string& m, int C) {
-        add(m, "scale", {1, 1, C});
-        add(m, "offset", {1, 1, C});
-        add(m + "/~/mean_ema", "average", {1, 1, C});
-        add(m + "/~/var_ema", "average", {1, 1, C});
-        bns.emplace_back(m, C);
-    }
-    // TokenEncoder (model.py:12-24): Embed, 3 x (Conv1D k=3 + BatchNorm), forward LSTM, backward LSTM
-    void add_token_encoder(const std::string& te, int V, int D) {
-        add(te + "embed", "embeddings", {V, D});
-        for (int i = 0; i < 3; ++i) {
-            const std::string sfx = i ? "_" + std::to_string(i) : "";
-            add(te + "conv1_d" + sfx, "w", {3, D, D});
-            add(te + "conv1_d" + sfx, "b", {D});
-            add_bn(te + "batch_norm" + sfx, D);
-        }
-        for (const char* l : {"lstm/linear", "lstm_1/linear"}) {
-            add(te + l, "w", {2 * D, 4 * D});
-            add(te + l, "b", {4 * D});
-            add_lstm_mfma(te + l, 2 * D, D);  // rows [x ; h] as hk.LSTM concatenates them
-        }
-    }
-    // an hk.LSTM's [K][4H] matrix in MFMA A-fragment order for nat_dec_lstm_k: [slice = 8 units][K/8][lane][4],
-    // element i of lane = W[hrow(8*kb + 4*(lane/32) + i)][gate*H + 8*slice + unit], (unit, gate) = ((lane%32)/4, (lane%32)%4);
-    // hrow maps a row of the kernel's state order to the row of the Haiku matrix (identity unless the caller permutes)
-    void add_lstm_mfma(const std::string& mod, int K, int H, std::function<int(int)> hrow = nullptr, const char* key = "#mfma") {
-        add_extra(mod + key, (size_t)K * 4 * H * sizeof(float), [mod, K, H, hrow](const NatModel& m, float* out) {
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            const int NIT = K / 8;
-            for (int sl = 0; sl < H / 8; ++sl)
-                for (int kb = 0; kb < NIT; ++kb)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int mrow = lane & 31, lh = lane >> 5, col = (mrow & 3) * H + 8 * sl + (mrow >> 2);
-                        for (int i = 0; i < 4; ++i) {
-                            const int zr = 8 * kb + 4 * lh + i;
-                            out[(((size_t)sl * NIT + kb) * 64 + lane) * 4 + i] = W[(size_t)(hrow ? hrow(zr) : zr) * 4 * H + col];
-                        }
-                    }
-        });
-    }
-    void add_extra(const std::string& key, size_t bytes, std::function<void(const NatModel&, float*)> fill) {
-        Extra e;
-        e.key = key;
-        e.bytes = bytes;
-        e.fill = std::move(fill);
-        extras.push_back(std::move(e));
-    }
-    const float* extra(const std::string& key) const {
-        for (auto& e : extras)
-            if (e.key == key) return reinterpret_cast<const float*>(blob + e.off);
-        return nullptr;
-    }
-    void layout() {
-        size_t off = 0;
-        for (auto& a : arrs) {
-            a.off = off;
-            off = align_up(off + a.elems() * sizeof(float), 256);
-        }
-        for (auto& b : bns) {
-            bn_off.push_back(off);
-            off = align_up(off + (size_t)b.second * sizeof(float), 256);
-        }
-        for (auto& e : extras) {
-            e.off = off;
-            off = align_up(off + e.bytes, 256);
-        }
-        blob_bytes = off;
-    }
-    int find(const std::string& module, const char* name) const {
-        for (size_t i = 0; i < arrs.size(); ++i)
-            if (arrs[i].module == module && arrs[i].name == name) return (int)i;
-        return -1;
-    }
-    const float* dev(const std::string& module, const char* name) const { return reinterpret_cast<const float*>(blob + arrs[find(module, name)].off); }
-    const float* inv(const std::string& bn) const {
-        for (size_t i = 0; i < bns.size(); ++i)
-            if (bns[i].first == bn) return reinterpret_cast<const float*>(blob + bn_off[i]);
-        return nullptr;
-    }
-
-    int param_info(int i, const char** module, const char** name, int64_t shape[3], int* ndim) const {
-        if (i < 0 || i >= (int)arrs.size()) return failf(VTTS_ERR_INVALID, "parameter index out of range");
-        const Arr& a = arrs[i];
-        if (module) *module = a.module.c_str();
-        if (name) *name = a.name.c_str();
-        if (shape)
-            for (int d = 0; d < 3; ++d) shape[d] = d < (int)a.shape.size() ? a.shape[d] : 1;
-        if (ndim) *ndim = (int)a.shape.size();
-        return VTTS_OK;
-    }
-    int set_param(const char* module, const char* name, const float* host, const int64_t* shape, int ndim) {
-        if (!module || !name || !host || !shape) return failf(VTTS_ERR_INVALID, "null argument");
-        const int i = find(module, name);
-        if (i < 0) return failf(VTTS_ERR_INVALID, "%s has no array '%s' in module '%s'", what, name, module);
-        Arr& a = arrs[i];
-        if (ndim != (int)a.shape.size()) return failf(VTTS_ERR_SHAPE, "%s/%s: expected %zu dimensions, got %d", module, name, a.shape.size(), ndim);
-        for (int d = 0; d < ndim; ++d)
-            if (shape[d] != a.shape[d])
-                return failf(VTTS_ERR_SHAPE, "%s/%s: dimension %d is %lld, expected %lld", module, name, d, (long long)shape[d], (long long)a.shape[d]);
-        a.host.assign(host, host + a.elems());
-        a.have = true;
-        return VTTS_OK;
-    }
-    int pack(void* dev_blob, size_t bytes, void* stream) {
-        if (!dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-        if (bytes < blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", bytes, blob_bytes);
-        for (auto& a : arrs)
-            if (!a.have) return failf(VTTS_ERR_MISSING, "array %s/%s was never set", a.module.c_str(), a.name.c_str());
-        std::vector<char> img(blob_bytes, 0);
-        for (auto& a : arrs) memcpy(img.data() + a.off, a.host.data(), a.elems() * sizeof(float));
-        for (size_t i = 0; i < bns.size(); ++i) {
-            const Arr& sc = arrs[find(bns[i].first, "scale")];
-            const Arr& var = arrs[find(bns[i].first + "/~/var_ema", "average")];
-            float* iv = reinterpret_cast<float*>(img.data() + bn_off[i]);
-            for (int c = 0; c < bns[i].second; ++c) iv[c] = sc.host[c] / std::sqrt(var.host[c] + 1e-5f);  // hk.BatchNorm eps
-        }
-        for (auto& e : extras) e.fill(*this, reinterpret_cast<float*>(img.data() + e.off));
-        HIP_TRYN(hipMemcpyAsync(dev_blob, img.data(), blob_bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
-        HIP_TRYN(hipStreamSynchronize(static_cast<hipStream_t>(stream)));  // img dies at return
-        blob = static_cast<char*>(dev_blob);
-        return VTTS_OK;
-    }
-    int bind(void* dev_blob, size_t bytes) {
-        if (!dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-        if (bytes < blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", bytes, blob_bytes);
-        blob = static_cast<char*>(dev_blob);
-        return VTTS_OK;
-    }
-};
-
-}  // namespace
+using namespace vtts;
 
 struct vtts_nat_duration : NatModel {
     vtts_nat_duration_cfg cfg;
 };
-// round-to-nearest-even bf16 of a float (host side of the bf16x3 split: v0 = bf16(v), v1 = bf16(v - v0); v - v0 is exact in fp32)
-static inline unsigned short nat_bf16_rne(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-static inline float nat_bf16_to_float(unsigned short h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 struct vtts_nat_acoustic : NatModel {
     vtts_nat_acoustic_cfg cfg;
     int x3 = 0;  // option "bf16x3": LSTM steps, gate GEMM and postnet as three bf16 x bf16 terms per product on the bf16 matrix pipe
@@ -340,7 +136,7 @@ __global__ __launch_bounds__(256) void nat_conv_bn_act_k(const float* __restrict
 
 // Postnet convolutions (model.py:113-121) and the hoisted gate GEMMs on the fp32 matrix cores: y = act(batchnorm_eval(conv1d_same(x))) [+ res],
 // channels-last fp32 rows, same zero-beyond-the-length semantics as nat_conv_bn_act_k.  GEMM view: M = cout (A = weights, host-packed
-// [mblk][32-channel step][tap][lane][16]: element i of lane = W[tap][32*cs + 16*(lane/32) + i][32*mblk + lane%32]), N = frame,
+// by pack_conv_frag_f32, nat_model.h), N = frame,
 // k = (32-channel step, tap, channel).  A workgroup = 64 frames x (4 waves x MR m-blocks); a wave owns MR x 2 accumulator blocks.
 // Round 4: the B operand goes through LDS.  Round 1-3 had every lane read 64 contiguous bytes of ITS frame's row per step and tap straight
 // from L1 (no LDS, no barrier): 64 lanes x 16 bytes from 32 different rows per instruction, five times over for the five taps — the kernel
@@ -1653,9 +1449,9 @@ int run_token_encoder(const NatModel& m, const std::string& te, int V, int D, co
         float* xt = lstm_ws;                                   // [2][Lmax] slabs
         float* hs = xt + 2 * (size_t)Lmax * slab;              // [2][Lmax + 1] slabs
         float* cs = hs + 2 * ((size_t)Lmax + 1) * slab;        // [2] slabs
-        HIP_TRYN(hipMemsetAsync(hs, 0, slab * 4, s));
-        HIP_TRYN(hipMemsetAsync(hs + ((size_t)Lmax + 1) * slab, 0, slab * 4, s));
-        HIP_TRYN(hipMemsetAsync(cs, 0, 2 * slab * 4, s));
+        HIP_TRY(hipMemsetAsync(hs, 0, slab * 4, s));
+        HIP_TRY(hipMemsetAsync(hs + ((size_t)Lmax + 1) * slab, 0, slab * 4, s));
+        HIP_TRY(hipMemsetAsync(cs, 0, 2 * slab * 4, s));
         const int gy = (int)std::min<size_t>((slab / 4 + 255) / 256, 64);
         hipLaunchKernelGGL(nat_enc_scatter_k, dim3(Lmax, gy, 2), dim3(256), 0, s, cur, lengths, xt, B, Bp, Lmax, D);
         const bool wide = B > 32;  // two 32-sentence tiles per wave once there are that many sentences
@@ -1663,7 +1459,7 @@ int run_token_encoder(const NatModel& m, const std::string& te, int V, int D, co
         NatLstmOps o[2];
         for (int dir = 0; dir < 2; ++dir) {
             const std::string mod = te + (dir ? "lstm_1/linear" : "lstm/linear");
-            o[dir].wpk = reinterpret_cast<const float4*>(m.extra(mod + "#mfma"));
+            o[dir].wpk = m.extra<float4>(mod + "#mfma");
             o[dir].bias = m.dev(mod, "b");
             o[dir].cst = cs + dir * slab;
             o[dir].gin = nullptr;
@@ -1691,6 +1487,58 @@ int check_encoder_dims(const char* what, int D, int V) {
                      what, D, V);
     return VTTS_OK;
 }
+
+// ---- workspaces: a layout is one walk over its buffers, each 256-byte aligned.  Over the caller's base pointer the walk yields the buffers, over
+// nullptr only `bytes`, so the *_workspace_bytes entry points and the passes read the same statement. ----
+struct NatCarver {
+    char* base = nullptr;
+    size_t bytes = 0;
+    float* take(size_t n) {
+        float* r = base ? reinterpret_cast<float*>(base + bytes) : nullptr;
+        bytes += align_up(n, 256);
+        return r;
+    }
+};
+struct NatDurationWs : NatCarver {
+    float *bufA, *bufB, *enc, *lstm_ws;
+    NatDurationWs(const vtts_nat_duration_cfg& c, int B, int Lmax, void* ws) : NatCarver{static_cast<char*>(ws)} {
+        const size_t BLD = (size_t)B * Lmax * c.lstm_dim * 4;
+        bufA = take(BLD), bufB = take(BLD), enc = take(2 * BLD);  // two ping-pong [B][Lmax][D] buffers + the encoder output [B][Lmax][2D]
+        lstm_ws = take(nat_enc_lstm_floats(c.lstm_dim, B, Lmax) * 4);
+    }
+};
+// the resident decoder's share of the workspace (whether the option is set or not: a workspace sized once serves both paths): 256 bytes of polled
+// words (arrival counter, abort word; development builds' phase clocks) in front, then the exchange buffer
+constexpr size_t NAT_RES_WS_BYTES = 256 + (size_t)NAT_RES_XCH_ELEMS * 4 * sizeof(float);
+static_assert(NAT_RES_WS_BYTES % 256 == 0, "workspace blocks are 256-byte aligned");
+size_t nat_dec_state_floats(const vtts_nat_acoustic_cfg& c, int B) {
+    const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, ZW = 2 * H + c.prenet_dim;  // rows [p | h1 | h2]
+    return (2 * ZW + 2 * H) * Bp;
+}
+struct NatAcousticWs : NatCarver {
+    float *bufA, *bufB, *enc, *EG1, *EG2, *mel0, *pA, *pB, *dstate, *G1, *G2, *lstm_ws;
+    unsigned* res_sync;
+    NatAcousticWs() = default;
+    NatAcousticWs(const vtts_nat_acoustic_cfg& c, int B, int Lmax, int Fmax, void* ws) : NatCarver{static_cast<char*>(ws)} {
+        const size_t BLD = (size_t)B * Lmax * c.encoder_dim * 4, BF = (size_t)B * Fmax * 4, G = (size_t)4 * c.decoder_dim;
+        bufA = take(BLD), bufB = take(BLD), enc = take(2 * BLD);           // encoder ping-pong + output
+        EG1 = take((size_t)B * Lmax * G * 4), EG2 = take((size_t)B * Lmax * G * 4);  // enc @ W_l[0:E] per token
+        mel0 = take(BF * c.mel_dim);                                       // decoder mel
+        pA = take(BF * c.postnet_dim), pB = take(BF * c.postnet_dim);      // postnet ping-pong
+        dstate = take(nat_dec_state_floats(c, B) * 4);                     // decoder state Z[2], c1, c2
+        G1 = take(BF * G), G2 = take(BF * G);                              // hoisted gate pre-activations
+        lstm_ws = take(nat_enc_lstm_floats(c.encoder_dim, B, Lmax) * 4);   // encoder LSTMs' scratch
+        res_sync = reinterpret_cast<unsigned*>(take(NAT_RES_WS_BYTES));    // resident decoder: counters, exchange buffer
+    }
+};
+// what the teacher-forced pass needs behind forward()'s layout `a`: the prenet's two layers, the hidden sequence, the recurrent state
+struct NatTeacherWs : NatCarver {
+    float *P1, *P2, *hseq, *tstate;
+    NatTeacherWs(const NatAcousticWs& a, const vtts_nat_acoustic_cfg& c, int B, int Fmax) : NatCarver{a.base, a.bytes} {
+        const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, BF = (size_t)B * Fmax * 4;
+        P1 = take(BF * c.prenet_dim), P2 = take(BF * c.prenet_dim), hseq = take(BF * 2 * H), tstate = take(7 * H * Bp * 4);
+    }
+};
 
 }  // namespace
 
@@ -1743,9 +1591,7 @@ VTTS_API int vtts_nat_duration_bind_packed(vtts_nat_duration* h, void* dev_blob,
 VTTS_API int vtts_nat_duration_workspace_bytes(const vtts_nat_duration* h, int B, int Lmax, size_t* bytes) {
     if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
     if (B <= 0 || Lmax <= 0) return failf(VTTS_ERR_INVALID, "B and Lmax must be positive (got %d, %d)", B, Lmax);
-    const size_t D = h->cfg.lstm_dim;
-    // two ping-pong [B][Lmax][D] buffers + the encoder output [B][Lmax][2D] + the LSTMs' scratch
-    *bytes = 2 * align_up((size_t)B * Lmax * D * 4, 256) + align_up((size_t)B * Lmax * 2 * D * 4, 256) + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256);
+    *bytes = NatDurationWs(h->cfg, B, Lmax, nullptr).bytes;
     return VTTS_OK;
 }
 VTTS_API int vtts_nat_duration_forward(vtts_nat_duration* h, const int32_t* tokens_dev, const int32_t* lengths_dev, int B, int Lmax,
@@ -1758,14 +1604,10 @@ VTTS_API int vtts_nat_duration_forward(vtts_nat_duration* h, const int32_t* toke
     if (!workspace || workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int D = h->cfg.lstm_dim, V = h->cfg.vocab_size;
-    const size_t per = align_up((size_t)B * Lmax * D * 4, 256);
-    float* bufA = reinterpret_cast<float*>(static_cast<char*>(workspace));
-    float* bufB = reinterpret_cast<float*>(static_cast<char*>(workspace) + per);
-    float* enc = reinterpret_cast<float*>(static_cast<char*>(workspace) + 2 * per);
-    float* lstm_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + 2 * per + align_up((size_t)B * Lmax * 2 * D * 4, 256));
-    rc = run_token_encoder(*h, "token_encoder/~/", V, D, tokens_dev, lengths_dev, B, Lmax, bufA, bufB, lstm_ws, enc, s);
+    const NatDurationWs ws(h->cfg, B, Lmax, workspace);
+    rc = run_token_encoder(*h, "token_encoder/~/", V, D, tokens_dev, lengths_dev, B, Lmax, ws.bufA, ws.bufB, ws.lstm_ws, ws.enc, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(nat_duration_head_k, dim3(Lmax, B), dim3(D), (2 * D + 16) * sizeof(float), s, enc, lengths_dev, h->dev("linear", "w"),
+    hipLaunchKernelGGL(nat_duration_head_k, dim3(Lmax, B), dim3(D), (2 * D + 16) * sizeof(float), s, ws.enc, lengths_dev, h->dev("linear", "w"),
                        h->dev("linear", "b"), h->dev("linear_1", "w"), h->dev("linear_1", "b"), durations_dev, Lmax, D);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(VTTS_ERR_HIP, "duration model launch failed: %s", hipGetErrorString(e));
@@ -1785,7 +1627,7 @@ VTTS_API int vtts_nat_acoustic_create(const vtts_nat_acoustic_cfg* cfg, int devi
     h->what = "acoustic model";
     h->cfg = *cfg;
     h->device = device;
-    const int X = 2 * D + PN;
+    const int E = 2 * D, X = E + PN, G4 = 4 * H;
     h->add_token_encoder("token_encoder/~/", V, D);
     h->add("lstm/linear", "w", {X + H, 4 * H});          // decoder layer 1: [x ; h1]
     h->add("lstm/linear", "b", {4 * H});
@@ -1802,158 +1644,52 @@ VTTS_API int vtts_nat_acoustic_create(const vtts_nat_acoustic_cfg* cfg, int devi
         h->add("conv1_d" + sfx, "b", {cout});
         if (i < 4) h->add_bn("batch_norm" + sfx, PD);
     }
-    // postnet convolution weights in MFMA A-fragment order (nat_conv_mfma_k): [mblk][32-channel step][tap][lane][16]
-    for (int i = 0; i < 5; ++i) {
-        const std::string mod = "conv1_d" + (i ? "_" + std::to_string(i) : std::string());
-        const int cin = i == 0 ? MEL : PD, cout = i == 4 ? MEL : PD, MB = (cout + 31) / 32, NCS = (cin + 31) / 32;
-        h->add_extra(mod + "#mfma", (size_t)MB * NCS * 5 * 64 * 16 * sizeof(float), [mod, cin, cout, MB, NCS](const NatModel& m, float* out) {
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            for (int mb = 0; mb < MB; ++mb)
-                for (int cs = 0; cs < NCS; ++cs)
-                    for (int j = 0; j < 5; ++j)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 16; ++e) {
-                                const int c = 32 * cs + 16 * (lane >> 5) + e, co = 32 * mb + (lane & 31);
-                                out[((((size_t)mb * NCS + cs) * 5 + j) * 64 + lane) * 16 + e] = (c < cin && co < cout) ? W[((size_t)j * cin + c) * cout + co] : 0.0f;
-                            }
-        });
-    }
-    // ... and split into two bf16 terms for nat_conv_x3_k: [mblk][step][tap][16-channel half][hi | lo][lane][8] bf16
-    for (int i = 0; i < 5; ++i) {
-        const std::string mod = "conv1_d" + (i ? "_" + std::to_string(i) : std::string());
-        const int cin = i == 0 ? MEL : PD, cout = i == 4 ? MEL : PD, MB = (cout + 31) / 32, NCS = (cin + 31) / 32;
-        h->add_extra(mod + "#x3", (size_t)MB * NCS * 5 * 4 * 64 * 8 * sizeof(unsigned short), [mod, cin, cout, MB, NCS](const NatModel& m, float* outf) {
-            unsigned short* out = reinterpret_cast<unsigned short*>(outf);
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            for (int mb = 0; mb < MB; ++mb)
-                for (int cs = 0; cs < NCS; ++cs)
-                    for (int j = 0; j < 5; ++j)
-                        for (int ks = 0; ks < 2; ++ks)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int c = 32 * cs + 16 * ks + 8 * (lane >> 5) + e, co = 32 * mb + (lane & 31);
-                                    const float w = (c < cin && co < cout) ? W[((size_t)j * cin + c) * cout + co] : 0.0f;
-                                    const unsigned short hi = nat_bf16_rne(w), lo = nat_bf16_rne(w - nat_bf16_to_float(hi));
-                                    const size_t base = ((((size_t)mb * NCS + cs) * 5 + j) * 4 + ks * 2) * 64;
-                                    out[(base + lane) * 8 + e] = hi;
-                                    out[(base + 64 + lane) * 8 + e] = lo;
-                                }
-        });
-    }
+    // The kernels' private layouts behind the plain arrays (nat_model.h states each one at its packer), in the blob's order.
+    // The postnet's convolutions for nat_conv_mfma_k, then their bf16 split for nat_conv_x3_k
+    for (int x3 = 0; x3 < 2; ++x3)
+        for (int i = 0; i < 5; ++i) {
+            const std::string mod = "conv1_d" + (i ? "_" + std::to_string(i) : std::string());
+            const int cin = i == 0 ? MEL : PD, cout = i == 4 ? MEL : PD;
+            h->add_conv_frag(mod + (x3 ? "#x3" : "#mfma"), mod, x3, 5, 0, cin, cout, cout);
+        }
     // projection and prenet matrices in [row / 4][col][4] order (nat_dec_proj_prenet_k: one 16-byte load = 4 rows of a column)
     for (const char* l : {"linear", "linear_1", "linear_2"}) {
         const std::string mod = l;
         const int rows = mod == "linear" ? 2 * H : (mod == "linear_1" ? MEL : PN), cols = mod == "linear" ? MEL : PN;
-        h->add_extra(mod + "#k4", (size_t)rows * cols * sizeof(float), [mod, rows, cols](const NatModel& m, float* out) {
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
+        h->add_extra(mod + "#k4", (size_t)rows * cols * sizeof(float), [mod, rows, cols](const NatModel& m, void* outv) {
+            const float* W = m.host(mod, "w");
+            float* out = static_cast<float*>(outv);
             for (int k = 0; k < rows; ++k)
                 for (int c = 0; c < cols; ++c) out[((size_t)(k >> 2) * cols + c) * 4 + (k & 3)] = W[(size_t)k * cols + c];
         });
     }
-    // decoder LSTM weights in the step kernel's order (add_lstm_mfma).  Haiku's matrices are [cond ; p ; h1] (layer 1) and
-    // [cond ; p ; h1 ; h2] (layer 2: hk.deep_rnn_with_skip_connections puts the network input first); the per-frame step multiplies
-    // the state rows [p ; h1] / [p ; h1 ; h2] = Haiku rows E + r, and the cond rows [0, E) go into the GEMM ahead of the loop:
-    // "#cond" = those rows as a one-tap convolution for nat_conv_mfma_k with the output columns in the step kernel's accumulator order
-    // c' = ((slice * 2 + lane / 32) * 4 + unit pair) * 4 + gate  <->  Haiku column gate * H + 8 * slice + 2 * (unit pair) + lane / 32,
-    // "#condb" = the bias in that order.
-    const int E = 2 * D;
-    h->add_lstm_mfma("lstm/linear", PN + H, H, [E](int zr) { return E + zr; });
-    h->add_lstm_mfma("lstm_1/linear", PN + H + H, H, [E](int zr) { return E + zr; });
-    // ... and split into two bf16 terms for nat_dec_lstm_x3_k: [slice][K / 16][hi | lo][lane][8] bf16, element i of lane = the bf16 term of
-    // W[E + 16*step + 8*(lane/32) + i][gate*H + 8*slice + unit], (unit, gate) = ((lane%32)/4, (lane%32)%4)
-    for (int l = 0; l < 2; ++l) {
-        const std::string mod = l ? "lstm_1/linear" : "lstm/linear";
-        const int K = l ? PN + 2 * H : PN + H;
-        h->add_extra(mod + "#x3", (size_t)K * 4 * H * sizeof(float), [mod, K, H, E](const NatModel& m, float* outf) {
-            unsigned short* out = reinterpret_cast<unsigned short*>(outf);
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            const int NST = K / 16;
-            for (int sl = 0; sl < H / 8; ++sl)
-                for (int st = 0; st < NST; ++st)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int mrow = lane & 31, lh = lane >> 5, col = (mrow & 3) * H + 8 * sl + (mrow >> 2);
-                        for (int i = 0; i < 8; ++i) {
-                            const float w = W[(size_t)(E + 16 * st + 8 * lh + i) * 4 * H + col];
-                            const unsigned short hi = nat_bf16_rne(w), lo = nat_bf16_rne(w - nat_bf16_to_float(hi));
-                            const size_t base = ((size_t)sl * NST + st) * 2 * 64;
-                            out[(base + lane) * 8 + i] = hi;
-                            out[(base + 64 + lane) * 8 + i] = lo;
-                        }
-                    }
+    // The decoder's LSTMs.  Haiku's matrices are [cond ; p ; h1] (layer 1) and [cond ; p ; h1 ; h2] (layer 2: hk.deep_rnn_with_skip_connections puts the
+    // network input first); the per-frame step multiplies the state rows [p ; h1] / [p ; h1 ; h2] = Haiku rows E + r ("#mfma", "#x3"), and the cond rows
+    // [0, E) go into the GEMM ahead of the loop: "#cond" / "#cond#x3" = those rows as a one-tap convolution with the output columns in the step kernel's
+    // accumulator order (nat_hcol), "#condb" = the bias in that order, "#zerob" = the zero bias of that GEMM (the mix adds the real one).
+    const char* const lstm[2] = {"lstm/linear", "lstm_1/linear"};
+    const std::vector<int> hcol = nat_hcol(H);
+    for (int x3 = 0; x3 < 2; ++x3)
+        for (int l = 0; l < 2; ++l) h->add_lstm_frag(std::string(lstm[l]) + (x3 ? "#x3" : "#mfma"), lstm[l], x3, PN + H + l * H, H, E);
+    for (const std::string mod : lstm) {
+        h->add_conv_frag(mod + "#cond", mod, false, 1, 0, E, G4, G4, hcol);
+        h->add_extra(mod + "#condb", (size_t)G4 * sizeof(float), [mod, hcol](const NatModel& m, void* out) {
+            const float* bv = m.host(mod, "b");
+            for (size_t cp = 0; cp < hcol.size(); ++cp) static_cast<float*>(out)[cp] = bv[hcol[cp]];
         });
+        h->add_conv_frag(mod + "#cond#x3", mod, true, 1, 0, E, G4, G4, hcol);
+        h->add_zeros(mod + "#zerob", G4);
     }
-    for (const char* l : {"lstm/linear", "lstm_1/linear"}) {
-        const std::string mod = l;
-        const int G4 = 4 * H, MB = G4 / 32, NCS = E / 32;
-        auto hcol = [H](int cp) {  // accumulator-order column -> Haiku column
-            const int gate = cp & 3, rq = (cp >> 2) & 3, lh = (cp >> 4) & 1, slice = cp >> 5;
-            return gate * H + 8 * slice + 2 * rq + lh;
-        };
-        h->add_extra(mod + "#cond", (size_t)MB * NCS * 64 * 16 * sizeof(float), [mod, E, G4, MB, NCS, hcol](const NatModel& m, float* out) {
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            for (int mb = 0; mb < MB; ++mb)
-                for (int cs = 0; cs < NCS; ++cs)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 16; ++e) {
-                            const int c = 32 * cs + 16 * (lane >> 5) + e, cp = 32 * mb + (lane & 31);
-                            out[(((size_t)mb * NCS + cs) * 64 + lane) * 16 + e] = W[(size_t)c * G4 + hcol(cp)];
-                        }
-        });
-        h->add_extra(mod + "#condb", (size_t)G4 * sizeof(float), [mod, G4, hcol](const NatModel& m, float* out) {
-            const std::vector<float>& bv = m.arrs[m.find(mod, "b")].host;
-            for (int cp = 0; cp < G4; ++cp) out[cp] = bv[hcol(cp)];
-        });
-        h->add_extra(mod + "#cond#x3", (size_t)MB * NCS * 4 * 64 * 8 * sizeof(unsigned short), [mod, E, G4, MB, NCS, hcol](const NatModel& m, float* outf) {
-            unsigned short* out = reinterpret_cast<unsigned short*>(outf);  // the same rows for nat_conv_x3_k: [mblk][step][16-channel half][hi | lo][lane][8] bf16
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            for (int mb = 0; mb < MB; ++mb)
-                for (int cs = 0; cs < NCS; ++cs)
-                    for (int ks = 0; ks < 2; ++ks)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                const int c = 32 * cs + 16 * ks + 8 * (lane >> 5) + e, cp = 32 * mb + (lane & 31);
-                                const float w = W[(size_t)c * G4 + hcol(cp)];
-                                const unsigned short hi = nat_bf16_rne(w), lo = nat_bf16_rne(w - nat_bf16_to_float(hi));
-                                const size_t base = (((size_t)mb * NCS + cs) * 4 + ks * 2) * 64;
-                                out[(base + lane) * 8 + e] = hi;
-                                out[(base + 64 + lane) * 8 + e] = lo;
-                            }
-        });
-        h->add_extra(mod + "#zerob", (size_t)G4 * sizeof(float), [G4](const NatModel&, float* out) {  // the token-rows GEMM adds no bias (the mix does)
-            for (int cp = 0; cp < G4; ++cp) out[cp] = 0.0f;
-        });
-    }
-    // The teacher-forced pass (nat_acoustic_run with a NatTeacher): the step multiplies the recurrent rows only — "#tf" = Haiku rows E + PN + r, [h1] for
-    // layer 1 and [h1 ; h2] for layer 2, in the step kernel's order — and everything known ahead of the loop is a one-tap nat_conv_mfma_k GEMM:
-    // "#pre" = the prenet's rows [E, E + PN) of the LSTM matrices with the columns in accumulator order (as "#cond"), "linear_1#mfma" / "linear_2#mfma" the
-    // prenet's own matrices and "linear#mfma" the mel projection, columns as they are.
-    h->add_lstm_mfma("lstm/linear", H, H, [E, PN](int zr) { return E + PN + zr; }, "#tf");
-    h->add_lstm_mfma("lstm_1/linear", 2 * H, H, [E, PN](int zr) { return E + PN + zr; }, "#tf");
-    auto add_gemm = [h](const std::string& key, const std::string& mod, int row0, int cin, int cout, int ncols, std::function<int(int)> col) {
-        const int MB = (cout + 31) / 32, NCS = (cin + 31) / 32;
-        h->add_extra(key, (size_t)MB * NCS * 64 * 16 * sizeof(float), [mod, row0, cin, cout, ncols, col, MB, NCS](const NatModel& m, float* out) {
-            const std::vector<float>& W = m.arrs[m.find(mod, "w")].host;
-            for (int mb = 0; mb < MB; ++mb)
-                for (int cs = 0; cs < NCS; ++cs)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 16; ++e) {
-                            const int c = 32 * cs + 16 * (lane >> 5) + e, co = 32 * mb + (lane & 31);
-                            out[(((size_t)mb * NCS + cs) * 64 + lane) * 16 + e] = (c < cin && co < cout) ? W[(size_t)(row0 + c) * ncols + (col ? col(co) : co)] : 0.0f;
-                        }
-        });
-    };
-    {
-        const int G4 = 4 * H;
-        auto hcol = [H](int cp) { return (cp & 3) * H + 8 * (cp >> 5) + 2 * ((cp >> 2) & 3) + ((cp >> 4) & 1); };  // accumulator-order column -> Haiku column
-        add_gemm("lstm/linear#pre", "lstm/linear", E, PN, G4, G4, hcol);
-        add_gemm("lstm_1/linear#pre", "lstm_1/linear", E, PN, G4, G4, hcol);
-        add_gemm("linear_1#mfma", "linear_1", 0, MEL, PN, PN, nullptr);
-        add_gemm("linear_2#mfma", "linear_2", 0, PN, PN, PN, nullptr);
-        add_gemm("linear#mfma", "linear", 0, 2 * H, MEL, MEL, nullptr);
-        h->add_extra("prenet#zerob", (size_t)PN * sizeof(float), [PN](const NatModel&, float* out) {
-            for (int c = 0; c < PN; ++c) out[c] = 0.0f;
-        });
-    }
+    // The teacher-forced pass (nat_teacher_decoder): the step multiplies the recurrent rows only — "#tf" = Haiku rows E + PN + r, [h1] for layer 1 and
+    // [h1 ; h2] for layer 2 — and everything known ahead of the loop is a one-tap nat_conv_mfma_k GEMM: "#pre" = the prenet's rows [E, E + PN) of the LSTM
+    // matrices with the columns in accumulator order (as "#cond"), "linear_1#mfma" / "linear_2#mfma" the prenet's own matrices and "linear#mfma" the mel
+    // projection, columns as they are.
+    for (int l = 0; l < 2; ++l) h->add_lstm_frag(std::string(lstm[l]) + "#tf", lstm[l], false, H + l * H, H, E + PN);
+    for (const std::string mod : lstm) h->add_conv_frag(mod + "#pre", mod, false, 1, E, PN, G4, G4, hcol);
+    h->add_conv_frag("linear_1#mfma", "linear_1", false, 1, 0, MEL, PN, PN);
+    h->add_conv_frag("linear_2#mfma", "linear_2", false, 1, 0, PN, PN, PN);
+    h->add_conv_frag("linear#mfma", "linear", false, 1, 0, 2 * H, MEL, MEL);
+    h->add_zeros("prenet#zerob", PN);
     h->layout();
     *out = h;
     return VTTS_OK;
@@ -2004,7 +1740,7 @@ VTTS_API int vtts_nat_acoustic_get_option(const vtts_nat_acoustic* h, const char
     if (stage >= 0) {
         if (!h->stage_valid) return failf(VTTS_ERR_STATE, "%s: no forward() with the option stage_times set has run", key);
         float ms = 0.0f;
-        HIP_TRYN(hipEventElapsedTime(&ms, h->ev_stage[stage], h->ev_stage[stage + 1]));  // (hipErrorNotReady before the caller has synchronised)
+        HIP_TRY(hipEventElapsedTime(&ms, h->ev_stage[stage], h->ev_stage[stage + 1]));  // (hipErrorNotReady before the caller has synchronised)
         *value = (int)(ms * 1000.0f + 0.5f);
         return VTTS_OK;
     }
@@ -2014,7 +1750,7 @@ VTTS_API int vtts_nat_acoustic_resident_status(vtts_nat_acoustic* h, int* timed_
     if (!h || !timed_out) return failf(VTTS_ERR_INVALID, "null argument");
     if (!h->res_sync) return failf(VTTS_ERR_STATE, "resident_status(): this handle has not launched the resident decoder");
     unsigned words[2 + 2 * 10] = {};
-    HIP_TRYN(hipMemcpy(words, h->res_sync, VTTS_TIMELINE ? sizeof(words) : 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(words, h->res_sync, VTTS_TIMELINE ? sizeof(words) : 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
     *timed_out = words[1] != 0u;
 #if VTTS_TIMELINE  // kernel-development builds: the phase clocks of workgroup 0 (10 ns ticks, summed over the frames)
     unsigned long long tl[10];
@@ -2051,36 +1787,15 @@ VTTS_API int vtts_nat_acoustic_bind_packed(vtts_nat_acoustic* h, void* dev_blob,
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     return h->bind(dev_blob, blob_bytes);
 }
-// the resident decoder's share of the workspace (whether the option is set or not: a workspace sized once serves both paths): 256 bytes of polled
-// words (arrival counter, abort word; development builds' phase clocks) in front, then the exchange buffer
-constexpr size_t NAT_RES_WS_BYTES = 256 + (size_t)vtts::NAT_RES_XCH_ELEMS * 4 * sizeof(float);
-static_assert(NAT_RES_WS_BYTES % 256 == 0, "workspace blocks are 256-byte aligned");
-static size_t nat_dec_state_floats(const vtts_nat_acoustic_cfg& c, int B) {
-    const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, ZW = 2 * H + c.prenet_dim;  // rows [p | h1 | h2]
-    return (2 * ZW + 2 * H) * Bp;
-}
 VTTS_API int vtts_nat_acoustic_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, size_t* bytes) {
     if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
     if (B <= 0 || Lmax <= 0 || Fmax <= 0) return failf(VTTS_ERR_INVALID, "B, Lmax and Fmax must be positive (got %d, %d, %d)", B, Lmax, Fmax);
-    const size_t D = h->cfg.encoder_dim, PD = h->cfg.postnet_dim, MEL = h->cfg.mel_dim;
-    *bytes = 2 * align_up((size_t)B * Lmax * D * 4, 256) + align_up((size_t)B * Lmax * 2 * D * 4, 256)  // encoder ping-pong + output
-             + 2 * align_up((size_t)B * Lmax * 4 * h->cfg.decoder_dim * 4, 256)                           // EG1, EG2: enc @ W_l[0:E] per token
-             + align_up((size_t)B * Fmax * MEL * 4, 256)                                                   // decoder mel
-             + 2 * align_up((size_t)B * Fmax * PD * 4, 256)                                                // postnet ping-pong
-             + align_up(nat_dec_state_floats(h->cfg, B) * 4, 256)                                          // decoder state Z[2], c1, c2
-             + 2 * align_up((size_t)B * Fmax * 4 * h->cfg.decoder_dim * 4, 256)                           // hoisted gate pre-activations G1, G2
-             + align_up(nat_enc_lstm_floats((int)D, B, Lmax) * 4, 256)                                     // encoder LSTMs' scratch
-             + NAT_RES_WS_BYTES;                                                                           // resident decoder: counters, exchange buffer
+    *bytes = NatAcousticWs(h->cfg, B, Lmax, Fmax, nullptr).bytes;
     return VTTS_OK;
-}
-// what the teacher-forced pass needs beyond forward()'s layout: the prenet's two layers, the hidden sequence, the recurrent state
-static size_t nat_teacher_extra_bytes(const vtts_nat_acoustic_cfg& c, int B, int Fmax) {
-    const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, BF = (size_t)B * Fmax;
-    return 2 * align_up(BF * c.prenet_dim * 4, 256) + align_up(BF * 2 * H * 4, 256) + align_up(7 * H * Bp * 4, 256);
 }
 VTTS_API int vtts_nat_acoustic_forward_teacher_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, size_t* bytes) {
     if (int rc = vtts_nat_acoustic_workspace_bytes(h, B, Lmax, Fmax, bytes)) return rc;
-    *bytes += nat_teacher_extra_bytes(h->cfg, B, Fmax);
+    *bytes = NatTeacherWs(NatAcousticWs(h->cfg, B, Lmax, Fmax, nullptr), h->cfg, B, Fmax).bytes;
     return VTTS_OK;
 }
 VTTS_API int vtts_nat_acoustic_keep_masks(const vtts_nat_acoustic* h, const uint64_t* seeds_dev, int B, int Fmax, uint8_t* keep_dev, void* stream) {
@@ -2144,326 +1859,347 @@ VTTS_API int vtts_nat_acoustic_teacher_masks_haiku(const vtts_nat_acoustic* h, u
     if (e != hipSuccess) return failf(VTTS_ERR_HIP, "teacher-mask launch failed: %s", hipGetErrorString(e));
     return VTTS_OK;
 }
-// forward_teacher()'s extra operands (nullptr for the inference entry points)
-struct NatTeacher {
-    const float* mels;    // [B][Fmax][MEL] target mels (the one-frame shift happens here)
-    const uint8_t* zone;  // [B][Fmax][4][H] or nullptr
-    float* mel_pre;       // optional: the decoder's mel before the postnet residual
+namespace {
+
+// One call of the acoustic model: the entry point's arguments, then what nat_validate() derives from them.
+struct NatCall {
+    vtts_nat_acoustic* h;
+    const int32_t *tokens, *lengths;
+    const float* durations;
+    const int32_t* nframes;
+    int B, Lmax, Fmax;
+    const uint8_t* keep;
+    float* mel;
+    void* workspace;
+    size_t workspace_bytes;
+    hipStream_t s;
+    int ngroups = 0;  // forward_groups(); 0 is the plain call (the postnet on the caller's stream after the last frame)
+    const int32_t *group_row0 = nullptr, *group_frames = nullptr;
+    const float* enc_pre = nullptr;    // the token encoder's output [B][Lmax][2D] computed ahead by vtts_nat_acoustic_encode() (tokens is not read then)
+    // forward_teacher(): [B][Fmax][MEL] target mels (the one-frame shift happens here), zone masks [B][Fmax][4][H] or nullptr, and optionally where the
+    // decoder's mel before the postnet residual goes
+    const float* mels = nullptr;
+    const uint8_t* zone = nullptr;
+    float* mel_pre = nullptr;
+    int H = 0, PN = 0, MEL = 0, PD = 0, E = 0, G4 = 0, Bp = 0, mtiles = 0;  // mtiles: the gate mix's tiles of NAT_MIX_FT frames
+    NatAcousticWs ws;
 };
-// forward() and forward_groups(): ngroups = 0 is the plain call (the postnet on the caller's stream after the last frame)
-// enc_pre: the token encoder's output [B][Lmax][2D] computed ahead by vtts_nat_acoustic_encode() (tokens_dev is not read then), or nullptr
-static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
-                            const int32_t* nframes_dev, int B, int Lmax, int Fmax, const uint8_t* keep_dev, float* mel_dev, void* workspace,
-                            size_t workspace_bytes, void* stream, int ngroups, const int32_t* group_row0, const int32_t* group_frames,
-                            const float* enc_pre = nullptr, const NatTeacher* tf = nullptr) {
-    if (!h || (!tokens_dev && !enc_pre) || !lengths_dev || !durations_dev || !nframes_dev || !mel_dev) return failf(VTTS_ERR_INVALID, "null argument");
+
+int nat_validate(NatCall& c) {
+    vtts_nat_acoustic* h = c.h;
+    if (!h || (!c.tokens && !c.enc_pre) || !c.lengths || !c.durations || !c.nframes || !c.mel) return failf(VTTS_ERR_INVALID, "null argument");
     if (!h->blob) return failf(VTTS_ERR_STATE, "forward() before pack()/bind_packed()");
     size_t need = 0;
-    int rc = tf ? vtts_nat_acoustic_forward_teacher_workspace_bytes(h, B, Lmax, Fmax, &need) : vtts_nat_acoustic_workspace_bytes(h, B, Lmax, Fmax, &need);
+    int rc = c.mels ? vtts_nat_acoustic_forward_teacher_workspace_bytes(h, c.B, c.Lmax, c.Fmax, &need) : vtts_nat_acoustic_workspace_bytes(h, c.B, c.Lmax, c.Fmax, &need);
     if (rc) return rc;
-    if (!workspace || workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-    if (tf && h->x3) return failf(VTTS_ERR_INVALID, "forward_teacher() has fp32 products only: clear the option bf16x3 (there is no split-operand teacher-forced step)");
-    if (Lmax > 2048) return failf(VTTS_ERR_INVALID, "at most 2048 tokens per sentence (upsampling weights live in LDS)");
+    if (!c.workspace || c.workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", c.workspace_bytes, need);
+    if (c.mels && h->x3) return failf(VTTS_ERR_INVALID, "forward_teacher() has fp32 products only: clear the option bf16x3 (there is no split-operand teacher-forced step)");
+    if (c.Lmax > 2048) return failf(VTTS_ERR_INVALID, "at most 2048 tokens per sentence (upsampling weights live in LDS)");
     h->groups_valid = 0;
-    if (ngroups > 0) {
-        if (!group_row0 || !group_frames) return failf(VTTS_ERR_INVALID, "null argument");
-        if (ngroups > 64) return failf(VTTS_ERR_INVALID, "at most 64 groups (got %d)", ngroups);
-        if (group_row0[0] != 0 || group_row0[ngroups] != B) return failf(VTTS_ERR_INVALID, "the groups must cover rows [0, %d)", B);
-        for (int g = 0; g < ngroups; ++g)
-            if (group_row0[g + 1] <= group_row0[g] || group_frames[g] < 1 || group_frames[g] > Fmax)
+    if (c.ngroups > 0) {
+        if (!c.group_row0 || !c.group_frames) return failf(VTTS_ERR_INVALID, "null argument");
+        if (c.ngroups > 64) return failf(VTTS_ERR_INVALID, "at most 64 groups (got %d)", c.ngroups);
+        if (c.group_row0[0] != 0 || c.group_row0[c.ngroups] != c.B) return failf(VTTS_ERR_INVALID, "the groups must cover rows [0, %d)", c.B);
+        for (int g = 0; g < c.ngroups; ++g)
+            if (c.group_row0[g + 1] <= c.group_row0[g] || c.group_frames[g] < 1 || c.group_frames[g] > c.Fmax)
                 return failf(VTTS_ERR_INVALID, "group %d: rows [%d, %d), %d frames (every group needs at least one row and 1 <= frames <= Fmax = %d)", g,
-                             group_row0[g], group_row0[g + 1], group_frames[g], Fmax);
+                             c.group_row0[g], c.group_row0[g + 1], c.group_frames[g], c.Fmax);
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int D = h->cfg.encoder_dim, V = h->cfg.vocab_size, H = h->cfg.decoder_dim, PN = h->cfg.prenet_dim, MEL = h->cfg.mel_dim, PD = h->cfg.postnet_dim;
-    const int E = 2 * D, G4 = 4 * H;
-    // the side stream and the events of the hand-over (created once per handle, on the device the caller made current)
+    c.H = h->cfg.decoder_dim, c.PN = h->cfg.prenet_dim, c.MEL = h->cfg.mel_dim, c.PD = h->cfg.postnet_dim;
+    c.E = 2 * h->cfg.encoder_dim, c.G4 = 4 * c.H, c.Bp = (c.B + 63) / 64 * 64, c.mtiles = (c.Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT;
+    c.ws = NatAcousticWs(h->cfg, c.B, c.Lmax, c.Fmax, c.workspace);
+    return VTTS_OK;
+}
+
+// the side stream and the events of the hand-over (created once per handle, on the device the caller made current)
+int nat_side_stream(vtts_nat_acoustic* h, int ngroups) {
     if (!h->side) {
-        HIP_TRYN(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-        HIP_TRYN(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIP_TRYN(hipEventCreateWithFlags(&h->ev_gates, hipEventDisableTiming));
+        HIP_TRY(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_gates, hipEventDisableTiming));
     }
     while ((int)h->ev_dec.size() < ngroups) {
         hipEvent_t a, b;
-        HIP_TRYN(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-        HIP_TRYN(hipEventCreateWithFlags(&b, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&b, hipEventDisableTiming));
         h->ev_dec.push_back(a);
         h->ev_done.push_back(b);
     }
-    char* p = static_cast<char*>(workspace);
-    auto take = [&](size_t bytes) {
-        float* r = reinterpret_cast<float*>(p);
-        p += align_up(bytes, 256);
-        return r;
-    };
-    float* bufA = take((size_t)B * Lmax * D * 4);
-    float* bufB = take((size_t)B * Lmax * D * 4);
-    float* enc = take((size_t)B * Lmax * E * 4);
-    float* EG1 = take((size_t)B * Lmax * G4 * 4);
-    float* EG2 = take((size_t)B * Lmax * G4 * 4);
-    float* mel0 = take((size_t)B * Fmax * MEL * 4);
-    float* pA = take((size_t)B * Fmax * PD * 4);
-    float* pB = take((size_t)B * Fmax * PD * 4);
-    float* dstate = take(nat_dec_state_floats(h->cfg, B) * 4);
-    float* G1 = take((size_t)B * Fmax * G4 * 4);
-    float* G2 = take((size_t)B * Fmax * G4 * 4);
-    float* lstm_ws = take(nat_enc_lstm_floats(D, B, Lmax) * 4);
-    unsigned* res_sync = reinterpret_cast<unsigned*>(take(NAT_RES_WS_BYTES));
-    float* res_xch = reinterpret_cast<float*>(res_sync + 64);
-    h->resident_used = 0;
-    if (enc_pre) {
-        enc = const_cast<float*>(enc_pre);  // read only from here on
-    } else {
-        rc = run_token_encoder(*h, "token_encoder/~/", V, D, tokens_dev, lengths_dev, B, Lmax, bufA, bufB, lstm_ws, enc, s);  // model.py:131
-        if (rc) return rc;
-    }
-    // :132 (upsample) lives inside the gates below: cond is never materialised (nat_gates_mix_k)
-    HIP_TRYN(hipMemsetAsync(mel_dev, 0, (size_t)B * Fmax * MEL * 4, s));  // rows past a sentence's last frame
-    // postnet (:113-121) + residual (:151) of rows [r0, r1) over their first `frames` frames: 4 x (Conv1D(PD, 5) + BatchNorm + tanh),
-    // Conv1D(MEL, 5), mel + .   A row's result does not depend on the launch it is part of.
-    auto postnet = [&](int r0, int r1, int frames, hipStream_t ps) {
-        const float* cur = mel0 + (size_t)r0 * Fmax * MEL;
-        float* bufs[2] = {pA + (size_t)r0 * Fmax * PD, pB + (size_t)r0 * Fmax * PD};
-        for (int i = 0; i < 5; ++i) {
-            const std::string sfx = i ? "_" + std::to_string(i) : "";
-            const std::string cv = "conv1_d" + sfx, bn = "batch_norm" + sfx;
-            const int cin = i == 0 ? MEL : PD, cout = i == 4 ? MEL : PD, MB = (cout + 31) / 32;
-            float* dst = i == 4 ? mel_dev + (size_t)r0 * Fmax * MEL : bufs[i & 1];
-            const float4* wpk = reinterpret_cast<const float4*>(h->extra(cv + "#mfma"));
-            const float *iv = i < 4 ? h->inv(bn) : nullptr, *mv = i < 4 ? h->dev(bn + "/~/mean_ema", "average") : nullptr, *ov = i < 4 ? h->dev(bn, "offset") : nullptr;
-            const int act = i < 4 ? (int)NAT_ACT_TANH : (int)NAT_ACT_NONE;
-            const float* res = i == 4 ? mel0 + (size_t)r0 * Fmax * MEL : nullptr;
-            const uint4* wx3 = reinterpret_cast<const uint4*>(h->extra(cv + "#x3"));
-            if (h->x3 && MB >= 8)
-                hipLaunchKernelGGL((nat_conv_x3_k<5, 2>), dim3((frames + 63) / 64, (MB + 7) / 8, r1 - r0), dim3(256), 0, ps, cur, nframes_dev + r0, wx3,
-                                   h->dev(cv, "b"), iv, mv, ov, res, dst, Fmax, cin, cout, act, 0);
-            else if (h->x3)
-                hipLaunchKernelGGL((nat_conv_x3_k<5, 1>), dim3((frames + 63) / 64, (MB + 3) / 4, r1 - r0), dim3(256), 0, ps, cur, nframes_dev + r0, wx3,
-                                   h->dev(cv, "b"), iv, mv, ov, res, dst, Fmax, cin, cout, act, 0);
-            else if (MB >= 8)
-                hipLaunchKernelGGL((nat_conv_mfma_k<5, 2>), dim3((frames + 63) / 64, (MB + 7) / 8, r1 - r0), dim3(256), 0, ps, cur, nframes_dev + r0, wpk,
-                                   h->dev(cv, "b"), iv, mv, ov, res, dst, Fmax, cin, cout, act, 0);
-            else
-                hipLaunchKernelGGL((nat_conv_mfma_k<5, 1>), dim3((frames + 63) / 64, (MB + 3) / 4, r1 - r0), dim3(256), 0, ps, cur, nframes_dev + r0, wpk,
-                                   h->dev(cv, "b"), iv, mv, ov, res, dst, Fmax, cin, cout, act, 0);
-            cur = dst;
+    return VTTS_OK;
+}
+
+// One launch of nat_conv_mfma_k, or with x3 of nat_conv_x3_k (w = the "#x3" fragments then), over `nrows` sentences and the first `npos` of their
+// `pitch` positions: y[b][t] = epilogue(act(conv(x[b])[t] + bias)) for t < rows[b], epilogue TF as described at the kernel.  A workgroup takes 64 positions
+// x 4 waves x MR blocks of 32 output channels, MR = 2 from 8 blocks on.  One tap makes it a GEMM over a sentence's positions.
+// The split-operand kernel has no TF epilogue, and of its one-tap form only MR = 2 is built: its one user, the gate GEMM, has 4H / 32 >= 32 blocks.
+struct NatConv {
+    int nrows, npos, pitch;
+    const int32_t* rows;
+    const float* x;
+    float* y;
+    const float *w, *bias;
+    int cin, cout, act;
+    const uint8_t* keep = nullptr;
+    const float *inv = nullptr, *mean = nullptr, *offset = nullptr, *res = nullptr;
+};
+template <int K, int TF = 0>
+void nat_conv(const NatConv& o, bool x3, hipStream_t s) {
+    const int MB = (o.cout + 31) / 32;
+    auto launch = [&](auto mr) {
+        constexpr int MR = decltype(mr)::value;
+        const dim3 grid((o.npos + 63) / 64, (MB + 4 * MR - 1) / (4 * MR), o.nrows);
+        if constexpr (TF == 0 && (K == 5 || MR == 2)) {
+            if (x3) {
+                hipLaunchKernelGGL((nat_conv_x3_k<K, MR>), grid, dim3(256), 0, s, o.x, o.rows, reinterpret_cast<const uint4*>(o.w), o.bias, o.inv, o.mean, o.offset,
+                                   o.res, o.y, o.pitch, o.cin, o.cout, o.act, 0);
+                return;
+            }
         }
+        hipLaunchKernelGGL((nat_conv_mfma_k<K, MR, TF>), grid, dim3(256), 0, s, o.x, o.rows, reinterpret_cast<const float4*>(o.w), o.bias, o.inv, o.mean, o.offset,
+                           o.res, o.y, o.pitch, o.cin, o.cout, o.act, 0, o.keep);
     };
-    if (tf) {  // teacher-forced decoder (model.py:146-167): everything but the two LSTMs' recurrent products ahead of the frame loop
-        const int Bp = (B + 63) / 64 * 64;
-        const size_t BF = (size_t)B * Fmax, HB = (size_t)H * Bp;
-        float* P1 = take(BF * PN * 4);
-        float* P2 = take(BF * PN * 4);
-        float* hseq = take(BF * 2 * H * 4);
-        float* tstate = take(7 * HB * 4);
-        float* hz1[2] = {tstate, tstate + HB};  // zoned h1, ping-pong by frame parity
-        float* hz2[2] = {tstate + 2 * HB, tstate + 3 * HB};
-        float* hf1 = tstate + 4 * HB;           // layer 1's un-zoned output of the frame in flight
-        float* c1 = tstate + 5 * HB;
-        float* c2 = tstate + 6 * HB;
-        if (G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: the gate mix wants 4 * decoder_dim in multiples of 1024", H);
-        HIP_TRYN(hipMemsetAsync(tstate, 0, 7 * HB * 4, s));
-        HIP_TRYN(hipMemsetAsync(mel0, 0, BF * MEL * 4, s));
-        // one-tap nat_conv_mfma_k = a GEMM over a sentence's frames: y[b][f] = epilogue(act(x[b][f] @ W + bias)), epilogue TF as described at the kernel;
-        // rows past nframes are not computed
-        auto gemm = [&](auto tfc, const float* x, const int32_t* rows, int L, const std::string& key, const float* bias, float* y, int cin, int cout, int act,
-                        const uint8_t* kp = nullptr) {
-            constexpr int TF = decltype(tfc)::value;
-            const int MB = (cout + 31) / 32;
-            const float4* w = reinterpret_cast<const float4*>(h->extra(key));
-            if (MB >= 8)
-                hipLaunchKernelGGL((nat_conv_mfma_k<1, 2, TF>), dim3((L + 63) / 64, (MB + 7) / 8, B), dim3(256), 0, s, x, rows, w, bias, nullptr, nullptr, nullptr, nullptr, y,
-                                   L, cin, cout, act, 0, kp);
-            else
-                hipLaunchKernelGGL((nat_conv_mfma_k<1, 1, TF>), dim3((L + 63) / 64, (MB + 3) / 4, B), dim3(256), 0, s, x, rows, w, bias, nullptr, nullptr, nullptr, nullptr, y,
-                                   L, cin, cout, act, 0, kp);
-        };
-        using TfNone = std::integral_constant<int, 0>;
-        using TfShift = std::integral_constant<int, NAT_TF_SHIFT>;
-        using TfShiftKeep = std::integral_constant<int, NAT_TF_SHIFT | NAT_TF_KEEP>;
-        using TfKeep = std::integral_constant<int, NAT_TF_KEEP>;
-        using TfAcc = std::integral_constant<int, NAT_TF_ACC>;
-        // G_l = b_l + cond @ W_l[0:E] for every frame: forward()'s token-rows GEMM and mix
-        gemm(TfNone{}, enc, lengths_dev, Lmax, "lstm/linear#cond", h->extra("lstm/linear#zerob"), EG1, E, G4, (int)NAT_ACT_NONE);
-        gemm(TfNone{}, enc, lengths_dev, Lmax, "lstm_1/linear#cond", h->extra("lstm_1/linear#zerob"), EG2, E, G4, (int)NAT_ACT_NONE);
-        const size_t mlds = ((size_t)(Lmax + 3) / 4 * 4 + (size_t)Lmax * NAT_MIX_FT) * sizeof(float);
-        if (mlds > 48 * 1024)
-            HIP_TRYN(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_gates_mix_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(nat_gates_mix_k, dim3((Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT, 2 * (G4 / 1024), B), dim3(256), mlds, s, EG1, EG2, h->extra("lstm/linear#condb"),
-                           h->extra("lstm_1/linear#condb"), lengths_dev, durations_dev, nframes_dev, G1, G2, Lmax, Fmax, G4, 0);
-        // prenet(inp_mels) over all frames (:149, :95-100), the one-frame shift of the target mels (gta.py:34-36) in the first GEMM's staging, relu and the
-        // dropout's keep x 2 in both epilogues
-        const float* zb = h->extra("prenet#zerob");
-        if (keep_dev) {
-            gemm(TfShiftKeep{}, tf->mels, nframes_dev, Fmax, "linear_1#mfma", zb, P1, MEL, PN, (int)NAT_ACT_RELU, keep_dev);
-            gemm(TfKeep{}, P1, nframes_dev, Fmax, "linear_2#mfma", zb, P2, PN, PN, (int)NAT_ACT_RELU, keep_dev + PN);
+    if (MB >= 8) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 1>{});
+}
+
+// The conditioning's share of both layers' gates for every frame, G_l = b_l + cond @ W_l[0:E]: the GEMM over the tokens' rows, then the mix over the
+// frames (:132, the upsampling, lives inside it: cond is never materialised).  The first `mfirst` of its tiles run on the
+// caller's stream, the rest beside it on the side stream, ev_gates behind them.
+int nat_cond_gates(const NatCall& c, int mfirst) {
+    vtts_nat_acoustic* h = c.h;
+    if (c.G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: the gate mix wants 4 * decoder_dim in multiples of 1024", c.H);
+    for (int l = 0; l < 2; ++l) {
+        const std::string mod = l ? "lstm_1/linear" : "lstm/linear";
+        nat_conv<1>(NatConv{c.B, c.Lmax, c.Lmax, c.lengths, c.ws.enc, l ? c.ws.EG2 : c.ws.EG1, h->extra(mod + (h->x3 ? "#cond#x3" : "#cond")), h->extra(mod + "#zerob"),
+                            c.E, c.G4, (int)NAT_ACT_NONE}, h->x3, c.s);
+    }
+    const size_t mlds = ((size_t)(c.Lmax + 3) / 4 * 4 + (size_t)c.Lmax * NAT_MIX_FT) * sizeof(float);
+    if (mlds > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_gates_mix_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
+    const float *b1 = h->extra("lstm/linear#condb"), *b2 = h->extra("lstm_1/linear#condb");
+    auto mix = [&](int tile0, int ntiles, hipStream_t gs) {
+        hipLaunchKernelGGL(nat_gates_mix_k, dim3(ntiles, 2 * (c.G4 / 1024), c.B), dim3(256), mlds, gs, c.ws.EG1, c.ws.EG2, b1, b2, c.lengths, c.durations,
+                           c.nframes, c.ws.G1, c.ws.G2, c.Lmax, c.Fmax, c.G4, tile0);
+    };
+    mix(0, mfirst, c.s);
+    if (c.mtiles > mfirst) {
+        HIP_TRY(hipEventRecord(h->ev_fork, c.s));
+        HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+        mix(mfirst, c.mtiles - mfirst, h->side);
+        HIP_TRY(hipEventRecord(h->ev_gates, h->side));
+    }
+    return VTTS_OK;
+}
+
+// postnet (:113-121) + residual (:151) of rows [r0, r1) over their first `frames` frames: 4 x (Conv1D(PD, 5) + BatchNorm + tanh),
+// Conv1D(MEL, 5), mel + .   A row's result does not depend on the launch it is part of.
+void nat_postnet(const NatCall& c, int r0, int r1, int frames, hipStream_t ps) {
+    const vtts_nat_acoustic* h = c.h;
+    const size_t m0 = (size_t)r0 * c.Fmax * c.MEL, p0 = (size_t)r0 * c.Fmax * c.PD;
+    const float* cur = c.ws.mel0 + m0;
+    float* bufs[2] = {c.ws.pA + p0, c.ws.pB + p0};
+    for (int i = 0; i < 5; ++i) {
+        const std::string sfx = i ? "_" + std::to_string(i) : "";
+        const std::string cv = "conv1_d" + sfx, bn = "batch_norm" + sfx;
+        const bool last = i == 4;
+        NatConv o{r1 - r0, frames, c.Fmax, c.nframes + r0, cur, last ? c.mel + m0 : bufs[i & 1], h->extra(cv + (h->x3 ? "#x3" : "#mfma")), h->dev(cv, "b"),
+                  i == 0 ? c.MEL : c.PD, last ? c.MEL : c.PD, last ? (int)NAT_ACT_NONE : (int)NAT_ACT_TANH};
+        if (last) o.res = c.ws.mel0 + m0;
+        else o.inv = h->inv(bn), o.mean = h->dev(bn + "/~/mean_ema", "average"), o.offset = h->dev(bn, "offset");
+        nat_conv<5>(o, h->x3, ps);
+        cur = o.y;
+    }
+}
+
+// teacher-forced decoder (model.py:146-167): everything but the two LSTMs' recurrent products ahead of the frame loop
+int nat_teacher_decoder(const NatCall& c) {
+    const vtts_nat_acoustic* h = c.h;
+    const NatAcousticWs& ws = c.ws;
+    const NatTeacherWs tw(ws, h->cfg, c.B, c.Fmax);
+    const int B = c.B, Bp = c.Bp, Fmax = c.Fmax, H = c.H, PN = c.PN, MEL = c.MEL, G4 = c.G4;
+    hipStream_t s = c.s;
+    const size_t BF = (size_t)B * Fmax, HB = (size_t)H * Bp;
+    float* hz1[2] = {tw.tstate, tw.tstate + HB};  // zoned h1, ping-pong by frame parity
+    float* hz2[2] = {tw.tstate + 2 * HB, tw.tstate + 3 * HB};
+    float* hf1 = tw.tstate + 4 * HB;              // layer 1's un-zoned output of the frame in flight
+    float* c1 = tw.tstate + 5 * HB;
+    float* c2 = tw.tstate + 6 * HB;
+    HIP_TRY(hipMemsetAsync(tw.tstate, 0, 7 * HB * 4, s));
+    HIP_TRY(hipMemsetAsync(ws.mel0, 0, BF * MEL * 4, s));
+    if (int rc = nat_cond_gates(c, c.mtiles)) return rc;
+    // a GEMM over every sentence's frames (nat_conv's one-tap form); rows past nframes are not computed
+    auto gemm = [&](const float* x, const char* key, const float* bias, float* y, int cin, int cout, int act, const uint8_t* kp = nullptr) {
+        return NatConv{B, Fmax, Fmax, c.nframes, x, y, h->extra(key), bias, cin, cout, act, kp};
+    };
+    // prenet(inp_mels) over all frames (:149, :95-100), the one-frame shift of the target mels (gta.py:34-36) in the first GEMM's staging, relu and the
+    // dropout's keep x 2 in both epilogues
+    const float* zb = h->extra("prenet#zerob");
+    if (c.keep) {
+        nat_conv<1, NAT_TF_SHIFT | NAT_TF_KEEP>(gemm(c.mels, "linear_1#mfma", zb, tw.P1, MEL, PN, (int)NAT_ACT_RELU, c.keep), false, s);
+        nat_conv<1, NAT_TF_KEEP>(gemm(tw.P1, "linear_2#mfma", zb, tw.P2, PN, PN, (int)NAT_ACT_RELU, c.keep + PN), false, s);
+    } else {
+        nat_conv<1, NAT_TF_SHIFT>(gemm(c.mels, "linear_1#mfma", zb, tw.P1, MEL, PN, (int)NAT_ACT_RELU), false, s);
+        nat_conv<1>(gemm(tw.P1, "linear_2#mfma", zb, tw.P2, PN, PN, (int)NAT_ACT_RELU), false, s);
+    }
+    // G_l += p @ W_l[E : E + PN], onto the mix's output
+    nat_conv<1, NAT_TF_ACC>(gemm(tw.P2, "lstm/linear#pre", h->extra("lstm/linear#zerob"), ws.G1, PN, G4, (int)NAT_ACT_NONE), false, s);
+    nat_conv<1, NAT_TF_ACC>(gemm(tw.P2, "lstm_1/linear#pre", h->extra("lstm_1/linear#zerob"), ws.G2, PN, G4, (int)NAT_ACT_NONE), false, s);
+    const float4 *w1 = h->extra<float4>("lstm/linear#tf"), *w2 = h->extra<float4>("lstm_1/linear#tf");
+    const bool wide = B > 32;
+    const dim3 lgrid(H / 8, wide ? Bp / 64 : 1);
+    auto step = [&](const NatTfOps& o, int KA, int f) {
+        if (wide) hipLaunchKernelGGL((nat_tf_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, H, c.nframes, f, B, Bp, H, Fmax);
+        else hipLaunchKernelGGL((nat_tf_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, H, c.nframes, f, B, Bp, H, Fmax);
+    };
+    const size_t gp = (size_t)Fmax * G4;
+    for (int f = 0; f < Fmax; ++f) {
+        const int cur = f & 1, prv = cur ^ 1;
+        step(NatTfOps{hz1[prv], hz1[prv], w1, c1, hz1[cur], hf1, tw.hseq, ws.G1 + (size_t)f * G4, gp, c.zone}, 0, f);
+        step(NatTfOps{hf1, hz2[prv], w2, c2, hz2[cur], nullptr, tw.hseq + H, ws.G2 + (size_t)f * G4, gp, c.zone ? c.zone + 2 * (size_t)H : nullptr}, H, f);
+    }
+    nat_conv<1>(gemm(tw.hseq, "linear#mfma", h->dev("linear", "b"), ws.mel0, 2 * H, MEL, (int)NAT_ACT_NONE), false, s);  // :167
+    if (c.mel_pre) HIP_TRY(hipMemcpyAsync(c.mel_pre, ws.mel0, BF * MEL * 4, hipMemcpyDeviceToDevice, s));
+    return VTTS_OK;
+}
+
+// option "resident": 1 <= B <= 4, fp32 products, the reference's decoder dimensions, no hand-over, a stream that is not being captured
+// and a grid the device can hold; in every other case *grid = 0 and the call takes the per-frame launches
+int nat_resident_grid(const NatCall& c, int* grid) {
+    vtts_nat_acoustic* h = c.h;
+    *grid = 0;
+    if (!h->resident || c.ngroups != 0 || c.B > 4 || h->x3 || c.H != NAT_RES_H || c.PN != NAT_RES_PN || c.MEL > NAT_RES_MELMAX) return VTTS_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(c.s, &cap));
+    if (!h->cu_count) {
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    // at most one workgroup per CU: the default grid where the device has that many CUs, else the next smaller one
+    int g = h->resident_grid ? h->resident_grid : NAT_RES_DEFAULT_GRID;
+    while (g > h->cu_count && g > 64) g /= 2;
+    if (cap == hipStreamCaptureStatusNone && g <= h->cu_count) *grid = g;
+    return VTTS_OK;
+}
+// the frame loop as one resident kernel; h->resident_used stays 0 where the runtime cannot hold the grid resident
+int nat_resident_launch(const NatCall& c, int grid) {
+    vtts_nat_acoustic* h = c.h;
+    const NatAcousticWs& ws = c.ws;
+    HIP_TRY(hipMemsetAsync(ws.res_sync, 0, 256, c.s));
+    const size_t e4 = (size_t)c.E * c.G4;  // Haiku rows [E, ...): the state's rows
+    const NatResidentArgs ra{h->dev("lstm/linear", "w") + e4, h->dev("lstm_1/linear", "w") + e4, h->dev("linear", "w"), h->dev("linear", "b"),
+                             h->dev("linear_1", "w"), h->dev("linear_2", "w"), ws.G1, ws.G2, c.nframes, c.keep, ws.mel0, reinterpret_cast<float*>(ws.res_sync + 64), ws.res_sync,
+                             reinterpret_cast<unsigned long long*>(ws.res_sync + 2), c.Fmax, c.MEL};
+    const hipError_t le = launch_nat_dec_resident(ra, c.B, grid, c.s);
+    if (le == hipSuccess) {
+        h->resident_used = 1;
+        h->res_sync = ws.res_sync;
+    } else if (le == hipErrorCooperativeLaunchTooLarge) {
+        (void)hipGetLastError();  // the per-frame launches take over
+    } else {
+        return failf(VTTS_ERR_HIP, "resident decoder launch failed: %s", hipGetErrorString(le));
+    }
+    return VTTS_OK;
+}
+
+// autoregressive decoder (:134-150): per frame LSTM1, LSTM2, projection + next frame's prenet, all sentences at once
+int nat_ar_decoder(const NatCall& c) {
+    vtts_nat_acoustic* h = c.h;
+    const NatAcousticWs& ws = c.ws;
+    const int B = c.B, Bp = c.Bp, Fmax = c.Fmax, H = c.H, PN = c.PN, MEL = c.MEL, G4 = c.G4, ZW = PN + 2 * H;
+    hipStream_t s = c.s;
+    float* Z[2] = {ws.dstate, ws.dstate + (size_t)ZW * Bp};
+    float* c1 = ws.dstate + 2 * (size_t)ZW * Bp;
+    float* c2 = c1 + (size_t)H * Bp;
+    HIP_TRY(hipMemsetAsync(ws.dstate, 0, nat_dec_state_floats(h->cfg, B) * 4, s));  // frame 0: h1 = h2 = 0, c = 0, prenet(0) = 0 (no biases)
+    HIP_TRY(hipMemsetAsync(ws.mel0, 0, (size_t)B * Fmax * MEL * 4, s));  // rows past a sentence's last frame stay zero
+    const bool stamps = h->stage_times && c.ngroups == 0;
+    h->stage_valid = 0;
+    if (stamps) {
+        for (hipEvent_t& e : h->ev_stage)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(h->ev_stage[0], s));
+    }
+    // the gates' mix for frames [0, 64) here and for the rest beside the first 64 steps; all of it here when the resident kernel will run
+    int res_grid = 0;
+    if (int rc = nat_resident_grid(c, &res_grid)) return rc;
+    const int mfirst = res_grid ? c.mtiles : std::min(64 / NAT_MIX_FT, c.mtiles);
+    if (int rc = nat_cond_gates(c, mfirst)) return rc;
+    const float4 *w1 = h->extra<float4>("lstm/linear#mfma"), *w2 = h->extra<float4>("lstm_1/linear#mfma");
+    const float4 *f1 = h->extra<float4>("linear_1#k4"), *f2 = h->extra<float4>("linear_2#k4"), *wp = h->extra<float4>("linear#k4");
+    const float* bp = h->dev("linear", "b");
+    const bool wide = B > 32;  // two 32-sentence tiles per wave once there are that many sentences
+    const dim3 lgrid(H / 8, wide ? Bp / 64 : 1);
+    auto lstm = [&](const float* inA, int KA, const float* inB, const float4* w, const float* gin, float* cst, float* hout, int f) {
+        const NatLstmOps o{inA, inB, w, nullptr, cst, hout, gin + (size_t)f * G4, (size_t)Fmax * G4};
+        if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, f, B, Bp, H);
+        else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, f, B, Bp, H);
+    };
+    const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);
+    auto group_handover = [&](int frames_done) -> int {  // a group whose last frame was frames_done - 1: its postnet starts now, on the side stream
+        for (int g = 0; g < c.ngroups; ++g) {
+            if (c.group_frames[g] != frames_done) continue;
+            HIP_TRY(hipEventRecord(h->ev_dec[g], s));
+            HIP_TRY(hipStreamWaitEvent(h->side, h->ev_dec[g], 0));
+            nat_postnet(c, c.group_row0[g], c.group_row0[g + 1], c.group_frames[g], h->side);
+            HIP_TRY(hipEventRecord(h->ev_done[g], h->side));
+        }
+        return VTTS_OK;
+    };
+    // option "bf16x3": the split-state step (nat_dec_lstm_x3_k) where its 16-row steps divide the row blocks; the state's two parities hold
+    // two bf16 planes each (the same bytes as the fp32 rows)
+    const bool dx3 = h->x3 && PN % 16 == 0 && H % 16 == 0 && ((PN + H) / 16) % 8 == 0 && ((PN + 2 * H) / 16) % 8 == 0;
+    const size_t zplane = (size_t)ZW * Bp;  // bf16 elements per plane
+    const uint4 *w1x = h->extra<uint4>("lstm/linear#x3"), *w2x = h->extra<uint4>("lstm_1/linear#x3");
+    auto lstm_x3 = [&](unsigned short* zcx, const unsigned short* zpx, int KA, int K, const uint4* w, const float* gin, float* cst, int out_row0, int f) {
+        const NatLstmX3Ops o{zcx, zpx, zplane, w, gin + (size_t)f * G4, (size_t)Fmax * G4, cst, zcx, out_row0};
+        if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, f, B, Bp, H);
+        else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, f, B, Bp, H);
+    };
+    if (stamps) HIP_TRY(hipEventRecord(h->ev_stage[1], s));
+    if (res_grid)  // every frame's gates are on `s` already (mfirst = mtiles)
+        if (int rc = nat_resident_launch(c, res_grid)) return rc;
+    for (int f = 0; f < Fmax && !h->resident_used; ++f) {
+        if (f == 64 && c.mtiles > mfirst) HIP_TRY(hipStreamWaitEvent(s, h->ev_gates, 0));
+        float* zc = Z[f & 1];
+        float* zp = Z[(f + 1) & 1];
+        if (dx3) {
+            unsigned short* zcx = reinterpret_cast<unsigned short*>(zc);
+            const unsigned short* zpx = reinterpret_cast<const unsigned short*>(zp);
+            lstm_x3(zcx, zpx, PN, PN + H, w1x, ws.G1, c1, PN, f);
+            lstm_x3(zcx, zpx, PN + H, PN + 2 * H, w2x, ws.G2, c2, PN + H, f);
+            hipLaunchKernelGGL(nat_dec_proj_prenet_k<true>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, c.nframes, f1, f2, wp, bp, c.keep, ws.mel0, f, B, Bp,
+                               Fmax, PN, H, MEL, zplane);
         } else {
-            gemm(TfShift{}, tf->mels, nframes_dev, Fmax, "linear_1#mfma", zb, P1, MEL, PN, (int)NAT_ACT_RELU);
-            gemm(TfNone{}, P1, nframes_dev, Fmax, "linear_2#mfma", zb, P2, PN, PN, (int)NAT_ACT_RELU);
+            lstm(zc, PN, zp + (size_t)PN * Bp, w1, ws.G1, c1, zc + (size_t)PN * Bp, f);
+            lstm(zc, PN + H, zp + (size_t)(PN + H) * Bp, w2, ws.G2, c2, zc + (size_t)(PN + H) * Bp, f);
+            hipLaunchKernelGGL(nat_dec_proj_prenet_k<false>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, c.nframes, f1, f2, wp, bp, c.keep, ws.mel0, f, B, Bp,
+                               Fmax, PN, H, MEL, (size_t)0);
         }
-        // G_l += p @ W_l[E : E + PN], onto the mix's output
-        gemm(TfAcc{}, P2, nframes_dev, Fmax, "lstm/linear#pre", h->extra("lstm/linear#zerob"), G1, PN, G4, (int)NAT_ACT_NONE);
-        gemm(TfAcc{}, P2, nframes_dev, Fmax, "lstm_1/linear#pre", h->extra("lstm_1/linear#zerob"), G2, PN, G4, (int)NAT_ACT_NONE);
-        const float4* w1 = reinterpret_cast<const float4*>(h->extra("lstm/linear#tf"));
-        const float4* w2 = reinterpret_cast<const float4*>(h->extra("lstm_1/linear#tf"));
-        const bool wide = B > 32;
-        const dim3 lgrid(H / 8, wide ? Bp / 64 : 1);
-        auto step = [&](const NatTfOps& o, int KA, int f) {
-            if (wide) hipLaunchKernelGGL((nat_tf_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, H, nframes_dev, f, B, Bp, H, Fmax);
-            else hipLaunchKernelGGL((nat_tf_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, H, nframes_dev, f, B, Bp, H, Fmax);
-        };
-        const size_t gp = (size_t)Fmax * G4;
-        for (int f = 0; f < Fmax; ++f) {
-            const int cur = f & 1, prv = cur ^ 1;
-            step(NatTfOps{hz1[prv], hz1[prv], w1, c1, hz1[cur], hf1, hseq, G1 + (size_t)f * G4, gp, tf->zone}, 0, f);
-            step(NatTfOps{hf1, hz2[prv], w2, c2, hz2[cur], nullptr, hseq + H, G2 + (size_t)f * G4, gp, tf->zone ? tf->zone + 2 * (size_t)H : nullptr}, H, f);
-        }
-        gemm(TfNone{}, hseq, nframes_dev, Fmax, "linear#mfma", h->dev("linear", "b"), mel0, 2 * H, MEL, (int)NAT_ACT_NONE);  // :167
-        if (tf->mel_pre) HIP_TRYN(hipMemcpyAsync(tf->mel_pre, mel0, BF * MEL * 4, hipMemcpyDeviceToDevice, s));
-    } else {  // autoregressive decoder (:134-150): per frame LSTM1, LSTM2, projection + next frame's prenet, all sentences at once
-        const int Bp = (B + 63) / 64 * 64, ZW = PN + 2 * H;
-        float* Z[2] = {dstate, dstate + (size_t)ZW * Bp};
-        float* c1 = dstate + 2 * (size_t)ZW * Bp;
-        float* c2 = c1 + (size_t)H * Bp;
-        HIP_TRYN(hipMemsetAsync(dstate, 0, nat_dec_state_floats(h->cfg, B) * 4, s));  // frame 0: h1 = h2 = 0, c = 0, prenet(0) = 0 (no biases)
-        HIP_TRYN(hipMemsetAsync(mel0, 0, (size_t)B * Fmax * MEL * 4, s));  // rows past a sentence's last frame stay zero
-        // the conditioning's share of both layers' gates for every frame (nat_gates_mix_k): the GEMM over the tokens' rows, then the mix for
-        // frames [0, 64) here and for the rest beside the first 64 steps
-        const int MBG = G4 / 32;
-        if (G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: the gate mix wants 4 * decoder_dim in multiples of 1024", H);
-        const bool stamps = h->stage_times && ngroups == 0;
-        h->stage_valid = 0;
-        if (stamps) {
-            for (hipEvent_t& e : h->ev_stage)
-                if (!e) HIP_TRYN(hipEventCreate(&e));
-            HIP_TRYN(hipEventRecord(h->ev_stage[0], s));
-        }
-        for (int l = 0; l < 2; ++l) {
-            const std::string mod = l ? "lstm_1/linear" : "lstm/linear";
-            if (h->x3)
-                hipLaunchKernelGGL((nat_conv_x3_k<1, 2>), dim3((Lmax + 63) / 64, (MBG + 7) / 8, B), dim3(256), 0, s, enc, lengths_dev,
-                                   reinterpret_cast<const uint4*>(h->extra(mod + "#cond#x3")), h->extra(mod + "#zerob"), nullptr, nullptr, nullptr, nullptr,
-                                   l ? EG2 : EG1, Lmax, E, G4, (int)NAT_ACT_NONE, 0);
-            else
-                hipLaunchKernelGGL((nat_conv_mfma_k<1, 2>), dim3((Lmax + 63) / 64, (MBG + 7) / 8, B), dim3(256), 0, s, enc, lengths_dev,
-                                   reinterpret_cast<const float4*>(h->extra(mod + "#cond")), h->extra(mod + "#zerob"), nullptr, nullptr, nullptr, nullptr,
-                                   l ? EG2 : EG1, Lmax, E, G4, (int)NAT_ACT_NONE, 0);
-        }
-        const size_t mlds = ((size_t)(Lmax + 3) / 4 * 4 + (size_t)Lmax * NAT_MIX_FT) * sizeof(float);
-        if (mlds > 48 * 1024)
-            HIP_TRYN(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_gates_mix_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        // option "resident": 1 <= B <= 4, fp32 products, the reference's decoder dimensions, no hand-over, a stream that is not being captured
-        // and a grid the device can hold; in every other case the call takes the per-frame launches below
-        int res_grid = 0;
-        if (h->resident && ngroups == 0 && B <= 4 && !h->x3 && H == vtts::NAT_RES_H && PN == vtts::NAT_RES_PN && MEL <= vtts::NAT_RES_MELMAX) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            HIP_TRYN(hipStreamIsCapturing(s, &cap));
-            if (!h->cu_count) {
-                int dev = 0;
-                HIP_TRYN(hipGetDevice(&dev));
-                HIP_TRYN(hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, dev));
-            }
-            // at most one workgroup per CU: the default grid where the device has that many CUs, else the next smaller one
-            res_grid = h->resident_grid ? h->resident_grid : NAT_RES_DEFAULT_GRID;
-            while (res_grid > h->cu_count && res_grid > 64) res_grid /= 2;
-            if (cap != hipStreamCaptureStatusNone || res_grid > h->cu_count) res_grid = 0;
-        }
-        const int mtiles = (Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT, mfirst = res_grid ? mtiles : (64 / NAT_MIX_FT < mtiles ? 64 / NAT_MIX_FT : mtiles);
-        auto gates = [&](int tile0, int ntiles, hipStream_t gs) {
-            hipLaunchKernelGGL(nat_gates_mix_k, dim3(ntiles, 2 * (G4 / 1024), B), dim3(256), mlds, gs, EG1, EG2, h->extra("lstm/linear#condb"),
-                               h->extra("lstm_1/linear#condb"), lengths_dev, durations_dev, nframes_dev, G1, G2, Lmax, Fmax, G4, tile0);
-        };
-        gates(0, mfirst, s);
-        if (mtiles > mfirst) {
-            HIP_TRYN(hipEventRecord(h->ev_fork, s));
-            HIP_TRYN(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            gates(mfirst, mtiles - mfirst, h->side);
-            HIP_TRYN(hipEventRecord(h->ev_gates, h->side));
-        }
-        const float4* w1 = reinterpret_cast<const float4*>(h->extra("lstm/linear#mfma"));
-        const float4* w2 = reinterpret_cast<const float4*>(h->extra("lstm_1/linear#mfma"));
-        const float4* f1 = reinterpret_cast<const float4*>(h->extra("linear_1#k4"));
-        const float4* f2 = reinterpret_cast<const float4*>(h->extra("linear_2#k4"));
-        const float4* wp = reinterpret_cast<const float4*>(h->extra("linear#k4"));
-        const float* bp = h->dev("linear", "b");
-        const bool wide = B > 32;  // two 32-sentence tiles per wave once there are that many sentences
-        const dim3 lgrid(H / 8, wide ? Bp / 64 : 1);
-        auto lstm = [&](const float* inA, int KA, const float* inB, const float4* w, const float* gin, float* cst, float* hout, int f) {
-            const NatLstmOps o{inA, inB, w, nullptr, cst, hout, gin + (size_t)f * G4, (size_t)Fmax * G4};
-            if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, nframes_dev, f, B, Bp, H);
-            else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, nframes_dev, f, B, Bp, H);
-        };
-        const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);
-        auto group_handover = [&](int frames_done) -> int {  // a group whose last frame was frames_done - 1: its postnet starts now, on the side stream
-            for (int g = 0; g < ngroups; ++g) {
-                if (group_frames[g] != frames_done) continue;
-                HIP_TRYN(hipEventRecord(h->ev_dec[g], s));
-                HIP_TRYN(hipStreamWaitEvent(h->side, h->ev_dec[g], 0));
-                postnet(group_row0[g], group_row0[g + 1], group_frames[g], h->side);
-                HIP_TRYN(hipEventRecord(h->ev_done[g], h->side));
-            }
-            return VTTS_OK;
-        };
-        // option "bf16x3": the split-state step (nat_dec_lstm_x3_k) where its 16-row steps divide the row blocks; the state's two parities hold
-        // two bf16 planes each (the same bytes as the fp32 rows)
-        const bool dx3 = h->x3 && PN % 16 == 0 && H % 16 == 0 && ((PN + H) / 16) % 8 == 0 && ((PN + 2 * H) / 16) % 8 == 0;
-        const size_t zplane = (size_t)ZW * Bp;  // bf16 elements per plane
-        const uint4* w1x = reinterpret_cast<const uint4*>(h->extra("lstm/linear#x3"));
-        const uint4* w2x = reinterpret_cast<const uint4*>(h->extra("lstm_1/linear#x3"));
-        auto lstm_x3 = [&](unsigned short* zcx, const unsigned short* zpx, int KA, int K, const uint4* w, const float* gin, float* cst, int out_row0, int f) {
-            const NatLstmX3Ops o{zcx, zpx, zplane, w, gin + (size_t)f * G4, (size_t)Fmax * G4, cst, zcx, out_row0};
-            if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, nframes_dev, f, B, Bp, H);
-            else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, nframes_dev, f, B, Bp, H);
-        };
-        if (stamps) HIP_TRYN(hipEventRecord(h->ev_stage[1], s));
-        if (res_grid) {  // every frame's gates are on `s` already (mfirst = mtiles)
-            HIP_TRYN(hipMemsetAsync(res_sync, 0, 256, s));
-            const size_t e4 = (size_t)E * G4;  // Haiku rows [E, ...): the state's rows
-            const vtts::NatResidentArgs ra{h->dev("lstm/linear", "w") + e4, h->dev("lstm_1/linear", "w") + e4, h->dev("linear", "w"), bp, h->dev("linear_1", "w"),
-                                           h->dev("linear_2", "w"), G1, G2, nframes_dev, keep_dev, mel0, res_xch, res_sync,
-                                           reinterpret_cast<unsigned long long*>(res_sync + 2), Fmax, MEL};
-            const hipError_t le = vtts::launch_nat_dec_resident(ra, B, res_grid, s);
-            if (le == hipSuccess) {
-                h->resident_used = 1;
-                h->res_sync = res_sync;
-            } else if (le == hipErrorCooperativeLaunchTooLarge) {
-                (void)hipGetLastError();  // the runtime cannot hold the grid resident: the launches below take over
-            } else {
-                return failf(VTTS_ERR_HIP, "resident decoder launch failed: %s", hipGetErrorString(le));
-            }
-        }
-        for (int f = 0; f < Fmax && !h->resident_used; ++f) {
-            if (f == 64 && mtiles > mfirst) HIP_TRYN(hipStreamWaitEvent(s, h->ev_gates, 0));
-            float* zc = Z[f & 1];
-            float* zp = Z[(f + 1) & 1];
-            if (dx3) {
-                unsigned short* zcx = reinterpret_cast<unsigned short*>(zc);
-                const unsigned short* zpx = reinterpret_cast<const unsigned short*>(zp);
-                lstm_x3(zcx, zpx, PN, PN + H, w1x, G1, c1, PN, f);
-                lstm_x3(zcx, zpx, PN + H, PN + 2 * H, w2x, G2, c2, PN + H, f);
-                hipLaunchKernelGGL(nat_dec_proj_prenet_k<true>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, nframes_dev, f1, f2, wp, bp, keep_dev, mel0, f,
-                                   B, Bp, Fmax, PN, H, MEL, zplane);
-                rc = group_handover(f + 1);
-                if (rc) return rc;
-                continue;
-            }
-            lstm(zc, PN, zp + (size_t)PN * Bp, w1, G1, c1, zc + (size_t)PN * Bp, f);
-            lstm(zc, PN + H, zp + (size_t)(PN + H) * Bp, w2, G2, c2, zc + (size_t)(PN + H) * Bp, f);
-            hipLaunchKernelGGL(nat_dec_proj_prenet_k<false>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, nframes_dev, f1, f2, wp, bp, keep_dev, mel0, f, B,
-                               Bp, Fmax, PN, H, MEL, (size_t)0);
-            rc = group_handover(f + 1);  // under the remaining decoder steps
-            if (rc) return rc;
-        }
+        if (int rc = group_handover(f + 1)) return rc;  // under the remaining decoder steps
     }
-    if (ngroups > 0) {
-        for (int g = 0; g < ngroups; ++g) HIP_TRYN(hipStreamWaitEvent(s, h->ev_done[g], 0));  // stream order for the caller: mel_dev is complete after this call on `s`
-        h->groups_valid = ngroups;
+    return VTTS_OK;
+}
+
+// forward(), forward_groups(), forward_from_encoder() and forward_teacher()
+int nat_acoustic_run(NatCall& c) {
+    if (int rc = nat_validate(c)) return rc;
+    vtts_nat_acoustic* h = c.h;
+    if (int rc = nat_side_stream(h, c.ngroups)) return rc;
+    h->resident_used = 0;
+    if (c.enc_pre) c.ws.enc = const_cast<float*>(c.enc_pre);  // read only from here on
+    else if (int rc = run_token_encoder(*h, "token_encoder/~/", h->cfg.vocab_size, h->cfg.encoder_dim, c.tokens, c.lengths, c.B, c.Lmax, c.ws.bufA, c.ws.bufB, c.ws.lstm_ws, c.ws.enc, c.s)) return rc;  // model.py:131
+    HIP_TRY(hipMemsetAsync(c.mel, 0, (size_t)c.B * c.Fmax * c.MEL * 4, c.s));  // rows past a sentence's last frame
+    if (int rc = c.mels ? nat_teacher_decoder(c) : nat_ar_decoder(c)) return rc;
+    if (c.ngroups > 0) {
+        for (int g = 0; g < c.ngroups; ++g) HIP_TRY(hipStreamWaitEvent(c.s, h->ev_done[g], 0));  // stream order for the caller: mel is complete after this call on `s`
+        h->groups_valid = c.ngroups;
     } else {
-        const bool stamps = !tf && h->stage_times;
-        if (stamps) HIP_TRYN(hipEventRecord(h->ev_stage[2], s));
-        postnet(0, B, Fmax, s);
+        const bool stamps = !c.mels && h->stage_times;
+        if (stamps) HIP_TRY(hipEventRecord(h->ev_stage[2], c.s));
+        nat_postnet(c, 0, c.B, c.Fmax, c.s);
         if (stamps) {
-            HIP_TRYN(hipEventRecord(h->ev_stage[3], s));
+            HIP_TRY(hipEventRecord(h->ev_stage[3], c.s));
             h->stage_valid = 1;
         }
     }
@@ -2472,11 +2208,13 @@ static int nat_acoustic_run(vtts_nat_acoustic* h, const int32_t* tokens_dev, con
     return VTTS_OK;
 }
 
+}  // namespace
+
 VTTS_API int vtts_nat_acoustic_forward(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
                                        const int32_t* nframes_dev, int B, int Lmax, int Fmax, const uint8_t* keep_dev, float* mel_dev,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    return nat_acoustic_run(h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, stream, 0,
-                            nullptr, nullptr);
+    NatCall c{h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    return nat_acoustic_run(c);
 }
 
 VTTS_API int vtts_nat_acoustic_forward_groups(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
@@ -2484,8 +2222,9 @@ VTTS_API int vtts_nat_acoustic_forward_groups(vtts_nat_acoustic* h, const int32_
                                               void* workspace, size_t workspace_bytes, void* stream, int ngroups, const int32_t* group_row0,
                                               const int32_t* group_frames) {
     if (ngroups < 1) return failf(VTTS_ERR_INVALID, "forward_groups() needs at least one group (got %d)", ngroups);
-    return nat_acoustic_run(h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, stream,
-                            ngroups, group_row0, group_frames);
+    NatCall c{h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
+              ngroups, group_row0, group_frames};
+    return nat_acoustic_run(c);
 }
 
 // The teacher-forced pass (AcousticModel.__call__, model.py:146-169): the token encoder, forward()'s postnet, and the decoder fed with the target mels
@@ -2495,9 +2234,9 @@ VTTS_API int vtts_nat_acoustic_forward_teacher(vtts_nat_acoustic* h, const int32
     if (!tokens_dev || !mels_dev) return failf(VTTS_ERR_INVALID, "null argument");
     if ((uintptr_t)mels_dev % 16 != 0 || (uintptr_t)keep_dev % 4 != 0)
         return failf(VTTS_ERR_INVALID, "forward_teacher() reads mels_dev in 16-byte and keep_dev in 4-byte units: align them so");
-    const NatTeacher tf{mels_dev, zone_dev, mel_pre_dev};
-    return nat_acoustic_run(h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, stream, 0, nullptr,
-                            nullptr, nullptr, &tf);
+    NatCall c{h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    c.mels = mels_dev, c.zone = zone_dev, c.mel_pre = mel_pre_dev;
+    return nat_acoustic_run(c);
 }
 
 // The token encoder alone, ahead of forward_from_encoder(): it needs the tokens only, so a pipeline can run it while the host still turns the
@@ -2512,15 +2251,10 @@ VTTS_API int vtts_nat_acoustic_encode(vtts_nat_acoustic* h, const int32_t* token
     if (rc) return rc;
     if (!workspace || workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
     const int D = h->cfg.encoder_dim, V = h->cfg.vocab_size;
-    char* p = static_cast<char*>(workspace);
-    auto take = [&](size_t bytes) {
-        float* r = reinterpret_cast<float*>(p);
-        p += align_up(bytes, 256);
-        return r;
-    };
-    float* bufA = take((size_t)B * Lmax * D * 4);
-    float* bufB = take((size_t)B * Lmax * D * 4);
-    float* lstm_ws = take(nat_enc_lstm_floats(D, B, Lmax) * 4);  // (fits: the full layout holds the same three buffers and more)
+    NatCarver w{static_cast<char*>(workspace)};  // its own three-buffer prefix (fits: the full layout holds the same three buffers and more)
+    float* bufA = w.take((size_t)B * Lmax * D * 4);
+    float* bufB = w.take((size_t)B * Lmax * D * 4);
+    float* lstm_ws = w.take(nat_enc_lstm_floats(D, B, Lmax) * 4);
     rc = run_token_encoder(*h, "token_encoder/~/", V, D, tokens_dev, lengths_dev, B, Lmax, bufA, bufB, lstm_ws, enc_dev, static_cast<hipStream_t>(stream));
     if (rc) return rc;
     hipError_t e = hipGetLastError();
@@ -2534,13 +2268,14 @@ VTTS_API int vtts_nat_acoustic_forward_from_encoder(vtts_nat_acoustic* h, const 
                                                     const int32_t* group_frames) {
     if (!enc_dev) return failf(VTTS_ERR_INVALID, "null argument");
     if (ngroups < 0) return failf(VTTS_ERR_INVALID, "ngroups must be >= 0 (got %d)", ngroups);
-    return nat_acoustic_run(h, nullptr, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, stream, ngroups,
-                            group_row0, group_frames, enc_dev);
+    NatCall c{h, nullptr, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
+              ngroups, group_row0, group_frames, enc_dev};
+    return nat_acoustic_run(c);
 }
 
 VTTS_API int vtts_nat_acoustic_wait_group(vtts_nat_acoustic* h, int group, void* stream) {
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     if (group < 0 || group >= h->groups_valid) return failf(VTTS_ERR_STATE, "wait_group(%d): the last forward_groups() call had %d groups", group, h->groups_valid);
-    HIP_TRYN(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_done[group], 0));
+    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_done[group], 0));
     return VTTS_OK;
 }

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(32 * CW) void nat_dec_resident_k(NatResidentArgs a)
 #pragma unroll
         for (int j = 0; j < RJ2; ++j) w2r[j] = c2[(size_t)(ks + 32 * j) * RG4];
     }
-    // G1 / G2 hold the gates in the step kernel's accumulator order (nat.hip: hcol)
+    // G1 / G2 hold the gates in the step kernel's accumulator order (nat_model.h: nat_hcol)
     const int gcol = (unit >> 3) * 32 + (unit & 1) * 16 + ((unit >> 1) & 3) * 4 + gate;
     // the column of the projection / of the prenet this half-wave computes (clamped: a half-wave without one computes and stores nothing)
     const int ocol = wg + NWG * cl;

@@ -3,12 +3,26 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include "../../include/vtts_hifigan.h"
+
+#define VTTS_API extern "C" __attribute__((visibility("default")))
 
 namespace vtts {
 
-// engine.hip: record the calling thread's last error message (vtts_last_error()) and return `code`
-int set_error(int code, const char* msg);
+// engine.hip: record the calling thread's last error message (vtts_last_error(); printf-style, 511 characters at most) and return `code`
+int failf(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t _e = (expr);                                                                                \
+        if (_e != hipSuccess)                                                                                  \
+            return vtts::failf(VTTS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON A DEVICE: a process that drives several GPUs (a
 // second Generator on cuda:1 after cuda:0) must set it once per device, not once per process.  `done` = the caller's static
