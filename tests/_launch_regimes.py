@@ -10,11 +10,12 @@ from __future__ import annotations
 
 XCDS = 8  # the launchers pad gridDim.x to a multiple of this when the XCD-aware order is on
 
-# ---- thresholds (name in the sources -> value) -------------------------------------------------------------------------------------------
+# ---- thresholds (name -> value) -------------------------------------------------------------------------------------------
 THRESHOLDS = {
     "G_MIN_WGS": 384,            # kernels_bf16_rbg.hip: wide bf16 pair tile from this many wide-tile workgroups (tiles per row * B)
     "XCD_MAP_MIN_TILES": 192,    # kernels_bf16_rbg.hip: XCD order of resblock_pair_g_bf16_k from this many tiles per utterance slot
     "RB_BF16_XCD_MIN": 192,      # kernels_bf16_rbk.hip: XCD order of resblock_bf16_k from this many windows (a literal there)
+    # the next four: device_common.h's XCD_MIN_TILES, named here by the kernel that applies it
     "F32_XCD_MIN_TILES": 64,     # kernels_f32_mfma.hip: XCD order of conv1d_f32_mfma_k from this many time tiles per grid row
     "F32_MIN_WGS": 384,          # kernels_f32_mfma.hip: launch_conv1d_f32_mfma's MIN_WGS, wide tile from this many wide-tile workgroups
     "FP_XCD_MIN_TILES": 64,      # kernels_f32_pair.hip: XCD order of resblock_pair_f32_k

@@ -75,10 +75,10 @@ def test_thresholds_match_the_sources():
     T = R.THRESHOLDS
     assert _constexpr(rbg, "G_MIN_WGS") == T["G_MIN_WGS"]
     assert _constexpr(rbg, "XCD_MAP_MIN_TILES") == T["XCD_MAP_MIN_TILES"]
-    assert _constexpr(f32, "F32_XCD_MIN_TILES") == T["F32_XCD_MIN_TILES"]
-    assert _constexpr(fp, "FP_XCD_MIN_TILES") == T["FP_XCD_MIN_TILES"]
-    assert _constexpr(x3, "X3_XCD_MIN_TILES") == T["X3_XCD_MIN_TILES"]
-    assert _constexpr(rx, "RX_XCD_MIN_TILES") == T["RX_XCD_MIN_TILES"]
+    # the fp32 / split kernels share ONE threshold and ONE tile mapping (device_common.h): the table's four names are the four kernels that use it
+    common = _src("device_common.h")
+    for name in ("F32_XCD_MIN_TILES", "FP_XCD_MIN_TILES", "X3_XCD_MIN_TILES", "RX_XCD_MIN_TILES"):
+        assert _constexpr(common, "XCD_MIN_TILES") == T[name], name
     launcher = f32[f32.index("hipError_t launch_conv1d_f32_mfma(") :]
     assert _constexpr(launcher[: launcher.index("\n}\n")], "MIN_WGS") == T["F32_MIN_WGS"]
     # resblock_bf16_k's window threshold is a literal in two places: the kernel's xmap and the launcher's grid padding
@@ -86,8 +86,11 @@ def test_thresholds_match_the_sources():
     grid = re.findall(r"if \(\(int\)grid\.x >= (\d+)\) grid\.x = \(grid\.x \+ 7\) / 8 \* 8;", rbk)
     assert kern and grid and {int(v) for v in kern + grid} == {T["RB_BF16_XCD_MIN"]}, (kern, grid)
     # the kernels that share a threshold with their launcher name the same constant in both places
-    for src, name in ((rbg, "XCD_MAP_MIN_TILES"), (f32, "F32_XCD_MIN_TILES"), (fp, "FP_XCD_MIN_TILES"), (x3, "X3_XCD_MIN_TILES"), (rx, "RX_XCD_MIN_TILES")):
-        assert re.search(rf"grid\.x >= {name}\) grid\.x = \(grid\.x \+ 7\) / 8 \* 8", src), name
+    assert re.search(r"grid\.x >= XCD_MAP_MIN_TILES\) grid\.x = \(grid\.x \+ 7\) / 8 \* 8", rbg)
+    assert re.search(r"gridDim\.x >= XCD_MIN_TILES\)", common) and re.search(r"tiles >= XCD_MIN_TILES \? \(tiles \+ 7\) / 8 \* 8 : tiles", common)
+    for src, name in ((f32, "kernels_f32_mfma.hip"), (fp, "kernels_f32_pair.hip"), (x3, "kernels_x3.hip"), (rx, "kernels_x3_rb.hip")):
+        assert "_XCD_MIN_TILES" not in src, name  # no private copy of the threshold
+        assert len(re.findall(r"if \(!xcd_tile\(L, \w+, tile\)\) return;", src)) == 1 and len(re.findall(r"dim3 grid\(xcd_grid_x\(", src)) == 1, name
 
 
 def test_decision_rules_match_the_sources():

@@ -22,6 +22,36 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 }
 __device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+// Two bf16 terms of two fp32 values, v = hi + lo to 16 significand bits: (hi pair, lo pair), round-to-nearest-even; v - float(hi) is exact in fp32.
+// THE split of the split-operand kernels (x3_common.h) and of their host packers (vtts_internal.h: split_bf16).
+__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
+    hi = pack_bf16x2(v0, v1);
+    lo = pack_bf16x2(v0 - bf16_lo(hi), v1 - bf16_hi(hi));
+}
+// Exchange across the wave halves (v_permlane32_swap): lanes 0-31 get the upper half's pd in qd, lanes 32-63 the lower half's qd in pd.  In the
+// accumulator layout (device_common.h: acc_row) a lane holds channels 8 rq + 4 lh + i; with pd = the packed pairs of rq = 2p and qd = those of
+// rq = 2p + 1, lh = 0 owns channels 16p .. 16p+7 and lh = 1 owns 16p+8 .. 16p+15 afterwards: one 16-byte slot of a channels-last tile row.
+__device__ __forceinline__ void swap_pair(unsigned& pd, unsigned& qd) {
+    auto r = __builtin_amdgcn_permlane32_swap(pd, qd, false, false);
+    pd = r[0];
+    qd = r[1];
+}
+// Keep hipcc from sinking a k-step's look-ahead loads to their uses (it does, to save registers: the first build waited for every fragment right
+// in front of the MFMA that consumes it) and spread them between the step's NMF MFMAs: one MFMA, then the next pending of NA A loads (VMEM) or
+// NB B reads (DS).
+template <int NMF, int NA, int NB>
+__device__ __forceinline__ void pin_loads() {
+    int done = 0;
+#pragma unroll
+    for (int m = 0; m < NMF; ++m) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        const int upto = (m + 1) * (NA + NB) / NMF;
+        for (; done < upto; ++done) {
+            if (done < NA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+    }
+}
 // Plain multiply / add.  No v_pk_*_f32 may appear in these kernels (see lrelu01_pack below): the bf16 kernel files are compiled with
 // -fno-slp-vectorize (csrc/build.py) so that hipcc does not pair scalar f32 operations into packed ones.  NOT inline asm: a VALU
 // instruction hidden in an asm statement that reads an MFMA result gets none of the wait states the hazard recogniser inserts

@@ -367,14 +367,6 @@ const char* bf16_kernel_name(int cls, int K) {
     return buf;
 }
 
-static unsigned short f32_to_bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);  // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
 size_t bf16_packed_bytes(const BPackGeom& g) {
     const int ncc = g.cinp / g.ckc, nsl = (g.ks + g.tg - 1) / g.tg;
     return (size_t)(g.coutp / g.mt) * ncc * nsl * ((size_t)g.mt * g.tg * g.ckc * 2);

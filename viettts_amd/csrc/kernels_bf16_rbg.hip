@@ -450,14 +450,8 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     __syncthreads();  // B2: every wave is done reading the X tile
 
     // A lane's accumulators for one 32x32 block: column (time) l31, rows (channels) 8*rq + 4*lh + i, r = 4*rq + i.
-    // (lo, hi) of two packed dwords: after swapping across the wave halves, lh = 0 owns channels 16p .. 16p+7 and
+    // (lo, hi) of two packed dwords: after swap_pair (bf16_common.h) lh = 0 owns channels 16p .. 16p+7 and
     // lh = 1 owns 16p+8 .. 16p+15 of rq pair p, as [P'0 P'1 Q'0 Q'1].
-    auto swap_pair = [](unsigned& pd, unsigned& qd) {
-        auto r = __builtin_amdgcn_permlane32_swap(pd, qd, false, false);
-        pd = r[0];
-        qd = r[1];
-    };
-
 
     // ---------------- epilogue 1: LeakyReLU(0.1), bf16, zero outside [0, L) -> xt tile in LDS ----------------
     load_bias(a.bias + C);  // c2's bias: lands while epilogue 1 runs

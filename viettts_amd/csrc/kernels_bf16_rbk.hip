@@ -96,11 +96,6 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     const unsigned short* __restrict__ xg = static_cast<const unsigned short*>(a.x) + (size_t)b * Lp * C;
     unsigned short* __restrict__ yg = static_cast<unsigned short*>(a.y) + (size_t)b * Lp * C;
 
-    auto swap_pair = [](unsigned& pd, unsigned& qd) {
-        auto r = __builtin_amdgcn_permlane32_swap(pd, qd, false, false);
-        pd = r[0];
-        qd = r[1];
-    };
     auto act2 = [](unsigned u) { return lrelu01_pack(bf16_lo(u), bf16_hi(u)); };  // LRELU_SLOPE, model.py:5
 
     for (int u = tid; u < 6 * C; u += THREADS) reinterpret_cast<float*>(lds + 2 * T::TILE_BYTES)[u] = a.bias[u];

@@ -183,11 +183,6 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             }
         }
     };
-    auto swap_pair = [](unsigned& pd, unsigned& qd) {
-        auto r = __builtin_amdgcn_permlane32_swap(pd, qd, false, false);
-        pd = r[0];
-        qd = r[1];
-    };
 
     // small launches (batch-1 latency) split the chunks over gridDim.y workgroups per tile (each stages the tile itself)
     const int cpw = NCH / (int)gridDim.y, c_lo = (int)blockIdx.y * cpw, c_hi = c_lo + cpw;

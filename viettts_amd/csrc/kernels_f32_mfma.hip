@@ -36,7 +36,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int round_up4(int v) { return (v + 3) & ~3; }
 constexpr int MAX_DIL = 5;  // resblock_dilation_sizes max in V1; larger rates fall back to the generic kernel
-constexpr int F32_XCD_MIN_TILES = 64;  // XCD-aware tile order of conv1d_f32_mfma_k from this many time tiles per grid row on
 
 // =================================================================================================
 // dilated Conv1d
@@ -80,15 +79,8 @@ __global__ __launch_bounds__(256, 3) void conv1d_f32_mfma_k(ConvArgs a) {  // re
     const int b = a.zrev ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
     const int LP = a.L;              // row pitch of x / res / y
     const int L = valid_len(a, b);   // this utterance's columns (ragged batches; == LP otherwise)
-    // XCD-aware tile order (as the bf16 pair kernel, kernels_bf16_rbg.hip): workgroups go to the 8 XCDs round-robin in launch order, so on
-    // launches of at least F32_XCD_MIN_TILES tiles per row of the grid (gridDim.x then padded to a multiple of 8 by the launcher) XCD
-    // blockIdx.x % 8 takes a contiguous, balanced eighth of the time tiles: a tile's halo columns were staged by the same L2's previous tile
-    int tile = blockIdx.x;
-    if (gridDim.x >= F32_XCD_MIN_TILES) {
-        const int nt = (L + NT - 1) / NT, r = (int)((blockIdx.x + blockIdx.z) & 7), lo = (r * nt) >> 3, hi = ((r + 1) * nt) >> 3;
-        tile = lo + (int)(blockIdx.x >> 3);
-        if (tile >= hi) return;
-    }
+    int tile;  // XCD-aware tile order (device_common.h)
+    if (!xcd_tile(L, NT, tile)) return;
     const int t0 = tile * NT;
     if (t0 >= L) return;  // a tile past the utterance's end (ragged batches)
     const int m0 = blockIdx.y * MT + wm * (MT / T::WM);  // first output channel of this wave
@@ -210,7 +202,7 @@ __global__ __launch_bounds__(256, 3) void conv1d_f32_mfma_k(ConvArgs a) {  // re
                 if (ok) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const int co = acc_row(r, lh, m0 + mr * 32);
                         a.y[((long)b * COUT + co) * LP + t] = acc[mr][nr][r] + a.bias[co];
                     }
                 }
@@ -225,14 +217,14 @@ __global__ __launch_bounds__(256, 3) void conv1d_f32_mfma_k(ConvArgs a) {  // re
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int r = r0 + q;
-                    const int off = (m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tc;
+                    const int off = acc_row(r, lh, m0 + mr * 32) * LP + tc;
                     rv[q] = has_res ? resb[off] : 0.0f;
                     yv[q] = mode != ACC_STORE ? yb[off] : 0.0f;
                 }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int r = r0 + q;
-                    const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int co = acc_row(r, lh, m0 + mr * 32);
                     const int off = co * LP + tc;
                     float v = acc[mr][nr][r] + a.bias[co];
                     if (has_res) v = v + rv[q];
@@ -266,8 +258,7 @@ template <class T>
 static hipError_t launch_tile(const ConvArgs& a, hipStream_t s) {
     static DynLdsOnce once;  // per device (vtts_internal.h)
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv1d_f32_mfma_k<T>), T::LDS_BYTES, once); e != hipSuccess) return e;
-    dim3 grid((a.L + T::NT - 1) / T::NT, T::COUT / T::MT, a.B);
-    if ((int)grid.x >= F32_XCD_MIN_TILES) grid.x = (grid.x + 7) / 8 * 8;  // whole rounds of the 8 XCDs; with gridDim.x a multiple of 8, workgroup (x, y, z) runs on XCD x % 8
+    dim3 grid(xcd_grid_x((a.L + T::NT - 1) / T::NT), T::COUT / T::MT, a.B);
     hipLaunchKernelGGL(conv1d_f32_mfma_k<T>, grid, dim3(256), T::LDS_BYTES, s, a);
     return hipGetLastError();
 }
@@ -492,7 +483,7 @@ __global__ __launch_bounds__(256) void convT1d_f32_mfma_k(ConvArgs a) {
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const int co = acc_row(r, lh, m0 + mr * 32);
                         const float bv = a.bias[co];
                         float2 v;
                         v.x = acc[0][mr][nr][r] + bv;

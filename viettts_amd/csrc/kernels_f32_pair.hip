@@ -30,7 +30,6 @@ namespace vtts {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int FP_MAX_DIL = 5;
-constexpr int FP_XCD_MIN_TILES = 64;
 constexpr int fp_round_up4(int v) { return (v + 3) & ~3; }
 
 struct PairArgsF32 {
@@ -79,13 +78,8 @@ __global__ __launch_bounds__(256, T::WPS) void resblock_pair_f32_k(PairArgsF32 p
     const int b = a.zrev ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
     const int LP = a.L;              // row pitch of x / y
     const int L = valid_len(a, b);   // this utterance's columns (ragged batches; == LP otherwise): zero padding and store masks follow it
-    // XCD-aware tile order (as conv1d_f32_mfma_k): XCD blockIdx.x % 8 takes a contiguous, balanced eighth of the utterance's time tiles
-    int tile = blockIdx.x;
-    if (gridDim.x >= FP_XCD_MIN_TILES) {
-        const int nt = (L + NT2 - 1) / NT2, r = (int)((blockIdx.x + blockIdx.z) & 7), lo = (r * nt) >> 3, hi = ((r + 1) * nt) >> 3;
-        tile = lo + (int)(blockIdx.x >> 3);
-        if (tile >= hi) return;
-    }
+    int tile;  // XCD-aware tile order (device_common.h)
+    if (!xcd_tile(L, NT2, tile)) return;
     const int t0 = tile * NT2;  // first output time of this workgroup
     if (t0 >= L) return;
     const int dil = a.dil;
@@ -222,7 +216,7 @@ __global__ __launch_bounds__(256, T::WPS) void resblock_pair_f32_k(PairArgsF32 p
     for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int co = acc_row(r, lh, m0 + mr * 32);
             const float bv = a.bias[co];
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
@@ -266,7 +260,7 @@ __global__ __launch_bounds__(256, T::WPS) void resblock_pair_f32_k(PairArgsF32 p
 #pragma unroll
                 for (int q = 0; q < EB; ++q) {
                     const int r = r0 + q;
-                    const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int co = acc_row(r, lh, m0 + mr * 32);
                     const long idx = ((long)b * C + co) * LP + tc;
                     rv[q] = a.res[idx];
                     yv[q] = mode != ACC_STORE ? a.y[idx] : 0.0f;
@@ -274,7 +268,7 @@ __global__ __launch_bounds__(256, T::WPS) void resblock_pair_f32_k(PairArgsF32 p
 #pragma unroll
                 for (int q = 0; q < EB; ++q) {
                     const int r = r0 + q;
-                    const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int co = acc_row(r, lh, m0 + mr * 32);
                     const long idx = ((long)b * C + co) * LP + tc;
                     float v = acc[mr][nr][r] + p.bias2[co];
                     v = v + rv[q];
@@ -304,8 +298,7 @@ template <class T>
 static hipError_t launch_fp(const PairArgsF32& p, hipStream_t s) {
     static DynLdsOnce once;
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&resblock_pair_f32_k<T>), T::lds_floats(FP_MAX_DIL) * 4, once); e != hipSuccess) return e;
-    dim3 grid((p.a.L + T::NT2 - 1) / T::NT2, 1, p.a.B);
-    if ((int)grid.x >= FP_XCD_MIN_TILES) grid.x = (grid.x + 7) / 8 * 8;
+    dim3 grid(xcd_grid_x((p.a.L + T::NT2 - 1) / T::NT2), 1, p.a.B);
     hipLaunchKernelGGL(resblock_pair_f32_k<T>, grid, dim3(256), T::lds_floats(p.a.dil) * 4, s, p);
     return hipGetLastError();
 }

@@ -21,16 +21,11 @@
 //   * epilogue 2: + b2, + x (fp32, from HBM / L2), MRF accumulate / mean as device_common.h: epilogue_store, fp32 stores — in the MFMA
 //     accumulator layout a half-wave holds 32 consecutive time steps of one channel: coalesced 128-byte rows, no lane exchange.
 // LDS: two tiles of up to 78 KB -> one workgroup of 8 waves per CU (two waves per SIMD cover each other's fragment latencies).
-#include <string.h>
-
 #include <type_traits>
 
-#include "bf16_common.h"
-#include "device_common.h"
+#include "x3_common.h"
 
 namespace vtts {
-
-constexpr int X3_XCD_MIN_TILES = 64;
 
 struct PairArgsX3 {
     ConvArgs a;          // x, bias (b1), dil, slope_in, B, L, zrev; output side: y, res (= x), acc_mode, div
@@ -79,12 +74,8 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
     const int b = a.zrev ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
     const int LP = a.L;              // row pitch of x / y
     const int L = valid_len(a, b);   // this utterance's columns (ragged batches; == LP otherwise): zero padding and store masks follow it
-    int tile = blockIdx.x;
-    if (gridDim.x >= X3_XCD_MIN_TILES) {  // XCD-aware tile order (as the other pair kernels): XCD blockIdx.x % 8 takes a contiguous eighth of the tiles
-        const int nt = (L + NT2 - 1) / NT2, r = (int)((blockIdx.x + blockIdx.z) & 7), lo = (r * nt) >> 3, hi = ((r + 1) * nt) >> 3;
-        tile = lo + (int)(blockIdx.x >> 3);
-        if (tile >= hi) return;
-    }
+    int tile;  // XCD-aware tile order (device_common.h)
+    if (!xcd_tile(L, NT2, tile)) return;
     const int t0 = tile * NT2;
     if (t0 >= L) return;
     const int h1 = H2 * dil;
@@ -92,12 +83,6 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
     const float* __restrict__ xb = a.x + (long)b * C * LP;
     const int m0 = wm * (C / T::WM);         // first output channel of this wave
     const float slope = a.slope_in;
-
-    // two bf16 terms of two fp32 values: (hi pair, lo pair), round-to-nearest-even; v - float(hi) is exact in fp32
-    auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {
-        hi = pack_bf16x2(v0, v1);
-        lo = pack_bf16x2(v0 - bf16_lo(hi), v1 - bf16_hi(hi));
-    };
 
     // ---------------- X tile (channel chunk xc): lane <-> time step, 8 channels per unit; LeakyReLU, split, swizzled ds_write_b128 x 2 ----------------
     auto stage_x = [&](int xc) {
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
         for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float bv = bias[m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
+                const float bv = bias[acc_row(r, lh, m0 + mr * 32)];
 #pragma unroll
                 for (int nr = 0; nr < NR; ++nr) acc[mr][nr][r] = bv;
             }
@@ -202,22 +187,9 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
                 load_a(s0 + i + PA, (i + PA) % RA);
                 load_b(s0 + i + 1, (i + 1) & 1);
                 const int sl = i % RA, par = i & 1;
-                // small terms first; MR * NR independent accumulators between two MFMAs on the same one
-#pragma unroll
-                for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][mr][1], bf[par][nr][0], acc[mr][nr], 0, 0, 0);
-#pragma unroll
-                for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][mr][0], bf[par][nr][1], acc[mr][nr], 0, 0, 0);
-#pragma unroll
-                for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][mr][0], bf[par][nr][0], acc[mr][nr], 0, 0, 0);
-                // keep hipcc from sinking the look-ahead loads to their uses (it does, to save registers: the first build waited for every
-                // fragment right in front of the MFMA that consumes it) and spread them between this step's MFMAs (the bf16 pair kernel's
-                // pin_step): one MFMA, then the next pending A load (VMEM) or B read (DS)
+                x3_mma(acc, af[sl], bf[par]);
+                // bf16_common.h: pin_loads<3 * MR * NR, 2 * MR, 2 * NR>(), spelled out: behind x3_mma the call compiles to another instruction
+                // order at C = 128, k = 3 (and other register numbers in six more classes)
                 constexpr int NMF = 3 * MR * NR, NA = 2 * MR, NB = 2 * NR;
                 int done = 0;
 #pragma unroll
@@ -244,15 +216,8 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
     }
     __syncthreads();  // every wave is done reading the X tiles
 
-    auto swap_pair = [](unsigned& pd, unsigned& qd) {
-        auto r = __builtin_amdgcn_permlane32_swap(pd, qd, false, false);
-        pd = r[0];
-        qd = r[1];
-    };
-
     // ---------------- epilogue 1: + b1, LeakyReLU, zero outside [0, L), split -> xt tiles ----------------
-    // A lane's accumulators of one 32 x 32 block: column (time) l31, rows (channels) 8*rq + 4*lh + i, r = 4*rq + i.  After the exchange across
-    // the wave halves lh = 0 owns channels 16p .. 16p+7 and lh = 1 owns 16p+8 .. 16p+15 of the 16-channel half p (as the bf16 pair kernel).
+    // (per 16-channel half pp of a block: x3_common.h: put_block_split)
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -269,18 +234,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
                     v[e] = lrelu(acc[mr][nr][8 * pp + e], slope);  // (b1 is in the sum already)
                     if (!ok) v[e] = 0.0f;  // c2's own zero padding applies to xt
                 }
-                unsigned hp0, hp1, hq0, hq1, lp0, lp1, lq0, lq1;
-                split2(v[0], v[1], hp0, lp0);
-                split2(v[2], v[3], hp1, lp1);
-                split2(v[4], v[5], hq0, lq0);
-                split2(v[6], v[7], hq1, lq1);
-                swap_pair(hp0, hq0);
-                swap_pair(hp1, hq1);
-                swap_pair(lp0, lq0);
-                swap_pair(lp1, lq1);
-                const int off = tile_off<SPR2>(row, (cb >> 3) + lh);
-                *reinterpret_cast<uint4*>(thi + off) = make_uint4(hp0, hp1, hq0, hq1);
-                *reinterpret_cast<uint4*>(tlo + off) = make_uint4(lp0, lp1, lq0, lq1);
+                put_block_split<SPR2>(thi, tlo, row, (cb >> 3) + lh, v);
             }
         }
     for (int u = tid; u < 2 * H2 * SPR2; u += THREADS) {  // rows N1 .. N1 + 2*H2 - 1 are only read by the discarded output columns: keep them finite
@@ -311,7 +265,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
             const int t = t0 + n;
             const int tc = (n < NT2 && t < L) ? t : 0;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) rres[nr][r] = resb[(m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tc];
+            for (int r = 0; r < 16; ++r) rres[nr][r] = resb[acc_row(r, lh, m0 + mr * 32) * LP + tc];
         }
 #pragma unroll
         for (int nr = 0; nr < NR; ++nr) {
@@ -325,12 +279,12 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_pair_x3_k(PairArg
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int r = r0 + q;
-                    yv[q] = mode != ACC_STORE ? yb[(m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tc] : 0.0f;
+                    yv[q] = mode != ACC_STORE ? yb[acc_row(r, lh, m0 + mr * 32) * LP + tc] : 0.0f;
                 }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int r = r0 + q;
-                    const int co = m0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int co = acc_row(r, lh, m0 + mr * 32);
                     float v = acc[mr][nr][r];  // (b2 is in the sum already)
                     v = v + rres[nr][r];
                     if (mode == ACC_ADD) v = yv[q] + v;
@@ -363,8 +317,7 @@ template <class T>
 static hipError_t launch_x3(const PairArgsX3& p, hipStream_t s) {
     static DynLdsOnce once;
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&resblock_pair_x3_k<T>), T::lds_bytes(T::MAXDIL), once); e != hipSuccess) return e;
-    dim3 grid((p.a.L + T::NT2 - 1) / T::NT2, 1, p.a.B);
-    if ((int)grid.x >= X3_XCD_MIN_TILES) grid.x = (grid.x + 7) / 8 * 8;
+    dim3 grid(xcd_grid_x((p.a.L + T::NT2 - 1) / T::NT2), 1, p.a.B);
     hipLaunchKernelGGL(resblock_pair_x3_k<T>, grid, dim3(T::THREADS), T::lds_bytes(p.a.dil), s, p);
     return hipGetLastError();
 }
@@ -392,16 +345,28 @@ void pair_x3_pack(const float* w_hk, int C, int K, unsigned short* out) {
     float* hi = new float[2 * n];
     float* lo = hi + n;
     for (size_t i = 0; i < n; ++i) {
-        unsigned u;
-        memcpy(&u, &w_hk[i], 4);
-        u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;  // round to nearest even
-        memcpy(&hi[i], &u, 4);
-        lo[i] = w_hk[i] - hi[i];  // exact; bf16_pack rounds it to bf16
+        unsigned short h, l;
+        split_bf16(w_hk[i], h, l);
+        hi[i] = bf16_to_f32(h);  // (bf16_pack rounds to bf16 again: exact)
+        lo[i] = bf16_to_f32(l);
     }
     const BPackGeom g = pair_g_pack_geom(C, K);
     bf16_pack(hi, C, g, out);
     bf16_pack(lo, C, g, out + n);
     delete[] hi;
+}
+
+// A-fragment order of the transposed convolutions' and conv_pre's weights: [plane: hi, lo][outer][ks][mblk][lane][8] bf16, lane's element e of
+// (outer, ks, mblk) = weight(outer, row = mblk*32 + (lane & 31), k = ks*16 + 8*(lane >> 5) + e), split (vtts_internal.h: split_bf16)
+template <class F>
+static void x3_pack_fragments(int nouter, int ksteps, int mb, unsigned short* out, F weight) {
+    const size_t plane = (size_t)nouter * ksteps * mb * 512;  // elements
+    size_t o = 0;
+    for (int outer = 0; outer < nouter; ++outer)
+        for (int ks = 0; ks < ksteps; ++ks)
+            for (int mblk = 0; mblk < mb; ++mblk)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e, ++o) split_bf16(weight(outer, mblk * 32 + (lane & 31), ks * 16 + 8 * (lane >> 5) + e), out[o], out[plane + o]);
 }
 
 hipError_t launch_pair_x3(const ConvArgs& a, const void* w1, const void* w2, const float* bias2, hipStream_t s) {
@@ -420,7 +385,7 @@ hipError_t launch_pair_x3(const ConvArgs& a, const void* w1, const void* w2, con
 // The four transposed convolutions (model.py:112-114: x = ups_i(leaky_relu(x, 0.1))) with split operands, polyphase form (k = 2 * stride;
 // kernels_f32_mfma.hip: output p = s q + r of group g = r / (s/2) reads input frames q + g - 1 + m, m = 0, 1, through tap
 // j = s (g - 1 + m) + pad_a - r): per group a GEMM  Y_g[m' = co * SH + ph, q] = sum_{m, ci} W_g[m'][(m, ci)] lrelu(x)[ci][q + g - 1 + m].
-// Same staging as the pair kernel (fp32 channel-major in, hi / lo channels-last tiles of N1 + 2 frames); a wave owns one 32-row block of m' in BOTH
+// Same staging as the pair kernel's stage_x (fp32 channel-major in, hi / lo channels-last tiles of N1 + 2 frames); a wave owns one 32-row block of m' in BOTH
 // groups (m-block index = group), so the three distinct B fragments (frames q - 1, q, q + 1) are read once per k-step and, in the accumulator layout,
 // a lane ends up with consecutive output samples of one channel: SH = 4 -> a float4 per group (16 contiguous bytes of y[co][8 q + 4 g ..]),
 // SH = 1 -> a float2 of both groups (y[co][2 q], y[co][2 q + 1]).  fp32 in HBM on both sides, as everything outside the matrix products.
@@ -461,10 +426,6 @@ __global__ __launch_bounds__(T::THREADS, 2) void convt_x3_k(ConvArgs a) {
     const int mblk = blockIdx.y * T::WM + wm;  // this wave's 32-row block of m' (in both groups)
     const float* __restrict__ xb = a.x + (long)b * CIN * LP;
     const float slope = a.slope_in;
-    auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {
-        hi = pack_bf16x2(v0, v1);
-        lo = pack_bf16x2(v0 - bf16_lo(hi), v1 - bf16_hi(hi));
-    };
     // ---- input tile: frames t0 - 1 .. t0 + N1 (zero outside the utterance: lax "SAME"), lane <-> frame, 8 channels per unit ----
     {
         constexpr int NBLK = (ROWS + 63) / 64, UNITS = NBLK * SPR, UB = 4;
@@ -560,17 +521,7 @@ __global__ __launch_bounds__(T::THREADS, 2) void convt_x3_k(ConvArgs a) {
                         const int pa = term == 0 ? 1 : 0, pb = term == 1 ? 1 : 0;
                         acc[g][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][gm][pa], bf[sl][f][nr][pb], acc[g][nr], 0, 0, 0);
                     }
-            constexpr int NMF = 12 * NR, NA = 8, NB = 6 * NR;
-            int done = 0;
-#pragma unroll
-            for (int m = 0; m < NMF; ++m) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                const int upto = (m + 1) * (NA + NB) / NMF;
-                for (; done < upto; ++done) {
-                    if (done < NA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-            }
+            pin_loads<12 * NR, 8, 6 * NR>();
         }
     }
 
@@ -593,7 +544,7 @@ __global__ __launch_bounds__(T::THREADS, 2) void convt_x3_k(ConvArgs a) {
         } else if constexpr (!T::STAGED) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = mblk * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int co = acc_row(r, lh, mblk * 32);
                 const float bv = a.bias[co];
                 *reinterpret_cast<float2*>(yb + (long)co * Lout + 2l * q) = make_float2(acc[0][nr][r] + bv, acc[1][nr][r] + bv);
             }
@@ -611,7 +562,7 @@ __global__ __launch_bounds__(T::THREADS, 2) void convt_x3_k(ConvArgs a) {
             const int ql = wn * (N1 / WN) + nr * 32 + l31;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int col = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int col = acc_row(r, lh, wm * 32);
                 const float bv = a.bias[blockIdx.y * T::MT + col];
                 *reinterpret_cast<float2*>(fs + col * FS + 2 * ql) = make_float2(acc[0][nr][r] + bv, acc[1][nr][r] + bv);
             }
@@ -656,32 +607,14 @@ bool convt_x3_supported(int Cin, int Cout, int K, int stride, int pad_a, int L) 
 }
 size_t convt_x3_bytes(int Cin, int Cout, int stride) { return 2 * (size_t)4 * (Cin / 16) * (Cout * (stride / 2) / 32) * 1024; }
 
-// Haiku [K][Cout][Cin] fp32 -> [plane][g][m][ks][mblk][lane][8] bf16: row m' = mblk*32 + (lane & 31) = co*SH + ph, k = ks*16 + 8*(lane >> 5) + e = ci
+// Haiku [K][Cout][Cin] fp32 -> [plane][g][m][ks][mblk][lane][8] bf16 (x3_pack_fragments): row m' = co*SH + ph, k = ci
 void convt_x3_pack(const float* w_hk, int Cin, int Cout, int K, int stride, int pad_a, unsigned short* out) {
-    const int SH = stride / 2, MB = Cout * SH / 32, KSTEPS = Cin / 16;
-    const size_t plane = (size_t)4 * KSTEPS * MB * 512;  // elements
-    for (int gm = 0; gm < 4; ++gm)
-        for (int ks = 0; ks < KSTEPS; ++ks)
-            for (int mb = 0; mb < MB; ++mb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int mp = mb * 32 + (lane & 31), co = mp / SH, ph = mp % SH, g = gm >> 1, m = gm & 1;
-                        const int ci = ks * 16 + 8 * (lane >> 5) + e;
-                        const int j = stride * (g - 1 + m) + pad_a - (g * SH + ph);
-                        const float w = w_hk[((size_t)j * Cout + co) * Cin + ci];
-                        unsigned u;
-                        memcpy(&u, &w, 4);
-                        const unsigned uh = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-                        float hi;
-                        memcpy(&hi, &uh, 4);
-                        const float lo = w - hi;
-                        unsigned ul;
-                        memcpy(&ul, &lo, 4);
-                        ul = (ul + 0x7fffu + ((ul >> 16) & 1u)) >> 16;
-                        const size_t o = ((((size_t)gm * KSTEPS + ks) * MB + mb) * 64 + lane) * 8 + e;
-                        out[o] = (unsigned short)(uh >> 16);
-                        out[plane + o] = (unsigned short)ul;
-                    }
+    const int SH = stride / 2;
+    x3_pack_fragments(4, Cin / 16, Cout * SH / 32, out, [&](int gm, int mp, int ci) {
+        const int co = mp / SH, ph = mp % SH, g = gm >> 1, m = gm & 1;
+        const int j = stride * (g - 1 + m) + pad_a - (g * SH + ph);
+        return w_hk[((size_t)j * Cout + co) * Cin + ci];
+    });
 }
 
 template <class T>
@@ -739,10 +672,6 @@ __global__ __launch_bounds__(PreX3::THREADS, 2) void conv_pre_x3_k(ConvArgs a) {
     if (t0 >= L) return;
     const float* __restrict__ xb = a.x + (long)b * a.x_sb;  // [T][80]
     const float slope = a.slope_in;                           // 1 for conv_pre (identity); kept general
-    auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {
-        hi = pack_bf16x2(v0, v1);
-        lo = pack_bf16x2(v0 - bf16_lo(hi), v1 - bf16_hi(hi));
-    };
     // ---- mel tile: frames t0 - 3 .. t0 + N1 + 2 (zero outside the utterance), unit = (row, 8 bins): two float4 loads of a contiguous row ----
     for (int u = tid; u < ROWS * SPR; u += T::THREADS) {
         const int row = u / SPR, slot = u - row * SPR;
@@ -798,7 +727,8 @@ __global__ __launch_bounds__(PreX3::THREADS, 2) void conv_pre_x3_k(ConvArgs a) {
 #pragma unroll 1
     for (int s = 0; s < NSTEPS; ++s) {
         const int cur = s & 1;
-        // (the ring slot is a runtime parity here: 35 steps; both branches are the same code on swapped registers)
+        // (the ring slot is a runtime parity here: 35 steps; both branches are the same code on swapped registers.  The step is x3_common.h:
+        // x3_mma's — term, mr, nr — spelled out: the call compiles to other code in this kernel)
         if (cur == 0) {
             load_a(s + 1, 1);
             load_b(s + 1, 1);
@@ -831,7 +761,7 @@ __global__ __launch_bounds__(PreX3::THREADS, 2) void conv_pre_x3_k(ConvArgs a) {
             if (t >= L) continue;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = (wave * MR + mr) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int co = acc_row(r, lh, (wave * MR + mr) * 32);
                 yb[(long)co * LP + t] = acc[mr][nr][r] + a.bias[co];
             }
         }
@@ -840,30 +770,10 @@ __global__ __launch_bounds__(PreX3::THREADS, 2) void conv_pre_x3_k(ConvArgs a) {
 bool conv_pre_x3_supported(int Cin, int Cout, int K, int dil) { return Cin == PreX3::CIN && Cout == PreX3::COUT && K == PreX3::KS && dil == 1; }
 size_t conv_pre_x3_bytes() { return 2 * PreX3::PLANE_W; }
 
-// Haiku [K][Cin][Cout] fp32 -> [plane][tap][ks][mblk][lane][8] bf16: row m = mblk*32 + (lane & 31) = co, k = ks*16 + 8*(lane >> 5) + e = ci
+// Haiku [K][Cin][Cout] fp32 -> [plane][tap][ks][mblk][lane][8] bf16 (x3_pack_fragments): row m = co, k = ci
 void conv_pre_x3_pack(const float* w_hk, unsigned short* out) {
     using T = PreX3;
-    const size_t plane = T::PLANE_W / 2;  // elements
-    for (int tap = 0; tap < T::KS; ++tap)
-        for (int ks = 0; ks < T::KSTEPS; ++ks)
-            for (int mb = 0; mb < T::MB; ++mb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int co = mb * 32 + (lane & 31), ci = ks * 16 + 8 * (lane >> 5) + e;
-                        const float w = w_hk[((size_t)tap * T::CIN + ci) * T::COUT + co];
-                        unsigned u;
-                        memcpy(&u, &w, 4);
-                        const unsigned uh = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-                        float hi;
-                        memcpy(&hi, &uh, 4);
-                        const float lo = w - hi;
-                        unsigned ul;
-                        memcpy(&ul, &lo, 4);
-                        ul = (ul + 0x7fffu + ((ul >> 16) & 1u)) >> 16;
-                        const size_t o = ((((size_t)tap * T::KSTEPS + ks) * T::MB + mb) * 64 + lane) * 8 + e;
-                        out[o] = (unsigned short)(uh >> 16);
-                        out[plane + o] = (unsigned short)ul;
-                    }
+    x3_pack_fragments(T::KS, T::KSTEPS, T::MB, out, [&](int tap, int co, int ci) { return w_hk[((size_t)tap * T::CIN + ci) * T::COUT + co]; });
 }
 
 // a.x = mel [B][L][80] (a.x_sb = batch stride), a.y [B][512][L], a.wp = conv_pre_x3_pack's output, a.bias [512]

@@ -20,9 +20,9 @@
 //     four waves per CU on 512-step windows, one's staging / epilogues (VALU + memory) under the other's MFMA loops (the first cut — four planes,
 //     one 8-wave workgroup per CU, every phase workgroup-wide — measured 3.72 / 6.02 / 8.75 ms per C = 32 ResBlock at k = 3 / 7 / 11);
 //   * staging transposes: lane <-> time step (a wave reads 64 consecutive floats of one channel), 8 channels per unit, LeakyReLU, split, two
-//     16-byte LDS writes (kernels_x3.hip: stage_x);
-//   * MFMA loops: kernels_x3.hip's — per k-step A fragments hi / lo by buffer loads through a register ring, B fragments hi / lo one k-step ahead,
-//     three MFMAs per operand pair, small terms first, look-ahead loads pinned between the MFMAs;
+//     16-byte LDS writes (x3_common.h: put_block_split — the tile is staged from the residual registers, in the accumulator layout);
+//   * MFMA loops: resblock_pair_x3_k's — per k-step A fragments hi / lo by buffer loads through a register ring, B fragments hi / lo one k-step ahead,
+//     three MFMAs per operand pair (x3_common.h: x3_mma), look-ahead loads pinned between the MFMAs (bf16_common.h: pin_loads);
 //   * rows whose dependency cone left the window are garbage after each convolution; the margin grows to M = H * (d0 + d1 + d2) + 3 H per side
 //     (12 / 36 / 60 for k = 3 / 7 / 11); only the W - 2 M centre rows are stored;
 //   * zero padding: every convolution of the reference pads ITS input with zeros outside [0, L): every tile write masks rows outside the
@@ -30,19 +30,17 @@
 // Arithmetic: the SAME sequence of operations per output element as three launches of resblock_pair_x3_k (the bias is the C operand of every
 // block's first MFMA in BOTH kernels — the accumulators start from it, nothing is added afterwards —, k-steps in tap-major order, the three terms
 // in the same order, fp32 residual add, the same masks) — the results are BIT-IDENTICAL to the pair path
-// (tests/test_gpu_x3.py::test_x3_whole_resblock_equals_the_pair_path), so every parity test of the split engine covers this kernel.
+// (tests/test_gpu_x3.py::test_x3_whole_resblock_equals_the_pair_path), so every parity test of the split engine covers this kernel.  The pieces
+// the two kernels must share are one definition each: x3_common.h states the contract.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <type_traits>
 
-#include "bf16_common.h"
-#include "device_common.h"
+#include "x3_common.h"
 
 namespace vtts {
-
-constexpr int RX_XCD_MIN_TILES = 64;
 
 struct RbArgsX3 {
     ConvArgs a;            // x (stage input, raw), y (ResBlock output / MRF accumulator), B, L, lens / len_mul, slope_in, acc_mode, div, zrev
@@ -105,12 +103,8 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
     const int d0 = p.dils[0], d1 = p.dils[1], d2 = p.dils[2];
     const int M = H * (d0 + d1 + d2) + 3 * H;  // invalid margin per side after the three pairs
     const int NT = W - 2 * M;                  // outputs per workgroup
-    int tile = blockIdx.x;
-    if (gridDim.x >= RX_XCD_MIN_TILES) {  // XCD-aware tile order: XCD blockIdx.x % 8 takes a contiguous, balanced eighth of the utterance's valid windows
-        const int nt = (L + NT - 1) / NT, r = (int)((blockIdx.x + blockIdx.z) & 7), lo = (r * nt) >> 3, hi = ((r + 1) * nt) >> 3;
-        tile = lo + (int)(blockIdx.x >> 3);
-        if (tile >= hi) return;
-    }
+    int tile;  // XCD-aware tile order (device_common.h): a contiguous, balanced eighth of the utterance's valid windows per XCD
+    if (!xcd_tile(L, NT, tile)) return;
     const int t0 = tile * NT;  // first output time step
     if (t0 >= L) return;
     // (A start-up skew of the launch's second batch of workgroups — so that the two workgroups of a CU alternate MFMA loops and epilogues — was
@@ -128,18 +122,8 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
     const int cb0 = wm * (C / T::WM);  // this wave's first output channel
     const float slope = a.slope_in;    // LRELU_SLOPE, both activations of every pair (model.py:46,48)
 
-    auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {  // two bf16 terms of two fp32 values (kernels_x3.hip)
-        hi = pack_bf16x2(v0, v1);
-        lo = pack_bf16x2(v0 - bf16_lo(hi), v1 - bf16_hi(hi));
-    };
-    auto swap_pair = [](unsigned& pd, unsigned& qd) {
-        auto r = __builtin_amdgcn_permlane32_swap(pd, qd, false, false);
-        pd = r[0];
-        qd = r[1];
-    };
-
-    // ---- the running x of this lane's outputs, fp32, in the accumulator layout: column n = col0 + 32 nr (time tw + n), channel cb0 + 32 mr +
-    //      (r & 3) + 8 (r >> 2) + 4 lh; a half-wave reads 32 consecutive floats of one channel.  The waves' (channel block, column range) tiles cover
+    // ---- the running x of this lane's outputs, fp32, in the accumulator layout: column n = col0 + 32 nr (time tw + n), channel
+    //      acc_row(r, lh, cb0 + 32 mr); a half-wave reads 32 consecutive floats of one channel.  The waves' (channel block, column range) tiles cover
     //      the window exactly once, so these registers are also what the tile is STAGED from (write_tile below: the first cut read x twice) ----
     const int col0 = wn * (W / WN) + l31;
     float xr[MR][NR][16];
@@ -151,7 +135,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) xr[mr][nr][r] = xb[(long)(cb0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tw + col0 + nr * 32];
+                for (int r = 0; r < 16; ++r) xr[mr][nr][r] = xb[(long)acc_row(r, lh, cb0 + mr * 32) * LP + tw + col0 + nr * 32];
     } else {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr)
@@ -162,7 +146,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
                 const int tc = t < 0 ? 0 : (t >= L ? L - 1 : t);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float v = xb[(long)(cb0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tc];
+                    const float v = xb[(long)acc_row(r, lh, cb0 + mr * 32) * LP + tc];
                     xr[mr][nr][r] = ok ? v : 0.0f;
                 }
             }
@@ -201,7 +185,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
 
     // The accumulators START FROM THE BIAS: the very first MFMA of every 32 x 32 block takes a 16-register bias block (read from the LDS copy) as its C
     // operand — no accumulator initialisation (64 v_mov per convolution and wave) and no bias add in the epilogues (64 more), on a kernel whose epilogues
-    // are VALU-bound.  resblock_pair_x3_k starts its accumulators from the same values (kernels_x3.hip: init_acc), so the two stay bit-identical.
+    // are VALU-bound.  resblock_pair_x3_k starts its accumulators from the same values (its init_acc, kernels_x3.hip), so the two stay bit-identical.
     auto conv_phase = [&](auto nks_tag, const float* __restrict__ bias_lds, const void* __restrict__ w, const void* __restrict__ wnext, int dl, const unsigned char* __restrict__ thi, const unsigned char* __restrict__ tlo) {
         constexpr int NKS = decltype(nks_tag)::value;  // k-steps per channel chunk: flat step s = (chunk * KS + tap) * NKS + i  <->  k-step chunk * NKS + i of tap `tap`
         f32x16 bblk[MR];
@@ -248,32 +232,8 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
                 load_a(s0 + i + PA, (i + PA) % RA);
                 load_b(s0 + i + 1, (i + 1) & 1);
                 const int sl = i % RA, par = i & 1;
-                // small terms first (the order of resblock_pair_x3_k: bit-identical sums)
-#pragma unroll
-                for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-                    for (int nr = 0; nr < NR; ++nr)
-                        acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][mr][1], bf[par][nr][0], (FIRST && i == 0) ? bblk[mr] : acc[mr][nr], 0, 0, 0);
-#pragma unroll
-                for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][mr][0], bf[par][nr][1], acc[mr][nr], 0, 0, 0);
-#pragma unroll
-                for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-                    for (int nr = 0; nr < NR; ++nr) acc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[sl][mr][0], bf[par][nr][0], acc[mr][nr], 0, 0, 0);
-                // keep hipcc from sinking the look-ahead loads to their uses; spread them between this step's MFMAs (kernels_x3.hip)
-                constexpr int NMF = 3 * MR * NR, NA = 2 * MR, NB = 2 * NR;
-                int done = 0;
-#pragma unroll
-                for (int m = 0; m < NMF; ++m) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    const int upto = (m + 1) * (NA + NB) / NMF;
-                    for (; done < upto; ++done) {
-                        if (done < NA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                        else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                }
+                x3_mma(acc, af[sl], bf[par], (FIRST && i == 0) ? bblk : nullptr);
+                pin_loads<3 * MR * NR, 2 * MR, 2 * NR>();
             }
         };
         tap_iter(0, std::true_type{});
@@ -286,20 +246,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
     auto write_tile = [&](unsigned char* thi, unsigned char* tlo, int mr, int nr, const float (&v)[16]) {
         const int row = GUARD + col0 + nr * 32;
 #pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            unsigned hp0, hp1, hq0, hq1, lp0, lp1, lq0, lq1;
-            split2(v[8 * pp + 0], v[8 * pp + 1], hp0, lp0);
-            split2(v[8 * pp + 2], v[8 * pp + 3], hp1, lp1);
-            split2(v[8 * pp + 4], v[8 * pp + 5], hq0, lq0);
-            split2(v[8 * pp + 6], v[8 * pp + 7], hq1, lq1);
-            swap_pair(hp0, hq0);
-            swap_pair(hp1, hq1);
-            swap_pair(lp0, lq0);
-            swap_pair(lp1, lq1);
-            const int off = tile_off<SPR>(row, ((cb0 + mr * 32 + 16 * pp) >> 3) + lh);
-            *reinterpret_cast<uint4*>(thi + off) = make_uint4(hp0, hp1, hq0, hq1);
-            *reinterpret_cast<uint4*>(tlo + off) = make_uint4(lp0, lp1, lq0, lq1);
-        }
+        for (int pp = 0; pp < 2; ++pp) put_block_split<SPR>(thi, tlo, row, ((cb0 + mr * 32 + 16 * pp) >> 3) + lh, v + 8 * pp);
     };
 
     // ---- stage the tile = lrelu(x) from the residual registers (zero outside the utterance: xr is) ----
@@ -398,7 +345,7 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) fs[(cb0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * FS + col0 + nr * 32] = xr[mr][nr][r];
+                for (int r = 0; r < 16; ++r) fs[acc_row(r, lh, cb0 + mr * 32) * FS + col0 + nr * 32] = xr[mr][nr][r];
         __syncthreads();
         const int NT4 = NT / 4, total = C * NT4;
         constexpr int UB = 4;  // 16-byte units per round trip: the accumulator's values of a batch are requested before its first store (y may alias nothing else, but the compiler cannot know)
@@ -441,13 +388,13 @@ __global__ __launch_bounds__(T::THREADS, T::WPS) void resblock_x3_k(RbArgsX3 p) 
             const int tc = ok ? t : 0;
             float yv[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) yv[r] = mode != ACC_STORE ? yb[(long)(cb0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tc] : 0.0f;
+            for (int r = 0; r < 16; ++r) yv[r] = mode != ACC_STORE ? yb[(long)acc_row(r, lh, cb0 + mr * 32) * LP + tc] : 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = xr[mr][nr][r];
                 if (mode == ACC_ADD) v = yv[r] + v;
                 else if (mode == ACC_MEAN) v = (yv[r] + v) / dv;
-                if (ok) yb[(long)(cb0 + mr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LP + tc] = v;
+                if (ok) yb[(long)acc_row(r, lh, cb0 + mr * 32) * LP + tc] = v;
             }
         }
     RX_TL(22);
@@ -481,8 +428,7 @@ static hipError_t launch_rx(const RbArgsX3& p, hipStream_t s) {
     }
     const int NT = T::W - 2 * (T::H * dsum + 3 * T::H);
     if (NT < 32) return hipErrorInvalidValue;
-    dim3 grid((p.a.L + NT - 1) / NT, 1, p.a.B);
-    if ((int)grid.x >= RX_XCD_MIN_TILES) grid.x = (grid.x + 7) / 8 * 8;
+    dim3 grid(xcd_grid_x((p.a.L + NT - 1) / NT), 1, p.a.B);
     hipLaunchKernelGGL(resblock_x3_k<T>, grid, dim3(T::THREADS), T::LDS_BYTES, s, p);
     return hipGetLastError();
 }
@@ -507,58 +453,49 @@ hipError_t launch_resblock_x3(const ConvArgs& a, const int* dils, const void* co
     RbArgsX3 p;
     p.a = a;
     p.dbg = nullptr;
-#if VTTS_TIMELINE  // kernel-development builds only (--define VTTS_TIMELINE=1; tools/rx_timeline.py): not in the shipped library
-    static const char* const tl = getenv("VTTS_RX_TL");  // read once
-    if (tl) {  // kernel-development: stamps of ONE class (VTTS_RX_TL_K, default 3; C = VTTS_RX_TL_C, default 32), last launch wins; dumped right away (synchronous)
-        const int kk = getenv("VTTS_RX_TL_K") ? atoi(getenv("VTTS_RX_TL_K")) : 3, cc = getenv("VTTS_RX_TL_C") ? atoi(getenv("VTTS_RX_TL_C")) : 32;
-        if (a.K == kk && a.Cin == cc && a.Cin <= 64) {
-            static unsigned long long* buf = nullptr;
-            static size_t buf_bytes = 0;
-            const size_t nwg = (size_t)((a.L + 31) / 32 + 8) * a.B, bytes = nwg * 24 * 8;
-            if (bytes > buf_bytes) {  // a later launch of the class may be larger than the first
-                if (buf) (void)hipFree(buf);
-                buf_bytes = hipMalloc(&buf, bytes) == hipSuccess ? bytes : 0;
-                if (!buf_bytes) buf = nullptr;
-            }
-            if (buf) {
-                (void)hipMemsetAsync(buf, 0, bytes, s);
-                p.dbg = buf;
-                for (int i = 0; i < 3; ++i) p.dils[i] = dils[i];
-                for (int q = 0; q < 6; ++q) {
-                    p.w[q] = w[q];
-                    p.bias[q] = bias[q];
-                }
-                hipError_t e = a.Cin == 32 ? (a.K == 3 ? launch_rx<RX32<3>>(p, s) : a.K == 7 ? launch_rx<RX32<7>>(p, s) : launch_rx<RX32<11>>(p, s))
-                                           : (a.K == 3 ? launch_rx<RX64<3>>(p, s) : launch_rx<RX64<7>>(p, s));
-                (void)hipStreamSynchronize(s);
-                unsigned long long* host = (unsigned long long*)malloc(bytes);
-                (void)hipMemcpy(host, buf, bytes, hipMemcpyDeviceToHost);
-                if (FILE* f = fopen(tl, "wb")) {
-                    fwrite(host, 1, bytes, f);
-                    fclose(f);
-                }
-                free(host);
-                return e;
-            }
-        }
-    }
-#endif
     for (int i = 0; i < 3; ++i) p.dils[i] = dils[i];
     for (int q = 0; q < 6; ++q) {
         p.w[q] = w[q];
         p.bias[q] = bias[q];
     }
-    if (a.Cin == 32) switch (a.K) {
-            case 3: return launch_rx<RX32<3>>(p, s);
-            case 7: return launch_rx<RX32<7>>(p, s);
-            case 11: return launch_rx<RX32<11>>(p, s);
+#if VTTS_TIMELINE  // kernel-development builds only (--define VTTS_TIMELINE=1; tools/rx_timeline.py): not in the shipped library
+    // stamps of ONE class (VTTS_RX_TL_K, default 3; C = VTTS_RX_TL_C, default 32), last launch wins; dumped right away (synchronous)
+    static const char* const tl = getenv("VTTS_RX_TL");  // read once
+    static unsigned long long* buf = nullptr;
+    static size_t buf_bytes = 0;
+    const size_t bytes = (size_t)((a.L + 31) / 32 + 8) * a.B * 24 * 8;
+    if (tl && a.K == (getenv("VTTS_RX_TL_K") ? atoi(getenv("VTTS_RX_TL_K")) : 3) && a.Cin == (getenv("VTTS_RX_TL_C") ? atoi(getenv("VTTS_RX_TL_C")) : 32) && a.Cin <= 64) {
+        if (bytes > buf_bytes) {  // a later launch of the class may be larger than the first
+            if (buf) (void)hipFree(buf);
+            buf_bytes = hipMalloc(&buf, bytes) == hipSuccess ? bytes : 0;
+            if (!buf_bytes) buf = nullptr;
         }
-    if (a.Cin == 64) switch (a.K) {
-            case 3: return launch_rx<RX64<3>>(p, s);
-            case 7: return launch_rx<RX64<7>>(p, s);
+        if (buf) {
+            (void)hipMemsetAsync(buf, 0, bytes, s);
+            p.dbg = buf;
         }
-    if (a.Cin == 128 && a.K == 3) return launch_rx<RX128<3>>(p, s);
-    return hipErrorInvalidValue;
+    }
+#endif
+    hipError_t e = hipErrorInvalidValue;
+    if (a.Cin == 32 && a.K == 3) e = launch_rx<RX32<3>>(p, s);
+    else if (a.Cin == 32 && a.K == 7) e = launch_rx<RX32<7>>(p, s);
+    else if (a.Cin == 32 && a.K == 11) e = launch_rx<RX32<11>>(p, s);
+    else if (a.Cin == 64 && a.K == 3) e = launch_rx<RX64<3>>(p, s);
+    else if (a.Cin == 64 && a.K == 7) e = launch_rx<RX64<7>>(p, s);
+    else if (a.Cin == 128 && a.K == 3) e = launch_rx<RX128<3>>(p, s);
+#if VTTS_TIMELINE
+    if (p.dbg) {
+        (void)hipStreamSynchronize(s);
+        unsigned long long* host = (unsigned long long*)malloc(bytes);
+        (void)hipMemcpy(host, p.dbg, bytes, hipMemcpyDeviceToHost);
+        if (FILE* f = fopen(tl, "wb")) {
+            fwrite(host, 1, bytes, f);
+            fclose(f);
+        }
+        free(host);
+    }
+#endif
+    return e;
 }
 
 }  // namespace vtts

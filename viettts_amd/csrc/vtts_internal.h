@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/vtts_hifigan.h"
 
@@ -23,6 +24,27 @@ int failf(int code, const char* fmt, ...);
     } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// fp32 -> bf16 bits, round-to-nearest-even (what v_cvt_pk_bf16_f32 gives), and back
+inline unsigned short f32_to_bf16_rne(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);  // NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (unsigned short)(u >> 16);
+}
+inline float bf16_to_f32(unsigned short h) {
+    const uint32_t u = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+// The split-operand engine's two bf16 terms of a weight, w = hi + lo to 16 significand bits: the host form of bf16_common.h: split2
+// (w - float(hi) is exact in fp32)
+inline void split_bf16(float w, unsigned short& hi, unsigned short& lo) {
+    hi = f32_to_bf16_rne(w);
+    lo = f32_to_bf16_rne(w - bf16_to_f32(hi));
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON A DEVICE: a process that drives several GPUs (a
 // second Generator on cuda:1 after cuda:0) must set it once per device, not once per process.  `done` = the caller's static
