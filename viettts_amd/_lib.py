@@ -128,6 +128,25 @@ DISC_MIN_SAMPLES = 11
 DISC_LOSS_REAL, DISC_LOSS_FAKE, DISC_LOSS_GEN, DISC_LOSS_TOTALS, DISC_LOSS_RESULTS = 54, 62, 70, 78, 128
 DISC_LOSS_FLOATS = DISC_LOSS_RESULTS + 2 * (DISC_NUM_FMAPS + 3 * DISC_NUM_DISCS) * 64
 
+# Every symbol include/vtts_audio.h declares.
+AUDIO_EXPORTS = (
+    "vtts_audio_create",
+    "vtts_audio_destroy",
+    "vtts_audio_ratio",
+    "vtts_audio_out_samples",
+    "vtts_audio_prototype",
+    "vtts_audio_packed_bytes",
+    "vtts_audio_pack",
+    "vtts_audio_bind_packed",
+    "vtts_audio_forward",
+)
+VTTS_AUDIO_F32 = 0
+VTTS_AUDIO_PCM16 = 1
+AUDIO_OUT_PER_BLOCK = 1024  # include/vtts_audio.h: VTTS_AUDIO_OUT_PER_BLOCK
+AUDIO_ZEROS = 24  # include/vtts_audio.h: VTTS_AUDIO_ZEROS
+AUDIO_BETA = 10.0  # include/vtts_audio.h: VTTS_AUDIO_BETA
+AUDIO_MAX_R = 2048  # include/vtts_audio.h: VTTS_AUDIO_MAX_R
+
 VTTS_MEL_F32 = 0
 VTTS_MEL_PCM16 = 1
 MEL_FRAMES_PER_BLOCK = 8  # include/vtts_mel.h: VTTS_MEL_FRAMES_PER_BLOCK
@@ -136,6 +155,10 @@ MEL_MIN_SAMPLES = 385  # include/vtts_mel.h: VTTS_MEL_MIN_SAMPLES
 
 class MelCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
+
+
+class AudioCfg(C.Structure):
+    _fields_ = [("in_rate", C.c_int32), ("out_rate", C.c_int32)]
 
 
 class NatDurationCfg(C.Structure):
@@ -287,6 +310,15 @@ def load(path=None) -> C.CDLL:
         "vtts_mel_bind_packed": (C.c_int, [vp, vp, sz]),
         "vtts_mel_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
         "vtts_mel_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, i64, vp, vp]),
+        "vtts_audio_create": (C.c_int, [C.POINTER(AudioCfg), C.c_int, C.POINTER(vp)]),
+        "vtts_audio_destroy": (None, [vp]),
+        "vtts_audio_ratio": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "vtts_audio_out_samples": (C.c_int, [vp, i64, C.POINTER(i64)]),
+        "vtts_audio_prototype": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "vtts_audio_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+        "vtts_audio_pack": (C.c_int, [vp, vp, sz, vp]),
+        "vtts_audio_bind_packed": (C.c_int, [vp, vp, sz]),
+        "vtts_audio_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, C.c_int, i64, vp]),
         "vtts_disc_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
         "vtts_disc_destroy": (None, [vp]),
         "vtts_disc_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),

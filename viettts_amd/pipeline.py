@@ -83,8 +83,10 @@ def _copy_stream(device: torch.device):
 
 def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, acoustic_model, generator, silence_duration: float = -1.0,
                          dropout_seed: Optional[int] = 0, rank: int = 0, world: int = 1, gen_batch: int = 0,
-                         timing: Optional[dict] = None) -> Dict[int, np.ndarray]:
-    """Waveforms (float32, 16 kHz samples) of THIS rank's sentences, keyed by sentence index.  ``timing`` (a dict) receives
+                         timing: Optional[dict] = None, out_dtype: str = "f32", out_rate: Optional[int] = None) -> Dict[int, np.ndarray]:
+    """Waveforms (float32, 16 kHz samples) of THIS rank's sentences, keyed by sentence index.  ``out_dtype="pcm16"`` returns int16
+    arrays equal to ``wavio.float_to_pcm16`` of the default's, and ``out_rate`` samples at that rate: each pass is then converted
+    (``viettts_amd.audio.Resampler``) and packed on the device, and only the packed samples are read back.  ``timing`` (a dict) receives
     wall seconds per stage.  The stages run one after the other on the caller's stream; a pass's waveforms leave for pinned host memory
     on a copy stream while the next pass computes.  Masks are seeded by the GLOBAL sentence index and every stage computes a row
     independently of its batch, so the samples depend neither on the shard nor on the batch (tests/test_gpu_nat.py: bit-identical to each
@@ -101,6 +103,9 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
         timing[name] = timing.get(name, 0.0) + now - t_prev
         return now
 
+    if out_dtype not in ("f32", "pcm16"):
+        raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
+    convert = out_dtype != "f32" or (out_rate is not None and int(out_rate) != t2m.FLAGS.sample_rate)
     mine = shard_utterances([len(t) for t in token_lists], world)[rank]
     if not mine:
         return {}
@@ -172,6 +177,14 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
                 batch = torch.nn.functional.pad(batch, (0, 0, 0, Ts - batch.shape[1]))
             batch = batch.contiguous()
             w = generator.forward_ragged(batch, fr) if ragged else generator(batch)
+            counts = None
+            if convert:  # format and rate on the device, the rows packed back to back: the read-back carries no slot padding
+                from .audio import resampler
+
+                rs = resampler(t2m.FLAGS.sample_rate, int(out_rate) if out_rate is not None else t2m.FLAGS.sample_rate, dev)
+                valid = [generator.hop * f for f in fr]
+                counts = rs.out_lengths(valid)
+                w = rs(w, lengths=valid, out_dtype=out_dtype, packed=True)
             # pinned, on a copy stream: the next pass computes while this one's samples leave
             done = torch.cuda.Event()
             done.record(cur)
@@ -186,13 +199,18 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
                 with torch.cuda.stream(s_copy):
                     host.copy_(w, non_blocking=True)
                 w.record_stream(s_copy)
-            pending.append((rows, fr, host))
+            pending.append((rows, fr, host, counts))
         cur.wait_stream(s_copy)
         torch.cuda.synchronize()
-        for rows, fr, host in pending:
+        for rows, fr, host, counts in pending:
             hn = host.numpy()
+            at = 0
             for q, r in enumerate(rows):
-                wavs[mine[ok[r]]] = hn[q, : generator.hop * fr[q]]  # a view of the batch's pinned buffer (kept alive by the view)
+                if counts is None:
+                    wavs[mine[ok[r]]] = hn[q, : generator.hop * fr[q]]  # a view of the batch's pinned buffer (kept alive by the view)
+                else:
+                    wavs[mine[ok[r]]] = hn[at : at + counts[q]]
+                    at += counts[q]
     else:
         t_last = mark("acoustic_s", t_last)
     t_last = mark("generator_s", t_last)
@@ -202,5 +220,5 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
         timing["tokens"] = int(sum(len(t) for t in toks))
     for k in range(len(mine)):
         if mine[k] not in wavs:
-            wavs[mine[k]] = np.zeros((0,), np.float32)
+            wavs[mine[k]] = np.zeros((0,), np.int16 if out_dtype == "pcm16" else np.float32)
     return wavs

@@ -2,9 +2,10 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000]
 
-reads PCM16 mono, uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
+reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
+at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
 ``FileNotFoundError`` without them.
 """
 from __future__ import annotations
@@ -49,11 +50,19 @@ def wav2mel(wav, lengths=None, mel_filter: Optional[MelFilter] = None, device=No
     return mel_filter(_on_device(wav, mel_filter.device), lengths=lengths, out=out)
 
 
-def resynthesize(wav, generator, lengths=None, mel_filter: Optional[MelFilter] = None) -> torch.Tensor:
+def resynthesize(wav, generator, lengths=None, mel_filter: Optional[MelFilter] = None, in_rate: Optional[int] = None) -> torch.Tensor:
     """``generator.forward_ragged(MelFilter(wav), frames)``: ``[N, 256 * T]`` float32, row b's first ``256 * (lengths[b] // 256)``
-    samples valid and the rest zero."""
+    samples valid and the rest zero.  ``in_rate``: the rate of ``wav`` (and the unit of ``lengths``) when it is not the mel filter's;
+    the rows are converted on the GPU first, and ``T`` counts frames of the converted rows."""
     mf = mel_filter or default_mel_filter(generator.device)
     y = _on_device(wav, generator.device)
+    if in_rate is not None and int(in_rate) != mf.sample_rate:
+        from .audio import resampler
+
+        rs = resampler(int(in_rate), mf.sample_rate, generator.device)
+        y = rs(y, lengths=lengths)
+        if lengths is not None:
+            lengths = rs.out_lengths(lengths)
     mel = mf(y, lengths=lengths)
     lens = [y.shape[1]] * y.shape[0] if lengths is None else [int(v) for v in lengths]
     return generator.forward_ragged(mel, [mf.num_frames(n) for n in lens])
@@ -78,9 +87,10 @@ def log_mel_l1(a, b, lengths=None, mel_filter: Optional[MelFilter] = None) -> fl
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="wav -> log-mel -> wav through the HiFi-GAN generator on the GPU")
-    ap.add_argument("--input", required=True, help="PCM16 mono .wav at the model's sample rate")
+    ap.add_argument("--input", required=True, help="PCM16 mono .wav; any rate but the model's is converted on the GPU")
     ap.add_argument("--output", required=True)
     ap.add_argument("--dtype", default="f32", choices=("f32", "bf16", "bf16x3"))
+    ap.add_argument("--output-rate", type=int, default=None, help="convert the result to this rate on the GPU (default: the model's rate)")
     return ap
 
 
@@ -90,12 +100,22 @@ def main(argv=None) -> None:
     a = build_parser().parse_args(argv)
     gen = _generator(a.dtype)  # FileNotFoundError without config / checkpoint, before the input is touched
     sr, pcm = wavio.read_wav(a.input)
-    if sr != NAT_FLAGS.sample_rate:
-        raise ValueError(f"{a.input}: {sr} Hz, the model runs at {NAT_FLAGS.sample_rate} Hz")
-    wav = resynthesize(pcm.astype(np.int16)[None, :], gen)
-    n = 256 * (len(pcm) // 256)
-    wavio.write_wav(a.output, wav[0, :n].cpu().numpy(), sr)
-    print(f"wrote {a.output}: {n} samples, log-mel L1 against the input {log_mel_l1(wav[:, :n], pcm[None, :n].astype(np.int16)):.4f}")
+    model_rate = NAT_FLAGS.sample_rate
+    y = _on_device(pcm.astype(np.int16)[None, :], gen.device)
+    if sr != model_rate:
+        from .audio import resampler
+
+        y = resampler(sr, model_rate, gen.device)(y)
+    wav = resynthesize(y, gen)
+    n = 256 * (y.shape[1] // 256)
+    if a.output_rate is None or a.output_rate == model_rate:
+        wavio.write_wav(a.output, wav[0, :n].cpu().numpy(), model_rate)
+    else:
+        from .audio import resampler
+
+        out = resampler(model_rate, a.output_rate, gen.device)(wav[0, :n].contiguous(), out_dtype="pcm16")
+        wavio.write_wav_pcm16(a.output, out.cpu().numpy(), a.output_rate)
+    print(f"wrote {a.output}: {n} samples, log-mel L1 against the input {log_mel_l1(wav[:, :n], y[:, :n].contiguous()):.4f}")
 
 
 if __name__ == "__main__":

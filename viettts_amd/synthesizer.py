@@ -6,7 +6,8 @@ reference runs the whole pipeline at import time).  One 
 ``--mel-file`` synthesises from a saved ``[T, 80]`` / ``[1, T, 80]`` float32 mel (.npy) so the
 mel->waveform path can be driven on its own (the text path runs the NAT duration and acoustic models of
 ``viettts_amd/nat`` like the reference's), and ``--low-latency`` runs the acoustic decoder's frame loop as one resident kernel
-(``viettts_amd.nat.text2mel.set_low_latency``).
+(``viettts_amd.nat.text2mel.set_low_latency``), and ``--resample`` makes ``--sample-rate R`` a conversion to R on the GPU
+(``viettts_amd.audio.Resampler``) where the reference, and this CLI without the flag, only label the 16 kHz samples with R.
 
     python -m viettts_amd.synthesizer --text "..." --output clip.wav --lexicon-file assets/infore/lexicon.txt
 """
@@ -48,13 +49,14 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--lexicon-file", default=None)
     p.add_argument("--mel-file", default=None, type=Path, help="(extension) synthesise from a saved mel instead of text")
     p.add_argument("--low-latency", action="store_true", help="(extension) run the acoustic decoder's frame loop as one resident kernel")
+    p.add_argument("--resample", action="store_true", help="(extension) convert the samples to --sample-rate on the GPU instead of relabelling them")
     return p
 
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     from .hifigan.mel2wave import mel2wave
-    from .wavio import write_wav
+    from .wavio import write_wav, write_wav_pcm16
 
     if args.mel_file is not None:
         mel = np.load(args.mel_file).astype(np.float32)
@@ -72,7 +74,14 @@ def main(argv=None) -> int:
         mel = text2mel(text, args.lexicon_file, args.silence_duration)
     wave = mel2wave(mel)
     print("writing output to file", args.output)
-    write_wav(args.output, wave, args.sample_rate)
+    if args.resample and args.sample_rate != FLAGS.sample_rate:
+        from .audio import Resampler
+
+        rs = Resampler(FLAGS.sample_rate, args.sample_rate, "cuda")
+        write_wav_pcm16(args.output, rs(np.asarray(wave, dtype=np.float32), out_dtype="pcm16").cpu().numpy(), args.sample_rate)
+        rs.close()
+    else:
+        write_wav(args.output, wave, args.sample_rate)
     return 0
 
 

@@ -4,7 +4,8 @@
     python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192]
 
 prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
-MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono at the model's sample rate, the
+MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono (any rate but the model's is converted
+on the GPU first: ``viettts_amd.audio.Resampler``), the
 generator as ``mel2wave`` reads it (``assets/hifigan/config.json`` + a Haiku pickle) and upstream's ``do_*`` file; raises
 ``FileNotFoundError`` without them, before any input is touched.  Forward only: nothing is trained.
 """
@@ -35,7 +36,7 @@ def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None) 
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="adversarial, feature-matching and mel terms of a HiFi-GAN checkpoint on the GPU")
-    ap.add_argument("--wav", nargs="+", required=True, help="PCM16 mono .wav files at the model's sample rate")
+    ap.add_argument("--wav", nargs="+", required=True, help="PCM16 mono .wav files; any rate but the model's is converted on the GPU")
     ap.add_argument("--generator", required=True, help="the generator's Haiku pickle (hk_hifi.pickle)")
     ap.add_argument("--discriminator", required=True, help="upstream's do_* checkpoint (keys mpd, msd)")
     ap.add_argument("--config", default="assets/hifigan/config.json")
@@ -66,8 +67,11 @@ def main(argv=None) -> None:
     for path in a.wav:
         sr, pcm = wavio.read_wav(path)
         if sr != NAT_FLAGS.sample_rate:
-            raise ValueError(f"{path}: {sr} Hz, the model runs at {NAT_FLAGS.sample_rate} Hz")
-        x = pcm.astype(np.float32) / 32768.0
+            from .audio import resampler
+
+            x = resampler(sr, NAT_FLAGS.sample_rate, dev)(pcm.astype(np.int16)).cpu().numpy()
+        else:
+            x = pcm.astype(np.float32) / 32768.0
         segs += [x[i : i + a.segment] for i in range(0, len(x) - a.segment + 1, a.segment)]
     if not segs:
         raise ValueError(f"no input holds a whole segment of {a.segment} samples")

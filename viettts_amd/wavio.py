@@ -30,6 +30,20 @@ def write_wav(path, wave: np.ndarray, samplerate: int) -> None:
         f.write(hdr + pcm)
 
 
+def write_wav_pcm16(path, pcm: np.ndarray, samplerate: int) -> None:
+    """The same file from samples that are PCM16 already (``viettts_amd.audio.to_pcm16``, or a resampler's ``out_dtype="pcm16"``)."""
+    pcm = np.asarray(pcm)
+    if pcm.ndim != 1 or pcm.dtype != np.int16:
+        raise ValueError("write_wav_pcm16 expects a mono 1-D int16 array")
+    data = pcm.astype("<i2", copy=False).tobytes()
+    n = len(data)
+    hdr = b"RIFF" + struct.pack("<I", 36 + n) + b"WAVE"
+    hdr += b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, int(samplerate), int(samplerate) * 2, 2, 16)
+    hdr += b"data" + struct.pack("<I", n)
+    with open(str(path), "wb") as f:
+        f.write(hdr + data)
+
+
 def read_wav(path):
     """(samplerate, int16 array) — for tests."""
     with open(str(path), "rb") as f:
