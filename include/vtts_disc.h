@@ -70,7 +70,8 @@ int vtts_disc_param_info(const vtts_disc* h, int i, const char** key, const char
 int vtts_disc_set_param(vtts_disc* h, const char* key, const char* which, const float* host, const int64_t* shape, int ndim);
 
 /* The weights in MFMA A-fragment order plus biases as one device blob, caller-owned and 256-B aligned: pack() copies it on the
- * stream and waits (VTTS_ERR_MISSING while a parameter was never set); bind_packed() adopts a blob another handle packed. */
+ * stream and waits (VTTS_ERR_MISSING while a parameter was never set); bind_packed() adopts a blob another handle packed.
+ * blob_bytes may exceed packed_bytes(), as for every other handle; a smaller blob is VTTS_ERR_NOMEM. */
 int vtts_disc_packed_bytes(const vtts_disc* h, size_t* bytes);
 int vtts_disc_pack(vtts_disc* h, void* dev_blob, size_t blob_bytes, void* stream);
 int vtts_disc_bind_packed(vtts_disc* h, void* dev_blob, size_t blob_bytes);

@@ -46,7 +46,8 @@ int vtts_nat_duration_num_params(const vtts_nat_duration* h, int* n);
 int vtts_nat_duration_param_info(const vtts_nat_duration* h, int i, const char** module, const char** name,
                                  int64_t shape[3], int* ndim);
 
-/* Packed device blob (caller-owned, 256-B aligned), as in vtts_hifigan.h. */
+/* Packed device blob (caller-owned, 256-B aligned), as in vtts_hifigan.h.  pack() and bind_packed() of both models refuse a misaligned
+ * blob with VTTS_ERR_INVALID, as every other handle does: the kernels read the blob as float4 / uint4. */
 int vtts_nat_duration_packed_bytes(const vtts_nat_duration* h, size_t* bytes);
 int vtts_nat_duration_pack(vtts_nat_duration* h, void* dev_blob, size_t blob_bytes, void* stream);
 int vtts_nat_duration_bind_packed(vtts_nat_duration* h, void* dev_blob, size_t blob_bytes);

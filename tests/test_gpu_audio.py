@@ -160,6 +160,25 @@ def test_ragged_packed_and_pcm_input_are_the_same_bits(rs, dev, rates):
         assert np.array_equal(_host(r(pcm, lengths=lengths, out_dtype="pcm16")), p_str)
 
 
+def test_an_adopted_blob_gives_the_same_bits(rs, dev):
+    """A second resampler that binds the first one's tap table (cloned) instead of packing its own."""
+    from viettts_amd.audio import Resampler
+
+    r = rs(16000, 44100)
+    lengths = [1, 1000]
+    x = torch.from_numpy(oracle.speechlike(np.random.default_rng(7), 2000).reshape(2, 1000)).to(dev)
+    want = r(x, lengths, out_dtype="pcm16", packed=True)
+    other = Resampler(16000, 44100, dev)
+    try:
+        other.adopt_packed(r.packed_blob().clone())
+        got = other(x, lengths, out_dtype="pcm16", packed=True)
+        torch.cuda.synchronize()
+        assert got.dtype == torch.int16 and got.shape == (sum(r.out_lengths(lengths)),) and got.numel() > 2000
+        assert torch.equal(got, want)
+    finally:
+        other.close()
+
+
 def test_indices_past_2_to_31(rs, dev):
     """One row of 13 500 000 samples at 160/441: m M passes 2^31 at output 4 869 579.  Three windows of 2 048 outputs (start, across
     the crossing, end) against the oracle's windowed evaluation, at the parity tests' bar."""

@@ -133,6 +133,26 @@ def test_rows_are_bit_identical_alone_and_in_any_batch(setup, T):
     assert torch.equal(r1.view(torch.int32), r2.view(torch.int32)) and torch.isfinite(r1).all()
 
 
+@pytest.mark.parametrize("T", [11, 37])
+def test_an_adopted_blob_gives_the_same_bits(setup, T):
+    """A second owner that binds the first one's packed weights (cloned) instead of loading its own: the raw buffers, bit for bit."""
+    from viettts_amd.hifigan.discriminators import Discriminators
+
+    d, _ = setup
+    y = oracle.make_inputs(1, T, SHAPES[T][1])[:1]
+    fb, sb = run_nan_filled(d, y)
+    other = Discriminators("cuda:0")
+    try:
+        other.adopt_packed(d.packed_blob().clone())
+        fb2, sb2 = run_nan_filled(other, y)
+        scores, fmaps = other.views(fb2, sb2, 1, T)
+        assert all(torch.isfinite(v).all() for v in [m for maps in fmaps for m in maps] + scores)
+        # the raw buffers as bits: the alignment gaps between the maps keep the NaN fill in both
+        assert torch.equal(fb2.view(torch.int32), fb.view(torch.int32)) and torch.equal(sb2.view(torch.int32), sb.view(torch.int32))
+    finally:
+        other.close()
+
+
 def test_reference_import_path(setup):
     """vietTTS.hifigan.torch_model's discriminators return the reference's four lists, and feature_loss of them is the kernel's number."""
     from vietTTS.hifigan import torch_model as tm

@@ -104,6 +104,27 @@ def test_ragged_rows_equal_the_rows_alone(mf, golden):
     assert err <= _bar(e32, want)
 
 
+def test_an_adopted_blob_gives_the_same_bits(mf, golden):
+    """A second filter that binds the first one's tables (cloned) instead of packing its own.  It names its device "cuda", the current
+    one, as a caller without an index in hand does."""
+    from viettts_amd.nat.dsp import MelFilter
+
+    lengths = [385, 1409]
+    y = torch.from_numpy(np.ascontiguousarray(golden["speech"][:2, :1409])).to(mf.device)
+    assert y.dtype == torch.float32
+    want = mf(y, lengths=lengths)
+    other = MelFilter(16000, 1024, 80, 0.0, 8000, device="cuda")
+    try:
+        assert other.device == mf.device
+        other.adopt_packed(mf.packed_blob().clone())
+        got = other(y, lengths=lengths)
+        torch.cuda.synchronize()
+        assert got.shape == (2, oracle.num_frames(1409), 80) and torch.isfinite(got).all()
+        assert torch.equal(got, want)
+    finally:
+        other.close()
+
+
 def _speechlike(rng, n_rows, S):
     t = np.arange(S) / 16000.0
     y = np.zeros((n_rows, S))

@@ -26,7 +26,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from viettts_amd import _lib  # noqa: E402
 from viettts_amd.nat.acoustic import AcousticModel  # noqa: E402
 from viettts_amd.nat.config import FLAGS  # noqa: E402
-from viettts_amd.nat.duration import _ptr  # noqa: E402
+from viettts_amd._handle import ptr  # noqa: E402
 from viettts_amd.nat.synth import synthetic_acoustic_checkpoint, synthetic_sentences  # noqa: E402
 
 RNG_KEY = np.array([0x1234ABCD, 0x0F1E2D3C], dtype=np.uint32)
@@ -73,14 +73,14 @@ class Operands:
 
 def call_forward(m, o):
     st = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
-    _lib.check(m.lib, m.lib.vtts_nat_acoustic_forward(m._h, _ptr(o.tok), _ptr(o.len), _ptr(o.dur), _ptr(o.nf), o.B, o.L, o.F, _ptr(o.keep), _ptr(o.out), _ptr(o.ws),
+    _lib.check(m.lib, m.lib.vtts_nat_acoustic_forward(m._h, ptr(o.tok), ptr(o.len), ptr(o.dur), ptr(o.nf), o.B, o.L, o.F, ptr(o.keep), ptr(o.out), ptr(o.ws),
                                                       o.ws.numel(), st))
 
 
 def call_teacher(m, o):
     st = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
-    _lib.check(m.lib, m.lib.vtts_nat_acoustic_forward_teacher(m._h, _ptr(o.tok), _ptr(o.len), _ptr(o.dur), _ptr(o.nf), o.B, o.L, o.F, _ptr(o.mels), _ptr(o.keep),
-                                                              _ptr(o.zone), _ptr(o.out), None, _ptr(o.ws), o.ws.numel(), st))
+    _lib.check(m.lib, m.lib.vtts_nat_acoustic_forward_teacher(m._h, ptr(o.tok), ptr(o.len), ptr(o.dur), ptr(o.nf), o.B, o.L, o.F, ptr(o.mels), ptr(o.keep),
+                                                              ptr(o.zone), ptr(o.out), None, ptr(o.ws), o.ws.numel(), st))
 
 
 def timed_ms(fn) -> float:

@@ -29,98 +29,6 @@ STATUS_NAMES = {
     -6: "VTTS_ERR_SHAPE",
 }
 
-# Every symbol include/vtts_hifigan.h declares (tests/test_cabi.py checks the header against this).
-EXPORTS = (
-    "vtts_abi_version",
-    "vtts_last_error",
-    "vtts_hifigan_create",
-    "vtts_hifigan_destroy",
-    "vtts_hifigan_set_param",
-    "vtts_hifigan_num_params",
-    "vtts_hifigan_param_info",
-    "vtts_hifigan_packed_bytes",
-    "vtts_hifigan_pack",
-    "vtts_hifigan_bind_packed",
-    "vtts_hifigan_workspace_bytes",
-    "vtts_hifigan_forward",
-    "vtts_hifigan_forward_ragged",
-    "vtts_hifigan_tap_elems",
-    "vtts_hifigan_forward_tap",
-    "vtts_hifigan_run_module",
-    "vtts_hifigan_run_pair",
-    "vtts_hifigan_set_option",
-    "vtts_hifigan_get_option",
-    "vtts_hifigan_profile_read",
-    "vtts_hifigan_profile_kernel",
-)
-
-
-# Every symbol include/vtts_nat.h declares.
-NAT_EXPORTS = (
-    "vtts_nat_duration_create",
-    "vtts_nat_duration_destroy",
-    "vtts_nat_duration_set_param",
-    "vtts_nat_duration_num_params",
-    "vtts_nat_duration_param_info",
-    "vtts_nat_duration_packed_bytes",
-    "vtts_nat_duration_pack",
-    "vtts_nat_duration_bind_packed",
-    "vtts_nat_duration_workspace_bytes",
-    "vtts_nat_duration_forward",
-    "vtts_nat_acoustic_forward_teacher_workspace_bytes",
-    "vtts_nat_acoustic_forward_teacher",
-    "vtts_nat_acoustic_teacher_masks_haiku",
-    "vtts_nat_acoustic_create",
-    "vtts_nat_acoustic_destroy",
-    "vtts_nat_acoustic_set_param",
-    "vtts_nat_acoustic_num_params",
-    "vtts_nat_acoustic_param_info",
-    "vtts_nat_acoustic_packed_bytes",
-    "vtts_nat_acoustic_pack",
-    "vtts_nat_acoustic_bind_packed",
-    "vtts_nat_acoustic_workspace_bytes",
-    "vtts_nat_acoustic_set_option",
-    "vtts_nat_acoustic_get_option",
-    "vtts_nat_acoustic_resident_status",
-    "vtts_nat_acoustic_keep_masks",
-    "vtts_nat_acoustic_keep_masks_haiku",
-    "vtts_nat_acoustic_keep_masks_haiku_mode",
-    "vtts_nat_acoustic_forward",
-    "vtts_nat_acoustic_forward_groups",
-    "vtts_nat_acoustic_wait_group",
-    "vtts_nat_acoustic_encode",
-    "vtts_nat_acoustic_forward_from_encoder",
-)
-
-# Every symbol include/vtts_mel.h declares.
-MEL_EXPORTS = (
-    "vtts_mel_create",
-    "vtts_mel_destroy",
-    "vtts_mel_num_frames",
-    "vtts_mel_filterbank",
-    "vtts_mel_packed_bytes",
-    "vtts_mel_pack",
-    "vtts_mel_bind_packed",
-    "vtts_mel_workspace_bytes",
-    "vtts_mel_forward",
-)
-
-# Every symbol include/vtts_disc.h declares.
-DISC_EXPORTS = (
-    "vtts_disc_create",
-    "vtts_disc_destroy",
-    "vtts_disc_num_params",
-    "vtts_disc_param_info",
-    "vtts_disc_set_param",
-    "vtts_disc_packed_bytes",
-    "vtts_disc_pack",
-    "vtts_disc_bind_packed",
-    "vtts_disc_workspace_bytes",
-    "vtts_disc_num_fmaps",
-    "vtts_disc_fmap_info",
-    "vtts_disc_forward",
-    "vtts_disc_losses",
-)
 # include/vtts_disc.h: the loss buffer's layout
 DISC_NUM_FMAPS = 54
 DISC_NUM_DISCS = 8
@@ -128,18 +36,6 @@ DISC_MIN_SAMPLES = 11
 DISC_LOSS_REAL, DISC_LOSS_FAKE, DISC_LOSS_GEN, DISC_LOSS_TOTALS, DISC_LOSS_RESULTS = 54, 62, 70, 78, 128
 DISC_LOSS_FLOATS = DISC_LOSS_RESULTS + 2 * (DISC_NUM_FMAPS + 3 * DISC_NUM_DISCS) * 64
 
-# Every symbol include/vtts_audio.h declares.
-AUDIO_EXPORTS = (
-    "vtts_audio_create",
-    "vtts_audio_destroy",
-    "vtts_audio_ratio",
-    "vtts_audio_out_samples",
-    "vtts_audio_prototype",
-    "vtts_audio_packed_bytes",
-    "vtts_audio_pack",
-    "vtts_audio_bind_packed",
-    "vtts_audio_forward",
-)
 VTTS_AUDIO_F32 = 0
 VTTS_AUDIO_PCM16 = 1
 AUDIO_OUT_PER_BLOCK = 1024  # include/vtts_audio.h: VTTS_AUDIO_OUT_PER_BLOCK
@@ -189,6 +85,100 @@ class CfgStruct(C.Structure):
         ("resblock_dilation_sizes", (C.c_int32 * 3) * MAX_KERNELS),
         ("resblock", C.c_int32),
     ]
+
+
+# shorthand for the prototype table below
+vp, cp, sz, i64 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int64
+fp = C.POINTER(C.c_float)
+
+
+def _handle_sigs(prefix: str, params: bool) -> dict:
+    """The prototypes every handle shares: its lifetime's end, the packed blob and (``params``) the checkpoint arrays it takes."""
+    sigs = {
+        "destroy": (None, [vp]),
+        "packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+        "pack": (C.c_int, [vp, vp, sz, vp]),
+        "bind_packed": (C.c_int, [vp, vp, sz]),
+    }
+    if params:
+        sigs["set_param"] = (C.c_int, [vp, cp, cp, vp, C.POINTER(i64), C.c_int])
+        sigs["num_params"] = (C.c_int, [vp, C.POINTER(C.c_int)])
+        sigs["param_info"] = (C.c_int, [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.POINTER(i64), C.POINTER(C.c_int)])
+    return {f"{prefix}_{name}": sig for name, sig in sigs.items()}
+
+
+# Every symbol the headers under include/ declare, with its prototype: the one list (load() declares them all, and the tests check each
+# header against its *_EXPORTS).
+SIGS = {
+    **_handle_sigs("vtts_hifigan", True),
+    **_handle_sigs("vtts_nat_duration", True),
+    **_handle_sigs("vtts_nat_acoustic", True),
+    **_handle_sigs("vtts_mel", False),
+    **_handle_sigs("vtts_audio", False),
+    **_handle_sigs("vtts_disc", True),
+    "vtts_abi_version": (C.c_int, []),
+    "vtts_last_error": (cp, []),
+    "vtts_hifigan_create": (C.c_int, [C.POINTER(CfgStruct), C.c_int, C.c_int, C.POINTER(vp)]),
+    "vtts_hifigan_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_hifigan_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
+    "vtts_hifigan_forward_ragged": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
+    "vtts_hifigan_tap_elems": (C.c_int, [vp, cp, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_hifigan_forward_tap": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp, cp, vp]),
+    "vtts_hifigan_run_module": (C.c_int, [vp, cp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
+    "vtts_hifigan_run_pair": (C.c_int, [vp, cp, vp, C.c_int, C.c_int, vp, vp]),
+    "vtts_hifigan_set_option": (C.c_int, [vp, cp, i64]),
+    "vtts_hifigan_get_option": (C.c_int, [vp, cp, C.POINTER(i64)]),
+    "vtts_hifigan_profile_read": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double), C.c_int]),
+    "vtts_hifigan_profile_kernel": (cp, [vp]),
+    "vtts_nat_duration_create": (C.c_int, [C.POINTER(NatDurationCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_nat_duration_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_nat_duration_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
+    "vtts_nat_acoustic_create": (C.c_int, [C.POINTER(NatAcousticCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_nat_acoustic_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_nat_acoustic_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
+    "vtts_nat_acoustic_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
+    "vtts_nat_acoustic_resident_status": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "vtts_nat_acoustic_keep_masks": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
+    "vtts_nat_acoustic_keep_masks_haiku": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, vp]),
+    "vtts_nat_acoustic_keep_masks_haiku_mode": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "vtts_nat_acoustic_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp]),
+    "vtts_nat_acoustic_forward_groups": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp, C.c_int,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vtts_nat_acoustic_wait_group": (C.c_int, [vp, C.c_int, vp]),
+    "vtts_nat_acoustic_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
+    "vtts_nat_acoustic_forward_from_encoder": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp, C.c_int,
+                                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vtts_nat_acoustic_forward_teacher_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_nat_acoustic_forward_teacher": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "vtts_nat_acoustic_teacher_masks_haiku": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "vtts_mel_create": (C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_mel_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_mel_filterbank": (C.c_int, [vp, fp]),
+    "vtts_mel_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_mel_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, i64, vp, vp]),
+    "vtts_audio_create": (C.c_int, [C.POINTER(AudioCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_audio_ratio": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vtts_audio_out_samples": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_audio_prototype": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "vtts_audio_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, C.c_int, i64, vp]),
+    "vtts_disc_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+    "vtts_disc_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_disc_num_fmaps": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "vtts_disc_fmap_info": (C.c_int, [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+    "vtts_disc_forward": (C.c_int, [vp, vp, C.c_int, i64, vp, vp, vp, vp]),
+    "vtts_disc_losses": (C.c_int, [vp, vp, vp, C.c_int, i64, vp, vp]),
+}
+
+
+def _exports(*prefixes: str) -> tuple:
+    return tuple(name for name in SIGS if name.startswith(prefixes))
+
+
+EXPORTS = _exports("vtts_abi_version", "vtts_last_error", "vtts_hifigan_")  # include/vtts_hifigan.h
+NAT_EXPORTS = _exports("vtts_nat_")  # include/vtts_nat.h
+MEL_EXPORTS = _exports("vtts_mel_")  # include/vtts_mel.h
+DISC_EXPORTS = _exports("vtts_disc_")  # include/vtts_disc.h
+AUDIO_EXPORTS = _exports("vtts_audio_")  # include/vtts_audio.h
 
 
 def default_lib_path() -> Path:
@@ -242,98 +232,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    vp, cp, sz, i64 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int64
-    fp = C.POINTER(C.c_float)
-    sigs = {
-        "vtts_abi_version": (C.c_int, []),
-        "vtts_last_error": (cp, []),
-        "vtts_hifigan_create": (C.c_int, [C.POINTER(CfgStruct), C.c_int, C.c_int, C.POINTER(vp)]),
-        "vtts_hifigan_destroy": (None, [vp]),
-        "vtts_hifigan_set_param": (C.c_int, [vp, cp, cp, vp, C.POINTER(i64), C.c_int]),
-        "vtts_hifigan_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "vtts_hifigan_param_info": (C.c_int, [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.POINTER(i64), C.POINTER(C.c_int)]),
-        "vtts_hifigan_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
-        "vtts_hifigan_pack": (C.c_int, [vp, vp, sz, vp]),
-        "vtts_hifigan_bind_packed": (C.c_int, [vp, vp, sz]),
-        "vtts_hifigan_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(sz)]),
-        "vtts_hifigan_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
-        "vtts_hifigan_forward_ragged": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
-        "vtts_hifigan_tap_elems": (C.c_int, [vp, cp, C.c_int, C.c_int, C.POINTER(sz)]),
-        "vtts_hifigan_forward_tap": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp, cp, vp]),
-        "vtts_hifigan_run_module": (C.c_int, [vp, cp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
-        "vtts_hifigan_run_pair": (C.c_int, [vp, cp, vp, C.c_int, C.c_int, vp, vp]),
-        "vtts_hifigan_set_option": (C.c_int, [vp, cp, i64]),
-        "vtts_hifigan_get_option": (C.c_int, [vp, cp, C.POINTER(i64)]),
-        "vtts_hifigan_profile_read": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double), C.c_int]),
-        "vtts_hifigan_profile_kernel": (cp, [vp]),
-        "vtts_nat_duration_create": (C.c_int, [C.POINTER(NatDurationCfg), C.c_int, C.POINTER(vp)]),
-        "vtts_nat_duration_destroy": (None, [vp]),
-        "vtts_nat_duration_set_param": (C.c_int, [vp, cp, cp, vp, C.POINTER(i64), C.c_int]),
-        "vtts_nat_duration_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "vtts_nat_duration_param_info": (C.c_int, [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.POINTER(i64), C.POINTER(C.c_int)]),
-        "vtts_nat_duration_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
-        "vtts_nat_duration_pack": (C.c_int, [vp, vp, sz, vp]),
-        "vtts_nat_duration_bind_packed": (C.c_int, [vp, vp, sz]),
-        "vtts_nat_duration_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(sz)]),
-        "vtts_nat_duration_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
-        "vtts_nat_acoustic_create": (C.c_int, [C.POINTER(NatAcousticCfg), C.c_int, C.POINTER(vp)]),
-        "vtts_nat_acoustic_destroy": (None, [vp]),
-        "vtts_nat_acoustic_set_param": (C.c_int, [vp, cp, cp, vp, C.POINTER(i64), C.c_int]),
-        "vtts_nat_acoustic_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "vtts_nat_acoustic_param_info": (C.c_int, [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.POINTER(i64), C.POINTER(C.c_int)]),
-        "vtts_nat_acoustic_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
-        "vtts_nat_acoustic_pack": (C.c_int, [vp, vp, sz, vp]),
-        "vtts_nat_acoustic_bind_packed": (C.c_int, [vp, vp, sz]),
-        "vtts_nat_acoustic_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
-        "vtts_nat_acoustic_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "vtts_nat_acoustic_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
-        "vtts_nat_acoustic_resident_status": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "vtts_nat_acoustic_keep_masks": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
-        "vtts_nat_acoustic_keep_masks_haiku": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, vp]),
-        "vtts_nat_acoustic_keep_masks_haiku_mode": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp]),
-        "vtts_nat_acoustic_forward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp]),
-        "vtts_nat_acoustic_forward_groups": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp, C.c_int,
-                                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-        "vtts_nat_acoustic_wait_group": (C.c_int, [vp, C.c_int, vp]),
-        "vtts_nat_acoustic_encode": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, sz, vp]),
-        "vtts_nat_acoustic_forward_from_encoder": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp, C.c_int,
-                                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-        "vtts_nat_acoustic_forward_teacher_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
-        "vtts_nat_acoustic_forward_teacher": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, sz, vp]),
-        "vtts_nat_acoustic_teacher_masks_haiku": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "vtts_mel_create": (C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
-        "vtts_mel_destroy": (None, [vp]),
-        "vtts_mel_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
-        "vtts_mel_filterbank": (C.c_int, [vp, fp]),
-        "vtts_mel_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
-        "vtts_mel_pack": (C.c_int, [vp, vp, sz, vp]),
-        "vtts_mel_bind_packed": (C.c_int, [vp, vp, sz]),
-        "vtts_mel_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
-        "vtts_mel_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, i64, vp, vp]),
-        "vtts_audio_create": (C.c_int, [C.POINTER(AudioCfg), C.c_int, C.POINTER(vp)]),
-        "vtts_audio_destroy": (None, [vp]),
-        "vtts_audio_ratio": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-        "vtts_audio_out_samples": (C.c_int, [vp, i64, C.POINTER(i64)]),
-        "vtts_audio_prototype": (C.c_int, [vp, C.POINTER(C.c_double)]),
-        "vtts_audio_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
-        "vtts_audio_pack": (C.c_int, [vp, vp, sz, vp]),
-        "vtts_audio_bind_packed": (C.c_int, [vp, vp, sz]),
-        "vtts_audio_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, C.c_int, i64, vp]),
-        "vtts_disc_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
-        "vtts_disc_destroy": (None, [vp]),
-        "vtts_disc_num_params": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "vtts_disc_param_info": (C.c_int, [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.POINTER(i64), C.POINTER(C.c_int)]),
-        "vtts_disc_set_param": (C.c_int, [vp, cp, cp, vp, C.POINTER(i64), C.c_int]),
-        "vtts_disc_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
-        "vtts_disc_pack": (C.c_int, [vp, vp, sz, vp]),
-        "vtts_disc_bind_packed": (C.c_int, [vp, vp, sz]),
-        "vtts_disc_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
-        "vtts_disc_num_fmaps": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "vtts_disc_fmap_info": (C.c_int, [vp, C.c_int, C.c_int, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
-        "vtts_disc_forward": (C.c_int, [vp, vp, C.c_int, i64, vp, vp, vp, vp]),
-        "vtts_disc_losses": (C.c_int, [vp, vp, vp, C.c_int, i64, vp, vp]),
-    }
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in SIGS.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

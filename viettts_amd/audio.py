@@ -11,17 +11,42 @@ No CPU fallback: the input lives on (or is copied to) the GPU.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import List
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._handle import NativeHandle, ptr
 
 _DTYPES = {"f32": (torch.float32, _lib.VTTS_AUDIO_F32), "pcm16": (torch.int16, _lib.VTTS_AUDIO_PCM16)}
 
 
-class Resampler:
+def waveform_rows(x, lengths, device, what: str):
+    """A waveform argument as the kernels take it: ``x`` (numpy array or tensor on ``device``, float32 or int16, ``[N, S]``) as a contiguous
+    device tensor, and ``lengths`` (samples per row, or None for all ``S``) as a list and as the ``c_int32`` array the C side reads (None
+    without ``lengths``).  ``what`` names the argument in messages."""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.int16:
+            x = x.astype(np.float32, copy=False)
+        x = torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what} must be a torch.Tensor on {device} or a numpy array")
+    if x.device != device:
+        raise ValueError(f"{what} is on {x.device}, expected {device}")
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"{what} must be float32 or int16 [N, S], got {tuple(x.shape)} {x.dtype}")
+    x = x.contiguous()
+    N, S = x.shape
+    if lengths is None:
+        return x, [S] * N, None
+    lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
+    if len(lens) != N:
+        raise ValueError("lengths must hold one sample count per row")
+    return x, lens, (C.c_int32 * N)(*lens)
+
+
+class Resampler(NativeHandle):
     """``Resampler(in_rate, out_rate, device)(wav, lengths=None, out_dtype="f32", packed=False)``.
 
     ``wav`` is ``[N, S]`` (or ``[S]``) float32 or int16 PCM, a tensor on the device or a numpy array.  Row b's first ``lengths[b]``
@@ -31,84 +56,38 @@ class Resampler:
     Asynchronous on torch's current stream of the device.  One Resampler serves one call at a time on one device."""
 
     def __init__(self, in_rate: int, out_rate: int, device="cuda:0", lib_path=None):
-        self.lib = _lib.load(lib_path)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("Resampler needs a ROCm device ('cuda:N'); there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__("vtts_audio", device, lib_path, "resampler")
         self.in_rate, self.out_rate = int(in_rate), int(out_rate)
-        self._h = C.c_void_p(0)
-        cfg = _lib.AudioCfg(self.in_rate, self.out_rate)
-        dev_index = self.device.index if self.device.index is not None else 0
-        _lib.check(self.lib, self.lib.vtts_audio_create(C.byref(cfg), dev_index, C.byref(self._h)))
+        self._create(C.byref(_lib.AudioCfg(self.in_rate, self.out_rate)))
         L, M, half = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        _lib.check(self.lib, self.lib.vtts_audio_ratio(self._h, C.byref(L), C.byref(M), C.byref(half)))
+        self._call("ratio", C.byref(L), C.byref(M), C.byref(half))
         self.L, self.M, self.half = int(L.value), int(M.value), int(half.value)
-        self._blob: Optional[torch.Tensor] = None
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.vtts_audio_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def prototype(self) -> np.ndarray:
         """The ``2 * half + 1`` float64 taps the table was rounded from."""
         h = np.empty(2 * self.half + 1, dtype=np.float64)
-        _lib.check(self.lib, self.lib.vtts_audio_prototype(self._h, h.ctypes.data_as(C.POINTER(C.c_double))))
+        self._call("prototype", h.ctypes.data_as(C.POINTER(C.c_double)))
         return h
 
     def out_samples(self, n_in: int) -> int:
         n = C.c_int64(0)
-        _lib.check(self.lib, self.lib.vtts_audio_out_samples(self._h, int(n_in), C.byref(n)))
+        self._call("out_samples", int(n_in), C.byref(n))
         return int(n.value)
 
     def out_lengths(self, lengths) -> List[int]:
         return [self.out_samples(int(n)) for n in lengths]
 
-    def _pack(self):
-        """The tap table goes to the device once, at the first call."""
-        if self._blob is None:
-            n = C.c_size_t(0)
-            _lib.check(self.lib, self.lib.vtts_audio_packed_bytes(self._h, C.byref(n)))
-            blob = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-            stream = torch.cuda.current_stream(self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib, self.lib.vtts_audio_pack(self._h, C.c_void_p(blob.data_ptr()), blob.numel(), C.c_void_p(stream.cuda_stream)))
-            self._blob = blob
-
     def __call__(self, wav, lengths=None, out_dtype: str = "f32", packed: bool = False) -> torch.Tensor:
         if out_dtype not in _DTYPES:
             raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
-        if isinstance(wav, np.ndarray):
-            if wav.dtype != np.int16:
-                wav = wav.astype(np.float32, copy=False)
-            wav = torch.from_numpy(np.ascontiguousarray(wav)).to(self.device)
-        if not isinstance(wav, torch.Tensor):
-            raise TypeError("wav must be a torch.Tensor on the resampler's device or a numpy array")
-        if wav.device != self.device:
-            raise ValueError(f"wav is on {wav.device}, Resampler on {self.device}")
-        one_row = wav.dim() == 1
+        one_row = getattr(wav, "ndim", 2) == 1
         if one_row:
             wav = wav[None, :]
-        if wav.dim() != 2 or wav.dtype not in (torch.float32, torch.int16) or wav.shape[0] < 1 or wav.shape[1] < 1:
-            raise ValueError(f"wav must be float32 or int16 [N, S], got {tuple(wav.shape)} {wav.dtype}")
-        wav = wav.contiguous()
+        wav, lens, lens_c = waveform_rows(wav, lengths, self.device, "wav")
         N, S = wav.shape
-        if lengths is None:
-            lens, lens_c = [S] * N, None
-        else:
-            lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-            if len(lens) != N:
-                raise ValueError("lengths must hold one sample count per row")
-            lens_c = (C.c_int32 * N)(*lens)
+        if N < 1 or S < 1:
+            raise ValueError(f"wav must have at least one row and one sample, got {tuple(wav.shape)}")
         outs = [self.out_samples(n) for n in lens] if lengths is not None else [self.out_samples(S)] * N
         tdt, code = _DTYPES[out_dtype]
         if packed:
@@ -116,16 +95,11 @@ class Resampler:
         else:
             o_stride = max(max(outs), 1)
             out = torch.empty((N, o_stride), dtype=tdt, device=self.device)
-        self._pack()
-        stream = torch.cuda.current_stream(self.device)
+        if self._blob is None:  # the tap table goes to the device once, at the first call
+            self._pack()
         in_code = _lib.VTTS_AUDIO_PCM16 if wav.dtype == torch.int16 else _lib.VTTS_AUDIO_F32
         if out.numel():
-            with torch.cuda.device(self.device):
-                _lib.check(
-                    self.lib,
-                    self.lib.vtts_audio_forward(self._h, C.c_void_p(wav.data_ptr()), in_code, N, S, lens_c, C.c_void_p(out.data_ptr()), code, o_stride,
-                                                C.c_void_p(stream.cuda_stream)),
-                )
+            self._on_stream("forward", ptr(wav), in_code, N, S, lens_c, ptr(out), code, o_stride)
         if not packed and max(outs) == 0:
             out = out[:, :0]
         return out[0] if one_row and not packed else out

@@ -31,7 +31,9 @@
 #include "audio_design.h"
 #include "vtts_internal.h"
 
+using vtts::check_blob;
 using vtts::failf;
+using vtts::upload_blob;
 namespace ad = vtts_audio_design;
 
 namespace {
@@ -219,22 +221,18 @@ VTTS_API int vtts_audio_packed_bytes(const vtts_audio* h, size_t* bytes) {
 }
 
 VTTS_API int vtts_audio_pack(vtts_audio* h, void* dev_blob, size_t blob_bytes, void* stream) {
-    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     const size_t need = h->d.table.size() * sizeof(float);
-    if (blob_bytes < need) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", blob_bytes, need);
-    if (reinterpret_cast<uintptr_t>(dev_blob) % 256) return failf(VTTS_ERR_INVALID, "blob must be 256-byte aligned");
-    hipError_t e = hipMemcpyAsync(dev_blob, h->d.table.data(), need, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "copying the tap table failed: %s", hipGetErrorString(e));
+    if (int rc = check_blob(dev_blob, blob_bytes, need)) return rc;
+    if (int rc = upload_blob(dev_blob, h->d.table.data(), need, static_cast<hipStream_t>(stream), "the tap table")) return rc;
     h->blob = static_cast<const float*>(dev_blob);
     return VTTS_OK;
 }
 
 VTTS_API int vtts_audio_bind_packed(vtts_audio* h, void* dev_blob, size_t blob_bytes) {
-    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     const size_t need = h->d.table.size() * sizeof(float);
-    if (blob_bytes < need) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", blob_bytes, need);
-    if (reinterpret_cast<uintptr_t>(dev_blob) % 256) return failf(VTTS_ERR_INVALID, "blob must be 256-byte aligned");
+    if (int rc = check_blob(dev_blob, blob_bytes, need)) return rc;
     h->blob = static_cast<const float*>(dev_blob);
     return VTTS_OK;
 }

@@ -32,7 +32,9 @@
 #include "../../include/vtts_hifigan.h"
 #include "vtts_internal.h"
 
+using vtts::check_blob;
 using vtts::failf;
+using vtts::upload_blob;
 
 namespace {
 
@@ -564,15 +566,12 @@ VTTS_API int vtts_disc_packed_bytes(const vtts_disc* h, size_t* bytes) {
 }
 
 VTTS_API int vtts_disc_pack(vtts_disc* h, void* dev_blob, size_t blob_bytes, void* stream) {
-    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    const size_t need = h->blob_floats * sizeof(float);
+    if (int rc = check_blob(dev_blob, blob_bytes, need)) return rc;
     for (int i = 0; i < 2 * NCONV; ++i)
         if (!h->have[i]) return failf(VTTS_ERR_MISSING, "parameter %s/%s was never set", h->specs[i / 2].key.c_str(), i % 2 ? "b" : "w");
-    const size_t need = h->blob_floats * sizeof(float);
-    if (blob_bytes != need) return failf(VTTS_ERR_NOMEM, "blob must be %zu bytes (got %zu)", need, blob_bytes);
-    if (reinterpret_cast<uintptr_t>(dev_blob) % 256) return failf(VTTS_ERR_INVALID, "blob must be 256-byte aligned");
-    hipError_t e = hipMemcpyAsync(dev_blob, h->img.data(), need, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "copying the discriminator weights failed: %s", hipGetErrorString(e));
+    if (int rc = upload_blob(dev_blob, h->img.data(), need, static_cast<hipStream_t>(stream), "the discriminator weights")) return rc;
     h->blob = static_cast<const float*>(dev_blob);
     std::vector<float>().swap(h->img);  // 283 MB of host memory; a later set_param starts a new image
     memset(h->have, 0, sizeof(h->have));
@@ -580,10 +579,8 @@ VTTS_API int vtts_disc_pack(vtts_disc* h, void* dev_blob, size_t blob_bytes, voi
 }
 
 VTTS_API int vtts_disc_bind_packed(vtts_disc* h, void* dev_blob, size_t blob_bytes) {
-    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-    const size_t need = h->blob_floats * sizeof(float);
-    if (blob_bytes != need) return failf(VTTS_ERR_NOMEM, "blob must be %zu bytes (got %zu)", need, blob_bytes);
-    if (reinterpret_cast<uintptr_t>(dev_blob) % 256) return failf(VTTS_ERR_INVALID, "blob must be 256-byte aligned");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    if (int rc = check_blob(dev_blob, blob_bytes, h->blob_floats * sizeof(float))) return rc;
     h->blob = static_cast<const float*>(dev_blob);
     return VTTS_OK;
 }

@@ -1220,9 +1220,8 @@ VTTS_API int vtts_hifigan_packed_bytes(const vtts_hifigan* h, size_t* bytes) {
 }
 
 VTTS_API int vtts_hifigan_pack(vtts_hifigan* h, void* dev_blob, size_t blob_bytes, vtts_stream stream) {
-    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-    if (blob_bytes < h->blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu", blob_bytes, h->blob_bytes);
-    if ((reinterpret_cast<uintptr_t>(dev_blob) & 255) != 0) return failf(VTTS_ERR_INVALID, "blob must be 256-B aligned");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    if (int rc = check_blob(dev_blob, blob_bytes, h->blob_bytes)) return rc;
     for (auto& l : h->layers)
         if (!l.have_w || !l.have_b) return failf(VTTS_ERR_MISSING, "parameter %s/%s was never set", l.key.c_str(), l.have_w ? "b" : "w");
     std::vector<char> host(h->blob_bytes, 0);
@@ -1295,17 +1294,15 @@ VTTS_API int vtts_hifigan_pack(vtts_hifigan* h, void* dev_blob, size_t blob_byte
             convT1d_f32_mfma_pack(l.w.data(), l.cin, l.cout, l.k, l.stride, l.pad_a, reinterpret_cast<float*>(host.data() + l.off_wp));
     }
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(dev_blob, host.data(), h->blob_bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
-    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));  // `host` dies at return
+    if (int rc = upload_blob(dev_blob, host.data(), h->blob_bytes, static_cast<hipStream_t>(stream), "the generator's weights")) return rc;
     h->blob = static_cast<char*>(dev_blob);
     ++h->epoch;  // captured graphs hold the old blob's addresses
     return VTTS_OK;
 }
 
 VTTS_API int vtts_hifigan_bind_packed(vtts_hifigan* h, void* dev_blob, size_t blob_bytes) {
-    if (!h || !dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-    if (blob_bytes < h->blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu", blob_bytes, h->blob_bytes);
-    if ((reinterpret_cast<uintptr_t>(dev_blob) & 255) != 0) return failf(VTTS_ERR_INVALID, "blob must be 256-B aligned");
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    if (int rc = check_blob(dev_blob, blob_bytes, h->blob_bytes)) return rc;
     h->blob = static_cast<char*>(dev_blob);
     ++h->epoch;  // captured graphs hold the old blob's addresses
     return VTTS_OK;

@@ -241,18 +241,15 @@ struct NatModel {
         return VTTS_OK;
     }
     int pack(void* dev_blob, size_t bytes, void* stream) {
-        if (!dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-        if (bytes < blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", bytes, blob_bytes);
+        if (int rc = check_blob(dev_blob, bytes, blob_bytes)) return rc;
         std::vector<char> img;
         if (int rc = image(img)) return rc;
-        HIP_TRY(hipMemcpyAsync(dev_blob, img.data(), blob_bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
-        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));  // img dies at return
+        if (int rc = upload_blob(dev_blob, img.data(), blob_bytes, static_cast<hipStream_t>(stream), "the model's weights")) return rc;
         blob = static_cast<char*>(dev_blob);
         return VTTS_OK;
     }
     int bind(void* dev_blob, size_t bytes) {
-        if (!dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
-        if (bytes < blob_bytes) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", bytes, blob_bytes);
+        if (int rc = check_blob(dev_blob, bytes, blob_bytes)) return rc;
         blob = static_cast<char*>(dev_blob);
         return VTTS_OK;
     }

@@ -25,6 +25,22 @@ int failf(int code, const char* fmt, ...);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The one rule for a caller's packed blob, behind every handle's pack() and bind_packed(): `bytes` at `dev_blob` must hold the handle's `need`
+// packed bytes (more is fine) and start on a 256-byte boundary (the kernels read it as float4 / uint4).  Host arithmetic only.
+inline int check_blob(const void* dev_blob, size_t bytes, size_t need) {
+    if (!dev_blob) return failf(VTTS_ERR_INVALID, "null argument");
+    if (bytes < need) return failf(VTTS_ERR_NOMEM, "blob too small: %zu < %zu bytes", bytes, need);
+    if (reinterpret_cast<uintptr_t>(dev_blob) % 256) return failf(VTTS_ERR_INVALID, "blob must be 256-byte aligned");
+    return VTTS_OK;
+}
+// pack()'s upload: `bytes` of `host` into the checked blob on `s`, waited for (the host image may die at the caller's return)
+inline int upload_blob(void* dev_blob, const void* host, size_t bytes, hipStream_t s, const char* what) {
+    hipError_t e = hipMemcpyAsync(dev_blob, host, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "copying %s failed: %s", what, hipGetErrorString(e));
+    return VTTS_OK;
+}
+
 // fp32 -> bf16 bits, round-to-nearest-even (what v_cvt_pk_bf16_f32 gives), and back
 inline unsigned short f32_to_bf16_rne(float f) {
     uint32_t u;

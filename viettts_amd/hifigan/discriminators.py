@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import NativeHandle, ptr
 
 PERIODS = (2, 3, 5, 7, 11)
 MPD_LAYERS, MSD_LAYERS = 6, 8  # feature maps per discriminator
@@ -106,47 +107,20 @@ class DiscLosses:
     raw: Optional[torch.Tensor] = None  # the device buffer of include/vtts_disc.h's layout
 
 
-class Discriminators:
+class Discriminators(NativeHandle):
     """Both discriminator stacks on one ROCm device.  One instance serves one call at a time."""
 
     def __init__(self, device="cuda:0", lib_path=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("Discriminators needs a ROCm device ('cuda:N'); there is no CPU path")
-        self.lib = _lib.load(lib_path)
-        self._h = C.c_void_p(0)
-        dev_index = self.device.index if self.device.index is not None else 0
-        _lib.check(self.lib, self.lib.vtts_disc_create(dev_index, C.byref(self._h)))
-        self._blob: Optional[torch.Tensor] = None
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.vtts_disc_destroy(self._h)
-            self._h = C.c_void_p(0)
-        self._blob = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__("vtts_disc", device, lib_path, "discriminator stack")
+        self._create()
 
     # ---- weights ----
     def load_params(self, params: Dict[str, Tuple[np.ndarray, np.ndarray]]) -> "Discriminators":
         """``{key: (w [Cout, Cin / groups, k], b [Cout])}`` effective fp32 weights for all 54 convolutions."""
         for key, (w, b) in params.items():
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            b = np.ascontiguousarray(b, dtype=np.float32)
-            for which, a in ((b"w", w), (b"b", b)):
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(self.lib, self.lib.vtts_disc_set_param(self._h, key.encode(), which, C.c_void_p(a.ctypes.data), shape, a.ndim))
-        n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_disc_packed_bytes(self._h, C.byref(n)))
-        blob = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_disc_pack(self._h, C.c_void_p(blob.data_ptr()), blob.numel(), C.c_void_p(stream.cuda_stream)))
-        self._blob = blob
+            self._set_param(key, "w", w)
+            self._set_param(key, "b", b)
+        self._pack()
         return self
 
     def load_checkpoint_dict(self, ckpt) -> "Discriminators":
@@ -162,7 +136,7 @@ class Discriminators:
     def fmap_info(self, i: int, N: int, T: int):
         """(C, L, columns, element offset) of feature map i in the buffer of an N-row, T-sample call."""
         c, l, p, off = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        _lib.check(self.lib, self.lib.vtts_disc_fmap_info(self._h, i, N, T, C.byref(c), C.byref(l), C.byref(p), C.byref(off)))
+        self._call("fmap_info", i, N, T, C.byref(c), C.byref(l), C.byref(p), C.byref(off))
         return int(c.value), int(l.value), int(p.value), int(off.value)
 
     def buffer_sizes(self, N: int, T: int) -> Tuple[int, int]:
@@ -200,10 +174,7 @@ class Discriminators:
         for buf, n in ((fmaps_buf, nf), (scores_buf, ns)):
             if buf.numel() != n or buf.dtype != torch.float32 or buf.device != self.device or not buf.is_contiguous():
                 raise ValueError(f"buffers must be contiguous float32 of {nf} and {ns} elements on {self.device}")
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_disc_forward(self._h, C.c_void_p(y.data_ptr()), N, T, C.c_void_p(fmaps_buf.data_ptr()),
-                                                            C.c_void_p(scores_buf.data_ptr()), None, C.c_void_p(stream.cuda_stream)))
+        self._on_stream("forward", ptr(y), N, T, ptr(fmaps_buf), ptr(scores_buf), None)
         return fmaps_buf, scores_buf
 
     def views(self, fmaps_buf: torch.Tensor, scores_buf: torch.Tensor, N: int, T: int):
@@ -230,10 +201,7 @@ class Discriminators:
     def losses_raw(self, fmaps_buf: torch.Tensor, scores_buf: torch.Tensor, B: int, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:
             out = torch.empty(_lib.DISC_LOSS_FLOATS, dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_disc_losses(self._h, C.c_void_p(fmaps_buf.data_ptr()), C.c_void_p(scores_buf.data_ptr()), B, T,
-                                                           C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+        self._on_stream("losses", ptr(fmaps_buf), ptr(scores_buf), B, T, ptr(out))
         return out
 
     @staticmethod

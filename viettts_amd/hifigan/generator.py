@@ -10,19 +10,15 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import NativeHandle, ptr
 from .config import HifiganConfig, V1
 from .weights import ParamDict, check_params, conv_specs
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-class Generator:
+class Generator(NativeHandle):
     """``Generator(cfg)(mel)`` — mel ``[B, T, num_mels]`` float32 NWC -> wav ``[B, hop*T]`` float32.
 
     No CPU fallback: construction fails if the HIP extension is missing, and ``__call__`` fails
@@ -35,62 +31,19 @@ class Generator:
     """
 
     def __init__(self, cfg: HifiganConfig = V1, device="cuda:0", dtype: str = "f32", lib_path=None):
+        super().__init__("vtts_hifigan", device, lib_path, "generator")
         self.cfg = cfg
-        self.lib = _lib.load(lib_path)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("Generator needs a ROCm device ('cuda:N'); there is no CPU path")
         self.dtype = {"f32": _lib.VTTS_F32, "bf16": _lib.VTTS_BF16, "bf16x3": _lib.VTTS_BF16X3}[dtype]  # bf16x3: the fp32 engine's layouts and entry points
         self.dtype_name = dtype
-        self._h = C.c_void_p(0)
-        cs = _lib.make_cfg(cfg)
-        dev_index = self.device.index if self.device.index is not None else 0
-        _lib.check(self.lib, self.lib.vtts_hifigan_create(C.byref(cs), dev_index, self.dtype, C.byref(self._h)))
-        self._blob: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
+        self._create(C.byref(_lib.make_cfg(cfg)), tail=(self.dtype,))
         self.hop = cfg.hop
 
-    # ---- lifetime -------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.vtts_hifigan_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # ---- parameters -----------------------------------------------------------------------------
+    # ---- parameters (param_table(): the same 156 arrays hk_hifi.pickle holds) ---------------------
     @property
     def max_frames_per_pass(self) -> int:
         """Utterances of this many mel frames or more are refused by the C ABI (an utterance's largest activation must stay
         below 2^31 bytes: include/vtts_hifigan.h, vtts_hifigan_workspace_bytes); they go through viettts_amd.longform."""
         return self.get_option("max_frames_per_pass")  # the engine's own rule (engine.hip: check_pass_size), not a copy of it
-
-    @property
-    def packed_bytes(self) -> int:
-        n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_hifigan_packed_bytes(self._h, C.byref(n)))
-        return int(n.value)
-
-    def param_table(self):
-        """[(key, which, shape)] the C side expects — the same 156 arrays hk_hifi.pickle holds."""
-        n = C.c_int(0)
-        _lib.check(self.lib, self.lib.vtts_hifigan_num_params(self._h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            key, which = C.c_char_p(), C.c_char_p()
-            shape = (C.c_int64 * 3)()
-            nd = C.c_int(0)
-            _lib.check(self.lib, self.lib.vtts_hifigan_param_info(self._h, i, C.byref(key), C.byref(which), shape, C.byref(nd)))
-            out.append((key.value.decode(), which.value.decode(), tuple(int(shape[d]) for d in range(nd.value))))
-        return out
-
-    def _alloc_blob(self) -> torch.Tensor:
-        # uint8 tensor from the caching allocator: >= 512-B aligned
-        return torch.empty(self.packed_bytes, dtype=torch.uint8, device=self.device)
 
     def load_params(self, params: ParamDict) -> None:
         """Re-lay-out a Haiku parameter dict into the packed device blob (once, not per call as
@@ -98,53 +51,24 @@ class Generator:
         check_params(self.cfg, params)
         for spec in conv_specs(self.cfg):
             for which in ("w", "b"):
-                a = np.ascontiguousarray(params[spec.key][which], dtype=np.float32)
-                shape = (C.c_int64 * a.ndim)(*a.shape)
-                _lib.check(
-                    self.lib,
-                    self.lib.vtts_hifigan_set_param(self._h, spec.key.encode(), which.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim),
-                )
-        blob = self._alloc_blob()
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_hifigan_pack(self._h, _ptr(blob), blob.numel(), C.c_void_p(stream.cuda_stream)))
-        self._blob = blob
-
-    def packed_blob(self) -> torch.Tensor:
-        if self._blob is None:
-            raise RuntimeError("no parameters loaded")
-        return self._blob
-
-    def adopt_packed(self, blob: torch.Tensor) -> None:
-        """Bind a packed blob produced by another rank's ``load_params`` (weights broadcast once
-        over RCCL; viettts_amd/dist.py)."""
-        if blob.dtype != torch.uint8 or blob.numel() < self.packed_bytes or blob.device != self.device:
-            raise ValueError("packed blob must be a uint8 tensor of packed_bytes on this generator's device")
-        _lib.check(self.lib, self.lib.vtts_hifigan_bind_packed(self._h, _ptr(blob), blob.numel()))
-        self._blob = blob
+                self._set_param(spec.key, which, params[spec.key][which])
+        self._pack()
 
     # ---- options --------------------------------------------------------------------------------
     def set_option(self, name: str, value: int) -> None:
-        _lib.check(self.lib, self.lib.vtts_hifigan_set_option(self._h, name.encode(), int(value)))
-        # the cached workspace stays: _workspace() asks the engine for the size every call and only ever grows it
+        self._call("set_option", name.encode(), int(value))
+        # the cached workspace stays: every call asks the engine for the size and _workspace() only ever grows it
 
     def get_option(self, name: str) -> int:
         v = C.c_int64(0)
-        _lib.check(self.lib, self.lib.vtts_hifigan_get_option(self._h, name.encode(), C.byref(v)))
+        self._call("get_option", name.encode(), C.byref(v))
         return int(v.value)
 
     # ---- forward --------------------------------------------------------------------------------
     def workspace_bytes(self, B: int, T: int) -> int:
         n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_hifigan_workspace_bytes(self._h, B, T, C.byref(n)))
+        self._call("workspace_bytes", B, T, C.byref(n))
         return int(n.value)
-
-    def _workspace(self, B: int, T: int) -> torch.Tensor:
-        need = self.workspace_bytes(B, T)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def _check_mel(self, mel: torch.Tensor):
         if not isinstance(mel, torch.Tensor):
@@ -170,13 +94,8 @@ class Generator:
         mel = self._check_mel(mel)
         B, T, _ = mel.shape
         out = self._check_out(out, (B, self.hop * T), "[B, hop*T]")
-        ws = self._workspace(B, T)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(
-                self.lib,
-                self.lib.vtts_hifigan_forward(self._h, _ptr(mel), B, T, _ptr(out), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)),
-            )
+        ws = self._workspace(self.workspace_bytes(B, T))
+        self._on_stream("forward", ptr(mel), B, T, ptr(out), ptr(ws), ws.numel())
         return out
 
     def forward_ragged(self, mel: torch.Tensor, frames, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -196,13 +115,8 @@ class Generator:
         if fr.numel() != B or (fr_host is not None and (min(fr_host) < 1 or max(fr_host) > T)):
             raise ValueError("frames must hold one count per utterance, 1 <= frames[b] <= mel.shape[1]")
         out = self._check_out(out, (B, self.hop * T), "[B, hop*T]")
-        ws = self._workspace(B, T)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(
-                self.lib,
-                self.lib.vtts_hifigan_forward_ragged(self._h, _ptr(mel), _ptr(fr), B, T, _ptr(out), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)),
-            )
+        ws = self._workspace(self.workspace_bytes(B, T))
+        self._on_stream("forward_ragged", ptr(mel), ptr(fr), B, T, ptr(out), ptr(ws), ws.numel())
         return out
 
     def forward_tap(self, mel: torch.Tensor, tap: str):
@@ -210,17 +124,11 @@ class Generator:
         mel = self._check_mel(mel)
         B, T, _ = mel.shape
         n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_hifigan_tap_elems(self._h, tap.encode(), B, T, C.byref(n)))
+        self._call("tap_elems", tap.encode(), B, T, C.byref(n))
         tap_t = torch.empty(int(n.value), dtype=torch.float32, device=self.device)
         out = torch.empty((B, self.hop * T), dtype=torch.float32, device=self.device)
-        ws = self._workspace(B, T)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(
-                self.lib,
-                self.lib.vtts_hifigan_forward_tap(self._h, _ptr(mel), B, T, _ptr(out), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream),
-                                                  tap.encode(), _ptr(tap_t)),
-            )
+        ws = self._workspace(self.workspace_bytes(B, T))
+        self._on_stream("forward_tap", ptr(mel), B, T, ptr(out), ptr(ws), ws.numel(), tail=(tap.encode(), ptr(tap_t)))
         if tap == "pre_tanh":
             tap_t = tap_t.view(B, self.hop * T)
         else:
@@ -248,13 +156,7 @@ class Generator:
         y = self._check_out(out, shape, "[" + ", ".join(str(d) for d in shape) + "]")
         if res is not None:
             res = res.contiguous()
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(
-                self.lib,
-                self.lib.vtts_hifigan_run_module(self._h, key.encode(), _ptr(x), B, L, C.c_float(slope_in), _ptr(res), _ptr(y),
-                                                 C.c_void_p(stream.cuda_stream)),
-            )
+        self._on_stream("run_module", key.encode(), ptr(x), B, L, C.c_float(slope_in), ptr(res), ptr(y))
         return y
 
     def run_pair(self, key_c1: str, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -269,14 +171,12 @@ class Generator:
         else:
             B, _, L = x.shape
         y = self._check_out(out, tuple(x.shape), "[" + ", ".join(str(d) for d in x.shape) + "]")
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_hifigan_run_pair(self._h, key_c1.encode(), _ptr(x), B, L, _ptr(y), C.c_void_p(stream.cuda_stream)))
+        self._on_stream("run_pair", key_c1.encode(), ptr(x), B, L, ptr(y))
         return y
 
     # ---- dominant-kernel timing (bench.py roofline) ----------------------------------------------
     def profile_read(self, reset: bool = True):
         ms, n, fl = C.c_double(0), C.c_int64(0), C.c_double(0)
-        _lib.check(self.lib, self.lib.vtts_hifigan_profile_read(self._h, C.byref(ms), C.byref(n), C.byref(fl), int(reset)))
+        self._call("profile_read", C.byref(ms), C.byref(n), C.byref(fl), int(reset))
         name = self.lib.vtts_hifigan_profile_kernel(self._h)
         return {"ms": ms.value, "launches": int(n.value), "flops": fl.value, "kernel": name.decode() if name else ""}

@@ -24,8 +24,9 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._handle import NativeHandle, ptr
 from .config import FLAGS
-from .duration import HaikuDict, _lookup, _ptr
+from .duration import HaikuDict, _lookup, padded_rows
 
 
 def bernoulli_keep_masks(n_frames: int, seed: int, prenet_dim: int = 256) -> np.ndarray:
@@ -48,62 +49,13 @@ def _log_stream_once(partitionable: bool) -> None:
             "partitionable (JAX >= 0.5 default; unpinned restatement)" if partitionable else "classic (JAX < 0.5 default)", 0 if partitionable else 1)
 
 
-class AcousticModel:
+class AcousticModel(NativeHandle):
     def __init__(self, device="cuda:0", lib_path=None, vocab_size: int = FLAGS.vocab_size, encoder_dim: int = FLAGS.acoustic_encoder_dim,
                  decoder_dim: int = FLAGS.acoustic_decoder_dim, prenet_dim: int = 256, mel_dim: int = FLAGS.mel_dim, postnet_dim: int = FLAGS.postnet_dim):
-        self.lib = _lib.load(lib_path)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("AcousticModel needs a ROCm device ('cuda:N'); there is no CPU path")
+        super().__init__("vtts_nat_acoustic", device, lib_path, "model")
         self.cfg = _lib.NatAcousticCfg(vocab_size, encoder_dim, decoder_dim, prenet_dim, mel_dim, postnet_dim)
         self.mel_dim, self.prenet_dim, self.encoder_dim = mel_dim, prenet_dim, encoder_dim
-        self._h = C.c_void_p(0)
-        dev_index = self.device.index if self.device.index is not None else 0
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_create(C.byref(self.cfg), dev_index, C.byref(self._h)))
-        self._blob: Optional[torch.Tensor] = None
-        self._ws: Optional[torch.Tensor] = None
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self.lib.vtts_nat_acoustic_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def param_table(self):
-        n = C.c_int(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_num_params(self._h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            mod, name = C.c_char_p(), C.c_char_p()
-            shape = (C.c_int64 * 3)()
-            nd = C.c_int(0)
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_param_info(self._h, i, C.byref(mod), C.byref(name), shape, C.byref(nd)))
-            out.append((mod.value.decode(), name.value.decode(), tuple(int(shape[d]) for d in range(nd.value))))
-        return out
-
-    # ---- packed weights: rank 0 packs, the other ranks of a data-parallel job receive the blob (viettts_amd/dist.py) ----
-    @property
-    def packed_bytes(self) -> int:
-        n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_packed_bytes(self._h, C.byref(n)))
-        return int(n.value)
-
-    def packed_blob(self) -> torch.Tensor:
-        if self._blob is None:
-            raise RuntimeError("no parameters loaded")
-        return self._blob
-
-    def adopt_packed(self, blob: torch.Tensor) -> None:
-        """Bind a packed blob produced by another rank's ``load_params`` (one broadcast at start-up, no data-path collective)."""
-        if blob.dtype != torch.uint8 or blob.numel() < self.packed_bytes or blob.device != self.device:
-            raise ValueError("packed blob must be a uint8 tensor of packed_bytes on this model's device")
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_bind_packed(self._h, _ptr(blob), blob.numel()))
-        self._blob = blob
+        self._create(C.byref(self.cfg))
 
     def load_params(self, params: HaikuDict, state: HaikuDict) -> None:
         """``dic["params"]`` and ``dic["aux"]`` of acoustic_latest_ckpt.pickle (text2mel.py:62-71)."""
@@ -111,15 +63,8 @@ class AcousticModel:
             a = _lookup(state if name == "average" else params, "acoustic_model/~/" + mod, name)
             if a.shape != shape:
                 raise ValueError(f"{mod}/{name}: checkpoint shape {a.shape}, the architecture needs {shape}")
-            shp = (C.c_int64 * a.ndim)(*a.shape)
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_set_param(self._h, mod.encode(), name.encode(), a.ctypes.data_as(C.c_void_p), shp, a.ndim))
-        n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_packed_bytes(self._h, C.byref(n)))
-        blob = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_pack(self._h, _ptr(blob), blob.numel(), C.c_void_p(stream.cuda_stream)))
-        self._blob = blob
+            self._set_param(mod, name, a)
+        self._pack()
 
     def device_keep_masks(self, seeds: Sequence[int], Fmax: int) -> torch.Tensor:
         """``[B, Fmax, 2, prenet_dim]`` uint8 keep masks drawn on the GPU (include/vtts_nat.h: Threefry-2x32-20, one
@@ -127,9 +72,7 @@ class AcousticModel:
         B = len(seeds)
         sd = torch.tensor([int(x) & 0x7FFFFFFFFFFFFFFF for x in seeds], dtype=torch.int64, device=self.device)
         keep = torch.empty((B, int(Fmax), 2, self.prenet_dim), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_keep_masks(self._h, _ptr(sd), B, int(Fmax), _ptr(keep), C.c_void_p(stream.cuda_stream)))
+        self._on_stream("keep_masks", ptr(sd), B, int(Fmax), ptr(keep))
         return keep
 
     def device_keep_masks_haiku(self, rng_key, B: int, Fmax: int, partitionable: Optional[bool] = None) -> torch.Tensor:
@@ -146,10 +89,7 @@ class AcousticModel:
         _log_stream_once(bool(partitionable))
         k = np.asarray(rng_key, dtype=np.uint32).reshape(2)
         keep = torch.empty((int(B), int(Fmax), 2, self.prenet_dim), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_keep_masks_haiku_mode(self._h, int(k[0]), int(k[1]), int(bool(partitionable)), int(B), int(Fmax),
-                                                                                  _ptr(keep), C.c_void_p(stream.cuda_stream)))
+        self._on_stream("keep_masks_haiku_mode", int(k[0]), int(k[1]), int(bool(partitionable)), int(B), int(Fmax), ptr(keep))
         return keep
 
     def device_teacher_masks_haiku(self, rng_key, B: int, F: int, partitionable: Optional[bool] = None):
@@ -163,10 +103,7 @@ class AcousticModel:
         k = np.asarray(rng_key, dtype=np.uint32).reshape(2)
         keep = torch.empty((int(B), int(F), 2, self.prenet_dim), dtype=torch.uint8, device=self.device)
         zone = torch.empty((int(B), int(F), 4, int(self.cfg.decoder_dim)), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_teacher_masks_haiku(self._h, int(k[0]), int(k[1]), int(bool(partitionable)), int(B), int(F), _ptr(keep),
-                                                                                _ptr(zone), C.c_void_p(stream.cuda_stream)))
+        self._on_stream("teacher_masks_haiku", int(k[0]), int(k[1]), int(bool(partitionable)), int(B), int(F), ptr(keep), ptr(zone))
         return keep, zone
 
     def _mask_tensor(self, m, B: int, Fmax: int, inner: tuple) -> torch.Tensor:
@@ -233,11 +170,7 @@ class AcousticModel:
         if len(n_frames) != B or min(n_frames) < 1 or max(n_frames) > Fmax:
             raise ValueError(f"n_frames: one count in 1 .. {Fmax} per row")
         Lmax = max(lens)
-        tok = np.zeros((B, Lmax), dtype=np.int32)
-        dur = np.zeros((B, Lmax), dtype=np.float32)
-        for i, s in enumerate(sentences):
-            tok[i, : lens[i]] = np.asarray(s, dtype=np.int32)
-            dur[i, : lens[i]] = np.asarray(durations_frames[i], dtype=np.float32).reshape(-1)
+        tok, dur = padded_rows(sentences, durations_frames)
         keep_d = zone_d = None
         if rng is not None:
             keep_d, zone_d = self.device_teacher_masks_haiku(rng, B, Fmax)
@@ -251,16 +184,10 @@ class AcousticModel:
         out = torch.empty((B, Fmax, self.mel_dim), dtype=torch.float32, device=self.device)
         pre = torch.empty_like(out) if return_pre else None
         n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_forward_teacher_workspace_bytes(self._h, B, Lmax, Fmax, C.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(
-                self.lib,
-                self.lib.vtts_nat_acoustic_forward_teacher(self._h, _ptr(tok_d), _ptr(len_d), _ptr(dur_d), _ptr(nf_d), B, Lmax, Fmax, _ptr(mel_d), _ptr(keep_d),
-                                                           _ptr(zone_d), _ptr(out), _ptr(pre), _ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream)),
-            )
+        self._call("forward_teacher_workspace_bytes", B, Lmax, Fmax, C.byref(n))
+        ws = self._workspace(int(n.value))
+        self._on_stream("forward_teacher", ptr(tok_d), ptr(len_d), ptr(dur_d), ptr(nf_d), B, Lmax, Fmax, ptr(mel_d), ptr(keep_d), ptr(zone_d), ptr(out),
+                        ptr(pre), ptr(ws), ws.numel())
         if not to_host:
             return (pre, out) if return_pre else out
         host = out.cpu().numpy()
@@ -275,11 +202,11 @@ class AcousticModel:
         ``"resident"``: 1 = calls with one to four sentences run the decoder's frame loop as one resident kernel instead of three launches per
         frame (the low-latency path; fp32, same oracle bar, rounding of its own; every other call takes the launches as before — see
         :attr:`resident_used`); 0 = the launches (default).  ``"resident_grid"``: 0 / 64 / 128 / 256 workgroups for it (0 = the library's default)."""
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_set_option(self._h, key.encode(), int(value)))
+        self._call("set_option", key.encode(), int(value))
 
     def get_option(self, key: str) -> int:
         v = C.c_int(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_get_option(self._h, key.encode(), C.byref(v)))
+        self._call("get_option", key.encode(), C.byref(v))
         return int(v.value)
 
     @property
@@ -291,14 +218,14 @@ class AcousticModel:
         """After a synchronisation: True if a wait inside the last resident launch ran out of its 100 ms budget (the kernel then gave up and the
         frames it did not produce are zero).  ``VttsError`` (VTTS_ERR_STATE) if this model has not launched the resident kernel."""
         v = C.c_int(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_resident_status(self._h, C.byref(v)))
+        self._call("resident_status", C.byref(v))
         return bool(v.value)
 
     def wait_group(self, group: int, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Make ``stream`` (default: torch's current stream) wait until the rows of ``group`` of the last ``group_row0`` call are complete."""
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_wait_group(self._h, int(group), C.c_void_p(st.cuda_stream)))
+            self._call("wait_group", int(group), C.c_void_p(st.cuda_stream))
 
     def encode(self, sentences: Sequence[Sequence[int]]) -> torch.Tensor:
         """The token encoder alone (include/vtts_nat.h: vtts_nat_acoustic_encode), enqueued on the current stream: ``[B, Lmax, 2 * encoder_dim]`` on the
@@ -311,20 +238,13 @@ class AcousticModel:
         if B == 0 or min(lens) < 1:
             raise ValueError("empty batch or token sequence")
         Lmax = max(lens)
-        tok = np.zeros((B, Lmax), dtype=np.int32)
-        for i, s in enumerate(sentences):
-            tok[i, : lens[i]] = np.asarray(s, dtype=np.int32)
-        tok_d = torch.from_numpy(tok).to(self.device)
+        tok_d = torch.from_numpy(padded_rows(sentences)[0]).to(self.device)
         len_d = torch.tensor(lens, dtype=torch.int32, device=self.device)
         enc = torch.empty((B, Lmax, 2 * self.encoder_dim), dtype=torch.float32, device=self.device)
         n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_workspace_bytes(self._h, B, Lmax, 1, C.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib, self.lib.vtts_nat_acoustic_encode(self._h, _ptr(tok_d), _ptr(len_d), B, Lmax, _ptr(enc), _ptr(self._ws), self._ws.numel(),
-                                                                   C.c_void_p(stream.cuda_stream)))
+        self._call("workspace_bytes", B, Lmax, 1, C.byref(n))
+        ws = self._workspace(int(n.value))
+        self._on_stream("encode", ptr(tok_d), ptr(len_d), B, Lmax, ptr(enc), ptr(ws), ws.numel())
         return enc
 
     def __call__(self, sentences: Sequence[Sequence[int]], durations_frames: Sequence[np.ndarray], n_frames: Sequence[int],
@@ -357,12 +277,7 @@ class AcousticModel:
                 raise ValueError(f"encoded must be float32 [{B}, >= {Lmax}, {2 * self.encoder_dim}] (got {tuple(encoded.shape)} {encoded.dtype})")
             encoded = encoded.contiguous()
             Lmax = int(encoded.shape[1])
-        tok = np.zeros((B, Lmax), dtype=np.int32) if encoded is None else None  # (the C side ignores the tokens when the encoder's output is given)
-        dur = np.zeros((B, Lmax), dtype=np.float32)
-        for i, s in enumerate(sentences):
-            if tok is not None:
-                tok[i, : lens[i]] = np.asarray(s, dtype=np.int32)
-            dur[i, : lens[i]] = np.asarray(durations_frames[i], dtype=np.float32).reshape(-1)
+        tok, dur = padded_rows(sentences, durations_frames, Lmax)
         keep_d = None
         if keep_masks is not None:
             keep = np.zeros((B, Fmax, 2, self.prenet_dim), dtype=np.uint8)
@@ -373,43 +288,26 @@ class AcousticModel:
             keep_d = self.device_keep_masks_haiku(dropout_rng, B, Fmax)
         elif dropout_seeds is not None:
             keep_d = self.device_keep_masks(dropout_seeds, Fmax)
-        tok_d = torch.from_numpy(tok).to(self.device) if tok is not None else None
+        tok_d = torch.from_numpy(tok).to(self.device) if encoded is None else None  # (the C side ignores the tokens when the encoder's output is given)
         dur_d = torch.from_numpy(dur).to(self.device)
         len_d = torch.tensor(lens, dtype=torch.int32, device=self.device)
         nf_d = torch.tensor([int(n) for n in n_frames], dtype=torch.int32, device=self.device)
         out = torch.empty((B, Fmax, self.mel_dim), dtype=torch.float32, device=self.device)
         n = C.c_size_t(0)
-        _lib.check(self.lib, self.lib.vtts_nat_acoustic_workspace_bytes(self._h, B, Lmax, Fmax, C.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
+        self._call("workspace_bytes", B, Lmax, Fmax, C.byref(n))
+        ws = self._workspace(int(n.value))
+        args = (ptr(len_d), ptr(dur_d), ptr(nf_d), B, Lmax, Fmax, ptr(keep_d), ptr(out), ptr(ws), ws.numel())
+        if encoded is None and group_row0 is None:
+            self._on_stream("forward", ptr(tok_d), *args)
+        else:  # the groups' row boundaries and longest frame counts travel behind the stream (no groups: boundaries [0], one unused count)
+            r0 = [int(v) for v in group_row0] if group_row0 is not None else [0]
+            ng = len(r0) - 1
+            gfr = [max(int(n) for n in n_frames[r0[g] : r0[g + 1]]) if r0[g + 1] > r0[g] else 0 for g in range(ng)]
+            groups = (ng, (C.c_int32 * (ng + 1))(*r0), (C.c_int32 * max(ng, 1))(*(gfr or [0])))
             if encoded is not None:
-                r0 = [int(v) for v in group_row0] if group_row0 is not None else [0]
-                ng = len(r0) - 1
-                gfr = [max(int(n) for n in n_frames[r0[g] : r0[g + 1]]) if r0[g + 1] > r0[g] else 0 for g in range(ng)]
-                _lib.check(
-                    self.lib,
-                    self.lib.vtts_nat_acoustic_forward_from_encoder(self._h, _ptr(encoded), _ptr(len_d), _ptr(dur_d), _ptr(nf_d), B, Lmax, Fmax, _ptr(keep_d),
-                                                                    _ptr(out), _ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream), ng,
-                                                                    (C.c_int32 * (ng + 1))(*r0), (C.c_int32 * max(ng, 1))(*(gfr or [0]))),
-                )
-            elif group_row0 is not None:
-                r0 = [int(v) for v in group_row0]
-                ng = len(r0) - 1
-                gfr = [max(int(n) for n in n_frames[r0[g] : r0[g + 1]]) if r0[g + 1] > r0[g] else 0 for g in range(ng)]
-                _lib.check(
-                    self.lib,
-                    self.lib.vtts_nat_acoustic_forward_groups(self._h, _ptr(tok_d), _ptr(len_d), _ptr(dur_d), _ptr(nf_d), B, Lmax, Fmax, _ptr(keep_d), _ptr(out),
-                                                              _ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream), ng,
-                                                              (C.c_int32 * (ng + 1))(*r0), (C.c_int32 * ng)(*gfr)),
-                )
+                self._on_stream("forward_from_encoder", ptr(encoded), *args, tail=groups)
             else:
-                _lib.check(
-                    self.lib,
-                    self.lib.vtts_nat_acoustic_forward(self._h, _ptr(tok_d), _ptr(len_d), _ptr(dur_d), _ptr(nf_d), B, Lmax, Fmax, _ptr(keep_d), _ptr(out),
-                                                       _ptr(self._ws), self._ws.numel(), C.c_void_p(stream.cuda_stream)),
-                )
+                self._on_stream("forward_groups", ptr(tok_d), *args, tail=groups)
         if not to_host:
             return out
         host = out.cpu().numpy()
