@@ -117,8 +117,8 @@ int main(int argc, char** argv) {
     const BPackGeom g = pair_g_pack_geom(C, K);
     const size_t pb = bf16_packed_bytes(g);
     std::vector<unsigned short> wp(pb);  // 2 * pb bytes
-    bf16_pack(w1.data(), C, g, wp.data());
-    bf16_pack(w2.data(), C, g, wp.data() + pb / 2);
+    pair_g_pack(w1.data(), C, K, wp.data());
+    pair_g_pack(w2.data(), C, K, wp.data() + pb / 2);
 
     unsigned short *dx, *dy, *dwp, *dxt;
     float *dbias, *dw1, *dw2, *dyref;

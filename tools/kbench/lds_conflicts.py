@@ -35,6 +35,24 @@ def blocked_off(SPR):
     return lambda row, slot: (row >> 4) * SPR * 256 + (slot << 8) + ((row & 15) << 4)
 
 
+def blk16_off(SPR):
+    """bf16_common.h::swz_of<SPR, 16>: the image of the tiles whose loops read 16x16x32 B fragments (row-major tiles only)"""
+    return lambda row, slot: row * SPR * 16 + ((slot ^ ((row & 7) | ((row & 1) << 3))) << 4)
+
+
+def check16(SPR, off):
+    """the 16x16x32 kernel's accesses: B-fragment reads (lane -> row r0 + (l & 15), slot 4*ks + (l >> 4)), epilogue writes after swap_pair16
+    (lane -> row r0 + 16*((l >> 4) & 1) + (l & 15), slot s0 + (l >> 5)) and the row-major staging writes"""
+    rd = wr = st = 0
+    for r0 in range(64):
+        for ks in range(SPR // 4):
+            rd += conflicts([off(r0 + (l & 15), 4 * ks + (l >> 4)) for l in range(64)], RG, 16)
+        for s0 in range(0, SPR, 2):
+            wr += conflicts([off(r0 + 16 * ((l >> 4) & 1) + (l & 15), s0 + (l >> 5)) for l in range(64)], WG, 8)
+        st += conflicts([off(r0 + l // SPR, l % SPR) for l in range(64)], WG, 8)
+    return rd, wr, st
+
+
 def check(SPR, off, stage_blocked):
     rd = wr = st = 0
     for r0 in range(64):
@@ -57,4 +75,5 @@ if __name__ == "__main__":
         if SPR <= 8:
             print(f"   blocked {check(SPR, blocked_off(SPR), True)}")
         else:
-            print()
+            print(f"   | 16x16x32 accesses: XOR swizzle {check16(SPR, xor_off(SPR))}   16-block image {check16(SPR, blk16_off(SPR))}"
+                  f"   | 32x32x16 accesses on the 16-block image {check(SPR, blk16_off(SPR), False)}")

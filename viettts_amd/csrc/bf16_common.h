@@ -36,6 +36,14 @@ __device__ __forceinline__ void swap_pair(unsigned& pd, unsigned& qd) {
     pd = r[0];
     qd = r[1];
 }
+// The same across 16-lane rows (v_permlane16_swap): the odd rows of pd change places with the even rows of qd.  In the 16x16x32 accumulator layout a
+// lane of row g holds channels 4 g + i of column (lane & 15); with pd = the two packed pairs' dword of column block 2j and qd = that of block 2j + 1,
+// rows 0 / 2 own channels 0-7 / 8-15 of block 2j's column afterwards and rows 1 / 3 those of block 2j + 1's, as [P'0 P'1 Q'0 Q'1].
+__device__ __forceinline__ void swap_pair16(unsigned& pd, unsigned& qd) {
+    auto r = __builtin_amdgcn_permlane16_swap(pd, qd, false, false);
+    pd = r[0];
+    qd = r[1];
+}
 // Keep hipcc from sinking a k-step's look-ahead loads to their uses (it does, to save registers: the first build waited for every fragment right
 // in front of the MFMA that consumes it) and spread them between the step's NMF MFMAs: one MFMA, then the next pending of NA A loads (VMEM) or
 // NB B reads (DS).
@@ -134,8 +142,15 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;
 }
 
-template <int SPR>
+// BLK = 16 (row-major tiles only): the image of the kernels that read 16x16x32 B fragments (ds_read_b128: 16 consecutive rows x 4 slots).  With
+// row & 15 that read is 2-way conflicted whenever its first row is odd; (row & 7) | ((row & 1) << 3) serves it at every row offset, and the
+// epilogue's 8-consecutive-row writes and the staging writes as well (tools/kbench/lds_conflicts.py).  It is 2-way for the 32x32x16 read.
+template <int SPR, int BLK = 32>
 __device__ __forceinline__ int swz_of(int row) {
+    if constexpr (BLK == 16) {
+        static_assert(SPR >= 16, "the 16-block image is a row-major image");
+        return (row & 7) | ((row & 1) << 3);
+    }
     constexpr int RPB = SPR >= 16 ? 1 : 16 / SPR;
     constexpr int MASK = (SPR >= 16 ? 16 : SPR) - 1;
     return (row / RPB) & MASK;
@@ -152,9 +167,9 @@ __device__ __forceinline__ int swz_of(int row) {
 //     profiles/r02_b_pmc_bf16.md).  These tiles are stored in blocks of 16 rows, slot-major inside a block: a block's 16 rows
 //     of one slot are one 256-byte LDS line, so any 16 rows that are distinct mod 16 (a read group) and any 8 consecutive rows
 //     (a write group) hit distinct banks.  Tile rows are allocated in multiples of 16.
-template <int SPR>
+template <int SPR, int BLK = 32>
 __device__ __forceinline__ int tile_off(int row, int slot) {
-    if constexpr (SPR >= 16) return row * (SPR * 16) + ((slot ^ swz_of<SPR>(row)) << 4);
+    if constexpr (SPR >= 16) return row * (SPR * 16) + ((slot ^ swz_of<SPR, BLK>(row)) << 4);
     else return (row >> 4) * (SPR * 256) + (slot << 8) + ((row & 15) << 4);
 }
 constexpr int tile_rows16(int rows) { return (rows + 15) / 16 * 16; }

@@ -1262,8 +1262,8 @@ VTTS_API int vtts_hifigan_pack(vtts_hifigan* h, void* dev_blob, size_t blob_byte
             const Layer& c2 = h->layers[i + 1];
             const BPackGeom pg = pair_g_pack_geom(c1.cin, c1.k);
             const size_t half = bf16_packed_bytes(pg);
-            bf16_pack(c1.w.data(), c1.cin, pg, reinterpret_cast<unsigned short*>(host.data() + c1.off_pw));
-            bf16_pack(c2.w.data(), c2.cin, pg, reinterpret_cast<unsigned short*>(host.data() + c1.off_pw + half));
+            pair_g_pack(c1.w.data(), c1.cin, c1.k, reinterpret_cast<unsigned short*>(host.data() + c1.off_pw));  // in its class's fragment order
+            pair_g_pack(c2.w.data(), c2.cin, c1.k, reinterpret_cast<unsigned short*>(host.data() + c1.off_pw + half));
             float* pb = reinterpret_cast<float*>(host.data() + c1.off_pb);
             memcpy(pb, c1.b.data(), c1.cin * sizeof(float));
             memcpy(pb + c1.cin, c2.b.data(), c1.cin * sizeof(float));

@@ -367,11 +367,6 @@ const char* bf16_kernel_name(int cls, int K) {
     return buf;
 }
 
-size_t bf16_packed_bytes(const BPackGeom& g) {
-    const int ncc = g.cinp / g.ckc, nsl = (g.ks + g.tg - 1) / g.tg;
-    return (size_t)(g.coutp / g.mt) * ncc * nsl * ((size_t)g.mt * g.tg * g.ckc * 2);
-}
-
 // Wc: conv weights [KS][cin_real][coutp] fp32 (Haiku layout).  Output: [mtile][cc][slab] slabs, each
 // [tj][ks][mblk][lane][8] bf16 with  row = mblk*32 + (lane&31),  k = ks*16 + 8*(lane>>5) + e.
 void bf16_pack(const float* Wc, int cin_real, const BPackGeom& g, unsigned short* out) {

@@ -37,17 +37,32 @@
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "bf16_common.h"
 
 namespace vtts {
 
+// f(integral_constant<int, 0>{}), ..., f(integral_constant<int, N - 1>{}): a loop whose index is a constant expression in the body (register ring slots)
+template <class F, int... I>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
 constexpr int XCD_MAP_MIN_TILES = 192;  // XCD-aware tile order from this many tiles per utterance slot on (resblock_pair_g_bf16_k)
 
-template <int C_, int KS_, int N1_, int WM_, int WN_, int PA_, int MINWG_, int XC_ = C_>
+// BLK_: the MFMA block shape of the two convolution loops, 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (see g_mfma_blk below).
+// It is the LAST parameter: rocprofv3's kernel names are matched by their prefix up to KS (pair_g_kernel_name).
+template <int C_, int KS_, int N1_, int WM_, int WN_, int PA_, int MINWG_, int XC_ = C_, int BLK_ = 32>
 struct GTile {
-    static constexpr int C = C_, KS = KS_, N1 = N1_, WM = WM_, WN = WN_, PA = PA_, MINWG = MINWG_;
+    static constexpr int C = C_, KS = KS_, N1 = N1_, WM = WM_, WN = WN_, PA = PA_, MINWG = MINWG_, BLK = BLK_;
     static constexpr int XC = XC_, NXC = C / XC;        // the X tile is staged XC input channels at a time (C = 256: 2 x 128)
+    // BLK = 16: a wave's 64 x (N1 / WN) tile as MR16 x NR16 blocks of 16 x 16; the loop's unit is one k = 32 step over 4 column blocks
+    static constexpr int MR16 = C / WM / 16, NR16 = N1 / WN / 16, NH = NR16 / 4;
+    static constexpr int KS32 = C / 32, KSX32 = XC / 32;  // k = 32 steps per tap: of the convolution / of one X channel chunk
+        static constexpr int LA16 = 3, RA16 = LA16 + 1;      // weight look-ahead in k = 32 steps and its register ring
+    static_assert(BLK == 32 || BLK == 16, "MFMA block shape");
+    static_assert(BLK == 32 || (XC >= 128 && C / WM == 64 && (N1 / WN) % 64 == 0 && KSX32 % 4 == 0 && 4 % RA16 == 0), "16-block tiles: C >= 128, 64-row wave tiles");
     static constexpr int THREADS = 64 * WM * WN;
     static constexpr int MR = C / WM / 32, NR = N1 / WN / 32;
     static constexpr int H2 = (KS - 1) / 2;             // c2 halo (rate 1); c1's is H2 * rate
@@ -112,6 +127,10 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     constexpr int THREADS = T::THREADS, MR = T::MR, NR = T::NR, H2 = T::H2, NT2 = T::NT2;
     constexpr int SPR1 = T::SPR1, P1 = T::P1, SPR2 = T::SPR2, P2 = T::P2, XC = T::XC, NXC = T::NXC, KSX = T::KSX;
     constexpr int KSTEPS = T::KSTEPS, NQT = T::NQT, MB = T::MB, XPT = T::XPT;
+    constexpr int BLK = T::BLK;
+    constexpr bool B16 = BLK == 16;
+    constexpr int MR16 = T::MR16, NR16 = T::NR16, NH = T::NH;
+    static_assert(!B16 || (!T::RAWRES && !T::TAIL && !T::WREG && !T::UNROLL_ALL), "16-block tiles are the rolled-loop C >= 128 tiles");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* xt = lds;  // X tile, later the xt tile
@@ -124,6 +143,8 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     const int wn = wave % WN;
     const int l31 = lane & 31;
     const int lh = lane >> 5;
+    const int l15 = lane & 15;  // B16: the lane's column in a 16 x 16 block
+    const int lg = lane >> 4;   //      its row group: rows (channels) 4 lg + i of the block, k = 8 lg + j of a fragment
     const int b = a.zrev ? (int)(gridDim.z - 1 - blockIdx.z) : (int)blockIdx.z;
     const int Lp = a.L;                                      // rows allocated per utterance
     const int L = a.lens ? min(max(a.lens[b], 0) * a.len_mul, a.L) : a.L;  // valid rows of this utterance, clamped to its slot (ragged batch: the rest reads as zero padding)
@@ -155,11 +176,19 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     // 32*mr + 8*rq + 4*lh + i of this wave's m-block, r = 4*rq + i; the same for every column block) as their C operand, so
     // there is no accumulator initialisation at all (it was 128 v_mov per convolution and wave, on the issue port the
     // co-resident workgroup's MFMAs need).
-    f32x16 acc[MR][NR];
-    f32x16 bblk[MR];
+    // B16: one f32x4 per 16-channel block (rows 4 lg + i), copied into the accumulators in front of the loop (conv_phase16).
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x16 acc[B16 ? 1 : MR][B16 ? 1 : NR];
+    f32x16 bblk[B16 ? 1 : MR];
+    f32x4 acc16[B16 ? MR16 : 1][B16 ? NR16 : 1];
+    f32x4 bblk16[B16 ? MR16 : 1];
     auto load_bias = [&](const float* __restrict__ bias) {  // requested a phase ahead of the MFMAs that consume it
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         typedef float f32x8 __attribute__((ext_vector_type(8)));
+        if constexpr (B16) {
+#pragma unroll
+            for (int mr = 0; mr < MR16; ++mr) bblk16[mr] = *reinterpret_cast<const f32x4*>(bias + wm * (C / T::WM) + mr * 16 + 4 * lg);
+            return;
+        }
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr) {
             const float* __restrict__ bp = bias + wm * (C / T::WM) + mr * 32 + 4 * lh;
@@ -209,11 +238,11 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         constexpr int RW = 64 / SPR1;  // rows per wave and unit
         const int row0 = SPR1 >= 16 ? tid / SPR1 : wave * RW + lane % RW, c = SPR1 >= 16 ? tid % SPR1 : lane / RW;
         auto act2 = [](unsigned u) { return lrelu01_pack(bf16_lo(u), bf16_hi(u)); };  // LRELU_SLOPE, model.py:5,46
-        unsigned char* const lds0 = xt + tile_off<SPR1>(row0, c);  // unit i: + i * RPI * P1 (RPI is a multiple of 16: same swizzle / same place in its block)
+        unsigned char* const lds0 = xt + tile_off<SPR1, BLK>(row0, c);  // unit i: + i * RPI * P1 (RPI is a multiple of 16: same swizzle / same place in its block)
         // T::RAWRES: X-tile row r holds time t0 - H2 - h1 + r; rows of times t0 .. t0 + N1 - 1 also go, un-activated, to the residual region
         [[maybe_unused]] auto keep_raw = [&](int r, int cc, const uint4& raw, bool live) {
             const int rr = r - H2 - h1;
-            if (live && rr >= 0 && rr < N1) *reinterpret_cast<uint4*>(xraw + tile_off<SPR1>(rr, cc)) = raw;
+            if (live && rr >= 0 && rr < N1) *reinterpret_cast<uint4*>(xraw + tile_off<SPR1, BLK>(rr, cc)) = raw;
         };
         if (tx0 >= 0 && tx0 + XPT * RPI <= L) {
             // interior tile (all but the first / last of an utterance): no clamping, no masking, constant strides
@@ -301,7 +330,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
                 const int row = rowbase0 + tap * dl + nr * 32;
-                bf[par][nr] = *reinterpret_cast<const bf16x8*>(xt + tile_off<SPRB>(row, ks * 2 + lh));
+                bf[par][nr] = *reinterpret_cast<const bf16x8*>(xt + tile_off<SPRB, BLK>(row, ks * 2 + lh));
             }
         };
         auto mfma_step = [&](int slot, int par, bool first) {
@@ -372,7 +401,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                     tapaddr = (unsigned)row * PB;
                     xs = (unsigned)(swz_of<SPRB>(row) ^ lh) << 4;
                 } else {  // blocked tile: slot 2*ks + lh is 512*ks + 256*lh bytes into the row's block
-                    tapaddr = (unsigned)tile_off<SPRB>(row, lh);
+                    tapaddr = (unsigned)tile_off<SPRB, BLK>(row, lh);
                     xs = 0;
                 }
             };
@@ -411,7 +440,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         auto load_b = [&](int q, int par) {
             const int tap = q / KSTEPS, ks = q % KSTEPS;
 #pragma unroll
-            for (int nr = 0; nr < NR; ++nr) bf[par][nr] = *reinterpret_cast<const bf16x8*>(xt + tile_off<SPRB>(rowbase0 + tap * dl + nr * 32, ks * 2 + lh));
+            for (int nr = 0; nr < NR; ++nr) bf[par][nr] = *reinterpret_cast<const bf16x8*>(xt + tile_off<SPRB, BLK>(rowbase0 + tap * dl + nr * 32, ks * 2 + lh));
         };
         load_b(0, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
@@ -430,6 +459,100 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         }
     };
 
+
+    // ---- the same pass on v_mfma_f32_16x16x32_bf16 (T::BLK = 16) -------------------------------------------------------------
+    // The C >= 128 loops run at the matrix pipe's rate in cycles and are held back by the clock the chip keeps under their load; it keeps a higher one
+    // on this block shape (profiles/mfma16_pair_findings.md).  A wave's 64 x (N1 / WN) tile is MR16 = 4 x NR16 blocks.  A whole k = 32 step (4 A + 8 B
+    // fragments, 32 MFMAs, double-buffered B) does not fit the registers, so the loop's unit is a COLUMN HALF of a step: 16 MFMAs over 4 column
+    // blocks, behind them the 4 ds_read_b128 of the next unit and the unit's share of the 4 weight fragments of the step LA16 steps ahead.
+    // A fragment (tap, ks, mblk): 16 bytes per lane at  wconv + (((tap*KS32 + ks0 + ks)*(C/16) + wm*4 + mr)*64 + lane)*16   (pair_g_pack)
+    // B fragment (tap, ks, nr):   tile row  n + tap*dl  (n = 16 nr + l15), 16-byte slot 4*ks + lg of that row
+    const int rowbase16 = wn * (N1 / WN) + l15;
+    auto conv_phase16 = [&](const unsigned char* __restrict__ wconv, int dl, auto sprb_tag, auto nks_tag, int ks0, auto fresh_tag) {
+        constexpr int SPRB = decltype(sprb_tag)::value, PB = SPRB * 16, NKS = decltype(nks_tag)::value;  // NKS: this pass's k = 32 steps per tap
+        constexpr bool FRESH = decltype(fresh_tag)::value;
+        constexpr int NSTEPS = KS * NKS, LA = T::LA16, RA = T::RA16, UB = 4, APU = MR16 / NH;  // APU: A fragments loaded per unit
+        static_assert(NKS % UB == 0 && UB % RA == 0 && (UB * NH) % 2 == 0, "ring slot / B parity must be compile-time in the block loop");
+        const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(wconv), 0, (int)T::CONV_BYTES, 0x00020000);
+        const unsigned a_voff = (unsigned)((wm * MR16) * 64 + lane) * 16;
+        bf16x8 af[RA][MR16], bf[2][4];
+        auto load_a = [&](int sa, auto h_tag, auto slot_tag) {  // flat step sa of this pass (may run past the end: re-read the last step)
+            constexpr int h = decltype(h_tag)::value, slot = decltype(slot_tag)::value;
+            const int sc = sa < NSTEPS ? sa : NSTEPS - 1;
+            const int tap = sc / NKS, ks = sc - tap * NKS;
+            const int soff = ((tap * T::KS32 + ks0 + ks) * (C / 16)) * 1024;
+#pragma unroll
+            for (int m = h * APU; m < (h + 1) * APU; ++m) af[slot][m] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, a_voff + m * 1024, soff, 0));
+        };
+        auto tap_terms = [&](int tap, unsigned& tapaddr, unsigned& xs) {
+            const int row = rowbase16 + tap * dl;
+            tapaddr = (unsigned)row * PB;
+            xs = (unsigned)(swz_of<SPRB, 16>(row) ^ lg) << 4;  // the same for rows 16 apart
+        };
+        auto load_b = [&](unsigned tapaddr, unsigned xs, int ks, int h, auto par_tag) {
+            const unsigned addr = tapaddr + (xs ^ (unsigned)(ks << 6));
+#pragma unroll
+            for (int nr = 0; nr < 4; ++nr) bf[decltype(par_tag)::value][nr] = *reinterpret_cast<const bf16x8*>(xt + addr + (4 * h + nr) * 16 * PB);
+        };
+        auto pin_unit = [&]() {  // pin_step's rule: an MFMA, then the memory instruction due.  The LDS fragments first: they are due one unit on
+            int done = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                const int upto = (i + 1) * (4 + APU) / 16;
+#pragma unroll
+                for (; done < upto; ++done) {
+                    if (done < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+            }
+        };
+        unsigned ta0, xs0;
+        tap_terms(0, ta0, xs0);
+        static_for(std::make_integer_sequence<int, LA * NH>{}, [&](auto v) {
+            constexpr int s = decltype(v)::value / NH, h = decltype(v)::value % NH;
+            load_a(s, std::integral_constant<int, h>{}, std::integral_constant<int, s % RA>{});
+        });
+        load_b(ta0, xs0, 0, 0, std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_group_barrier(0x020, MR16 * LA, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+        auto block = [&](int s0) {  // UB steps of one tap
+            const int tap = s0 / NKS, ksb = s0 - tap * NKS;
+            unsigned ta, xs, tn, xn;
+            tap_terms(tap, ta, xs);
+            const bool wrap = ksb + UB >= NKS;  // the block's last look-ahead B fragments are the next tap's first
+            const int tapn = tap + 1 < KS ? tap + 1 : KS - 1;
+            tap_terms(wrap ? tapn : tap, tn, xn);
+            const int ksn = wrap ? 0 : ksb + UB;
+            static_for(std::make_integer_sequence<int, UB * NH>{}, [&](auto v) {
+                constexpr int u = decltype(v)::value, i = u / NH, h = u % NH;
+                load_a(s0 + i + LA, std::integral_constant<int, h>{}, std::integral_constant<int, (i + LA) % RA>{});
+                constexpr auto par = std::integral_constant<int, (u + 1) & 1>{};
+                if constexpr (h + 1 < NH) load_b(ta, xs, ksb + i, h + 1, par);
+                else if constexpr (i + 1 < UB) load_b(ta, xs, ksb + i + 1, 0, par);
+                else load_b(tn, xn, ksn, 0, par);
+                // column block outermost: the unit's last fragment read is first needed 12 MFMAs into the next unit
+#pragma unroll
+                for (int nr = 0; nr < 4; ++nr)
+#pragma unroll
+                    for (int mr = 0; mr < MR16; ++mr)
+                        acc16[mr][4 * h + nr] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i % RA][mr], bf[u & 1][nr], acc16[mr][4 * h + nr], 0, 0, 0);
+                pin_unit();
+            });
+        };
+        // The bias block as the first step's C operand (as in the 32-block loop) needs that step's block peeled, and the peeled copy — ring full, bias
+        // block live, 128 MFMAs of straight-line code — spilled 43 - 69 VGPRs on the wide tiles.  So the accumulators start as copies of it: 128 v_mov
+        // per pass against 704 - 2816 MFMAs.
+        if constexpr (FRESH) {
+#pragma unroll
+            for (int mr = 0; mr < MR16; ++mr)
+#pragma unroll
+                for (int nr = 0; nr < NR16; ++nr) acc16[mr][nr] = bblk16[mr];
+        }
+#pragma nounroll
+        for (int s0 = 0; s0 < NSTEPS; s0 += UB) block(s0);
+    };
+
     // ---------------- phase 1: xt = c1(lrelu(x)); column n <-> xt time t0 - H2 + n; tap j reads X row n + j*dil ----------------
 #pragma unroll
     for (int xc = 0; xc < NXC; ++xc) {
@@ -438,7 +561,10 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             stage_x(xc, std::integral_constant<int, 4>{});
             __syncthreads();
         }
-        if constexpr (T::WREG)
+        if constexpr (B16) {
+            if (xc == 0) conv_phase16(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, T::KSX32>{}, 0, std::true_type{});
+            else conv_phase16(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, T::KSX32>{}, xc * T::KSX32, std::false_type{});
+        } else if constexpr (T::WREG)
             conv_phase_wreg(dil, std::integral_constant<int, SPR1>{});
         else if (xc == 0)
             conv_phase(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, KSX>{}, 0, std::true_type{});
@@ -455,7 +581,29 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 
     // ---------------- epilogue 1: LeakyReLU(0.1), bf16, zero outside [0, L) -> xt tile in LDS ----------------
     load_bias(a.bias + C);  // c2's bias: lands while epilogue 1 runs
+    // B16: a lane holds channels 4 lg + i of column l15 of a 16 x 16 block; after swap_pair16 over the column blocks 2j, 2j + 1 row groups 0 / 2 own
+    // channels 0-7 / 8-15 of block 2j's column and groups 1 / 3 those of block 2j + 1's: the same 16-byte slots of 32 consecutive rows as above
+    [[maybe_unused]] const int col16 = wn * (N1 / WN) + 16 * (lg & 1) + l15;  // + 32 j: the tile row (time) this lane owns after the swap
     {
+        if constexpr (B16) {
+#pragma unroll
+            for (int mr = 0; mr < MR16; ++mr) {
+                const int cb = wm * (C / T::WM) + mr * 16;
+#pragma unroll
+                for (int j = 0; j < NR16 / 2; ++j) {
+                    const int tp = t0 - H2 + wn * (N1 / WN) + 32 * j + l15, tq = tp + 16;  // the columns of the lane's own accumulators
+                    unsigned p0 = lrelu01_pack(acc16[mr][2 * j][0], acc16[mr][2 * j][1]);
+                    unsigned p1 = lrelu01_pack(acc16[mr][2 * j][2], acc16[mr][2 * j][3]);
+                    unsigned q0 = lrelu01_pack(acc16[mr][2 * j + 1][0], acc16[mr][2 * j + 1][1]);
+                    unsigned q1 = lrelu01_pack(acc16[mr][2 * j + 1][2], acc16[mr][2 * j + 1][3]);
+                    if (!(tp >= 0 && tp < L)) p0 = p1 = 0u;  // c2's own zero padding applies to xt
+                    if (!(tq >= 0 && tq < L)) q0 = q1 = 0u;
+                    swap_pair16(p0, q0);
+                    swap_pair16(p1, q1);
+                    *reinterpret_cast<uint4*>(xt + tile_off<SPR2, BLK>(col16 + 32 * j, (cb >> 3) + (lg >> 1))) = make_uint4(p0, p1, q0, q1);
+                }
+            }
+        } else {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr) {
 #pragma unroll
@@ -475,21 +623,24 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                     swap_pair(p0, q0);
                     swap_pair(p1, q1);
                     const int slot = (cb >> 3) + lh;
-                    *reinterpret_cast<uint4*>(xt + tile_off<SPR2>(row, slot)) = make_uint4(p0, p1, q0, q1);
+                    *reinterpret_cast<uint4*>(xt + tile_off<SPR2, BLK>(row, slot)) = make_uint4(p0, p1, q0, q1);
                 }
             }
+        }
         }
         // rows N1 .. N1 + 2*H2 - 1 are only read by the discarded output columns: keep them finite
         for (int u = tid; u < 2 * H2 * SPR2; u += THREADS) {
             const int row = N1 + u % (2 * H2), c = u / (2 * H2);  // consecutive lanes: consecutive rows of one slot (conflict-free in the blocked tiles)
-            *reinterpret_cast<uint4*>(xt + tile_off<SPR2>(row, c)) = make_uint4(0u, 0u, 0u, 0u);
+            *reinterpret_cast<uint4*>(xt + tile_off<SPR2, BLK>(row, c)) = make_uint4(0u, 0u, 0u, 0u);
         }
     }
     __syncthreads();  // B3: xt tile written
     VTTS_TL(a, wg_lin, 3);
 
     // ---------------- phase 2: c2 over the xt tile (rate 1): column n <-> time t0 + n, tap j reads xt row n + j ----------------
-    if constexpr (T::WREG)
+    if constexpr (B16)
+        conv_phase16(static_cast<const unsigned char*>(a.wp) + T::CONV_BYTES, 1, std::integral_constant<int, SPR2>{}, std::integral_constant<int, T::KS32>{}, 0, std::true_type{});
+    else if constexpr (T::WREG)
         conv_phase_wreg(1, std::integral_constant<int, SPR2>{});
     else
         conv_phase(static_cast<const unsigned char*>(a.wp) + T::CONV_BYTES, 1, std::integral_constant<int, SPR2>{}, std::integral_constant<int, KSTEPS>{}, 0, std::true_type{});
@@ -503,6 +654,31 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         unsigned short* __restrict__ yg = static_cast<unsigned short*>(a.y) + (size_t)b * Lp * C;
         // rows of a [B][L][C] tensor in the swapped accumulator layout: all requests first, one wait
         auto add_rows = [&](const unsigned short* __restrict__ src) {
+            if constexpr (B16) {
+                uint4 rv[MR16][NR16 / 2];
+#pragma unroll
+                for (int mr = 0; mr < MR16; ++mr)
+#pragma unroll
+                    for (int j = 0; j < NR16 / 2; ++j) {
+                        const int t = t0 + col16 + 32 * j;
+                        const int tc = t < 0 ? 0 : (t < L ? t : L - 1);  // rows outside the utterance are never stored: any in-bounds address will do
+                        rv[mr][j] = *reinterpret_cast<const uint4*>(src + (size_t)tc * C + wm * (C / T::WM) + mr * 16 + 8 * (lg >> 1));
+                    }
+#pragma unroll
+                for (int mr = 0; mr < MR16; ++mr)
+#pragma unroll
+                    for (int j = 0; j < NR16 / 2; ++j) {
+                        uint4 r = rv[mr][j];
+                        swap_pair16(r.x, r.z);  // un-swap the chunk into the accumulator layout
+                        swap_pair16(r.y, r.w);
+                        f32x4& ap = acc16[mr][2 * j];
+                        f32x4& aq = acc16[mr][2 * j + 1];
+                        ap[0] = vadd_raw(bf16_lo(r.x), ap[0]); ap[1] = vadd_raw(bf16_hi(r.x), ap[1]);
+                        ap[2] = vadd_raw(bf16_lo(r.y), ap[2]); ap[3] = vadd_raw(bf16_hi(r.y), ap[3]);
+                        aq[0] = vadd_raw(bf16_lo(r.z), aq[0]); aq[1] = vadd_raw(bf16_hi(r.z), aq[1]);
+                        aq[2] = vadd_raw(bf16_lo(r.w), aq[2]); aq[3] = vadd_raw(bf16_hi(r.w), aq[3]);
+                    }
+            } else {
             uint4 rv[MR][2][NR];
 #pragma unroll
             for (int mr = 0; mr < MR; ++mr)
@@ -534,6 +710,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                         acc[mr][nr][r0 + 4] = vadd_raw(bf16_lo(r.z), acc[mr][nr][r0 + 4]); acc[mr][nr][r0 + 5] = vadd_raw(bf16_hi(r.z), acc[mr][nr][r0 + 5]);
                         acc[mr][nr][r0 + 6] = vadd_raw(bf16_lo(r.w), acc[mr][nr][r0 + 6]); acc[mr][nr][r0 + 7] = vadd_raw(bf16_hi(r.w), acc[mr][nr][r0 + 7]);
                     }
+            }
         };
         if constexpr (T::RAWRES) {                                          // x = xt + x        (model.py:50), rows from the LDS copy
 #pragma unroll
@@ -543,7 +720,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 #pragma unroll
                     for (int nr = 0; nr < NR; ++nr) {
                         const int col = wn * (N1 / WN) + nr * 32 + l31;
-                        uint4 r = *reinterpret_cast<const uint4*>(xraw + tile_off<SPR1>(col, (wm * (C / T::WM) + mr * 32 + 16 * p) / 8 + lh));
+                        uint4 r = *reinterpret_cast<const uint4*>(xraw + tile_off<SPR1, BLK>(col, (wm * (C / T::WM) + mr * 32 + 16 * p) / 8 + lh));
                         swap_pair(r.x, r.z);
                         swap_pair(r.y, r.w);
                         const int r0 = 8 * p;
@@ -557,6 +734,37 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         }
         if (a.acc_add != 0) add_rows(yg);                                   // xs += rb(x)       (model.py:118-120)
         VTTS_TL(a, wg_lin, 12);
+        if constexpr (B16) {
+#pragma unroll
+            for (int mr = 0; mr < MR16; ++mr) {
+                const int cb = wm * (C / T::WM) + mr * 16;
+#pragma unroll
+                for (int j = 0; j < NR16 / 2; ++j) {
+                    const int row = col16 + 32 * j;
+                    const int t = t0 + row;
+                    const bool ok = row < NT2 && t >= 0 && t < L;
+                    float v[8];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[e] = acc16[mr][2 * j][e];
+                        v[4 + e] = acc16[mr][2 * j + 1][e];
+                    }
+                    if (dv != 1.0f) {  // x = xs / num_kernels  (model.py:121)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] = v[e] * rdv;
+                    }
+                    if (s_out != 1.0f) {  // the (only) consumer's LeakyReLU, applied once by the producer
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] = lrelu_f(v[e], s_out);
+                    }
+                    unsigned p0 = pack_bf16x2(v[0], v[1]), p1 = pack_bf16x2(v[2], v[3]);
+                    unsigned q0 = pack_bf16x2(v[4], v[5]), q1 = pack_bf16x2(v[6], v[7]);
+                    swap_pair16(p0, q0);
+                    swap_pair16(p1, q1);
+                    if (ok) *reinterpret_cast<uint4*>(yg + (size_t)t * C + cb + 8 * (lg >> 1)) = make_uint4(p0, p1, q0, q1);
+                }
+            }
+        } else {
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr) {
 #pragma unroll
@@ -586,12 +794,13 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                         // the row stays in LDS, where this lane has just read its residual values (same row, same slot: no other lane touches it);
                         // rows outside the utterance are conv_post's zero padding
                         const uint4 o = ok ? make_uint4(p0, p1, q0, q1) : make_uint4(0u, 0u, 0u, 0u);
-                        if (row < NT2) *reinterpret_cast<uint4*>(xraw + tile_off<SPR1>(row, (cb >> 3) + lh)) = o;
+                        if (row < NT2) *reinterpret_cast<uint4*>(xraw + tile_off<SPR1, BLK>(row, (cb >> 3) + lh)) = o;
                     } else {
                         if (ok) *reinterpret_cast<uint4*>(yg + (size_t)t * C + cb + 8 * lh) = make_uint4(p0, p1, q0, q1);
                     }
                 }
             }
+        }
         }
     }
     if constexpr (T::TAIL) {
@@ -607,7 +816,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             for (int j = 0; j < T::TAIL_KS; ++j) {
 #pragma unroll
                 for (int c = 0; c < SPR1; ++c) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(xraw + tile_off<SPR1>(n + j, c));
+                    const uint4 v = *reinterpret_cast<const uint4*>(xraw + tile_off<SPR1, BLK>(n + j, c));
                     const float* w = tw + j * C + c * 8;
                     accp = fmaf(w[0], bf16_lo(v.x), accp); accp = fmaf(w[1], bf16_hi(v.x), accp);
                     accp = fmaf(w[2], bf16_lo(v.y), accp); accp = fmaf(w[3], bf16_hi(v.y), accp);
@@ -638,18 +847,26 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 #define VTTS_G128K3_N1 256
 #define VTTS_G128K3_WG 2
 #endif
-template <int KS> using G128 = GTile<128, KS, KS == 3 ? VTTS_G128K3_N1 : 256, 2, 2, 3, KS == 3 ? VTTS_G128K3_WG : 2>;
+// MFMA block shape of the pair kernel's loops per (C, KS) class: 16 where the class, measured per launch on one device against the 32-block
+// build, is faster by wall time (profiles/mfma16_pair_findings.md); C <= 64 is not clock-capped and stays on 32.  A class's wide and narrow
+// tiles carry the SAME shape (a batch row must equal the utterance run alone, bit for bit), and so does the packer (pair_g_pack below).
+constexpr int g_mfma_blk(int C, int KS) {
+    return C == 256 ? (KS == 3 ? 32 : KS == 7 ? 32 : 16)
+         : C == 128 ? (KS == 3 ? 32 : KS == 7 ? 16 : 16)
+                    : 32;
+}
+template <int KS> using G128 = GTile<128, KS, KS == 3 ? VTTS_G128K3_N1 : 256, 2, 2, 3, KS == 3 ? VTTS_G128K3_WG : 2, 128, g_mfma_blk(128, KS)>;
 template <int KS> using G64 = GTile<64, KS, VTTS_G64_N1, 1, 4, 3, VTTS_G64_WG>;
 #ifndef VTTS_G32_PA
 #define VTTS_G32_PA 3
 #endif
 template <int KS> using G32 = GTile<32, KS, VTTS_G32_N1, 1, 4, VTTS_G32_PA, VTTS_G32_WG>;
-template <int KS> using G256 = GTile<256, KS, 128, 4, 1, 3, 2, 128>;
+template <int KS> using G256 = GTile<256, KS, 128, 4, 1, 3, 2, 128, g_mfma_blk(256, KS)>;
 // narrow tiles for SMALL launches (batch-1 latency: a 512-frame utterance is 35 wide tiles at C = 256, 134 at C = 128 — a
 // fraction of the 512 workgroup slots): half the time steps per workgroup, twice the workgroups.  Same per-element
 // accumulation order (the k loop), so the samples are bit-identical to the wide tiles'.
-template <int KS> using G256S = GTile<256, KS, 64, 4, 1, 3, 2, 128>;
-template <int KS> using G128S = GTile<128, KS, 128, 2, 2, 3, 2>;
+template <int KS> using G256S = GTile<256, KS, 64, 4, 1, 3, 2, 128, g_mfma_blk(256, KS)>;
+template <int KS> using G128S = GTile<128, KS, 128, 2, 2, 3, 2, 128, g_mfma_blk(128, KS)>;
 template <int KS> using G64S = GTile<64, KS, 256, 1, 4, 3, 2>;
 template <int KS> using G32S = GTile<32, KS, 256, 1, 4, 3, 2>;
 constexpr long G_MIN_WGS = 384;  // below this many wide-tile workgroups (1.5 per CU slot pair) the narrow tile is launched
@@ -697,6 +914,14 @@ bool pair_tail_bf16_supported(int C, int K, int post_cin, int post_cout, int pos
 
 // one convolution = [q = tap*KSTEPS + ks][mblk][lane][8] bf16: bf16_pack with (ckc = C, tg = 1, mt = C)
 BPackGeom pair_g_pack_geom(int C, int K) { return BPackGeom{C, C, C, K, C, 1}; }
+
+int pair_g_mfma_blk(int C, int K) { return g_mfma_blk(C, K); }
+
+// one convolution of resblock_pair_g_bf16_k's a.wp, in the order its class's loops read (g_mfma_blk)
+void pair_g_pack(const float* Wc, int C, int K, unsigned short* out) {
+    if (g_mfma_blk(C, K) == 16) pair_g_pack16(Wc, C, K, out);
+    else bf16_pack(Wc, C, pair_g_pack_geom(C, K), out);
+}
 
 const char* pair_g_kernel_name(int C, int K) {
     static thread_local char buf[96];

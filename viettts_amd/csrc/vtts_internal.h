@@ -208,7 +208,10 @@ struct BPackGeom { int cinp, ckc, coutp, ks, mt, tg; };
 hipError_t launch_conv_bf16(int cls, int K, const BConvArgs& a, hipStream_t s);
 BPackGeom bf16_pack_geom(int cls, int K);
 const char* bf16_kernel_name(int cls, int K);
-size_t bf16_packed_bytes(const BPackGeom& g);
+inline size_t bf16_packed_bytes(const BPackGeom& g) {
+    const int ncc = g.cinp / g.ckc, nsl = (g.ks + g.tg - 1) / g.tg;
+    return (size_t)(g.coutp / g.mt) * ncc * nsl * ((size_t)g.mt * g.tg * g.ckc * 2);
+}
 void bf16_pack(const float* Wc, int cin_real, const BPackGeom& g, unsigned short* out);
 // fused ResBlock1 pair (c1 -> lrelu -> c2 -> + x): kernels_bf16_rbg.hip, weights straight from L2 into register rings, no workgroup
 // sync in the main loops.  a.wp = [c1 fragments][c2 fragments] (each packed with pair_g_pack_geom), a.bias = [b1 (C)][b2 (C)],
@@ -217,6 +220,25 @@ bool pair_bf16_supported(int C, int K, int dil);
 bool pair_tail_bf16_supported(int C, int K, int post_cin, int post_cout, int post_k);
 hipError_t launch_pair_g_bf16(int C, int K, const BConvArgs& a, hipStream_t s);
 BPackGeom pair_g_pack_geom(int C, int K);
+// resblock_pair_g_bf16_k's own weights: pair_g_pack_geom's order on the classes whose loops run 32 x 32 x 16 blocks, the 16 x 16 x 32 fragment order
+// (pair_g_pack16, same byte count) on those that run 16-blocks (pair_g_mfma_blk).  The split-operand kernels and the whole-ResBlock blob keep pair_g_pack_geom.
+int pair_g_mfma_blk(int C, int K);
+// The 16 x 16 x 32 fragment order of one convolution: [q = tap*(C/32) + ks][mblk16][lane][8] bf16 with  co = 16 mblk + (lane & 15),
+// ci = 32 ks + 8 (lane >> 4) + e.  Wc: [K][C][C] fp32 (Haiku layout: tap, input channel, output channel).  K * C * C * 2 bytes, as pair_g_pack_geom's
+// order (tools/check_pair_pack16_host.cpp checks both, stand-alone and under the sanitizers).
+inline size_t pair_g_pack16_bytes(int C, int K) { return (size_t)K * (C / 32) * (C / 16) * 64 * 8 * sizeof(unsigned short); }
+inline void pair_g_pack16(const float* Wc, int C, int K, unsigned short* out) {
+    size_t o = 0;
+    for (int tap = 0; tap < K; ++tap)
+        for (int ks = 0; ks < C / 32; ++ks)
+            for (int mblk = 0; mblk < C / 16; ++mblk)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int ci = 32 * ks + 8 * (lane >> 4) + e, co = 16 * mblk + (lane & 15);
+                        out[o++] = f32_to_bf16_rne(Wc[((size_t)tap * C + ci) * C + co]);
+                    }
+}
+void pair_g_pack(const float* Wc, int C, int K, unsigned short* out);
 const char* pair_g_kernel_name(int C, int K);
 // whole ResBlock1 in one kernel (kernels_bf16_rbk.hip): C = 32 (k = 3, 7, 11), C = 64 / 128 (k = 3)
 bool resblock_bf16_supported(int C, int K, const int* dils);
