@@ -231,6 +231,43 @@ int vtts_nat_acoustic_forward_from_encoder(vtts_nat_acoustic* h, const float* en
                                            void* workspace, size_t workspace_bytes, void* stream, int ngroups, const int32_t* group_row0,
                                            const int32_t* group_frames);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Streaming session: forward() cut along TIME, for a caller who wants the first audio before the last frame is decoded (the reference has
+ * nothing like it: vietTTS/synthesizer.py:33-39 computes the whole mel, then the whole waveform).  The decoder runs up to a frame cursor, the
+ * mel is made final (postnet + residual) for one frame window after the other, and a finished window may be vocoded while the decoder carries
+ * on.  Every kernel and every sum is forward()'s: after the last window mel_dev equals forward()'s result in every byte, and after every window
+ * the frames below its end already do.  One session per handle; B >= 1 rows, all starting at frame 0.
+ *
+ * The postnet is 5 x Conv1D(k = 5): a frame of its output reads 5 * (5 - 1) / 2 = 10 frames of the decoder's mel on either side, so a window
+ * [f0, f1) is computed on a copy of the frames [max(0, f0 - 10), min(Fmax, f1 + 10)) in a compact buffer (the convolutions bound and zero-fill
+ * their stores by the row pitch, so they are not pointed into the full rows) and only [f0, f1) is copied out.  (fp64, 75 frames: the window's
+ * interior equals the whole-row postnet to 1.3e-15 with 10 halo frames, and differs by 2.7e-2 with 9.)
+ *
+ *   stream_workspace_bytes()  workspace_bytes(h, B, Lmax, Fmax) plus the compact window buffers; max_window = the largest f1 - f0 of a finish().
+ *   stream_begin()    forward()'s arguments and checks (and mel_dev 16-byte aligned).  Enqueues the token encoder and the conditioning gates of
+ *                     ALL frames on `stream` — a session puts nothing on the handle's side stream, so no later call has an event to wait for —
+ *                     and zeroes the decoder's state and mel_dev (rows past nframes[b] are zero as after forward()).  The arrays must stay
+ *                     allocated and unchanged until the session ends.  The frame loop of a session is the per-frame launches: the option
+ *                     "resident" is ignored ("resident_used" reads 0), "stage_times" records nothing, "bf16x3" is honoured as set at begin()
+ *                     (changing it inside a session makes decode() / finish() return VTTS_ERR_STATE).  A stream that is being captured is
+ *                     refused with VTTS_ERR_INVALID.
+ *   stream_decode()   enqueues the decoder's frames [cursor, min(upto, Fmax)) and moves the cursor; upto <= cursor does nothing (VTTS_OK).
+ *   stream_finish()   mel_dev[b][f0 .. f1) = postnet + residual, for every row.  Windows come in order and contiguous: the first f0 is 0, every
+ *                     later f0 the previous f1, f1 > f0 (an f1 past Fmax counts as Fmax) and f1 - f0 <= max_window, else VTTS_ERR_INVALID; the
+ *                     cursor must have reached min(f1 + VTTS_NAT_POSTNET_HALO, Fmax), else VTTS_ERR_STATE.  A refused call enqueues nothing.
+ *   stream_end()      forgets the session (nothing is enqueued; frames not decoded stay undecoded).  forward*(), encode() and stream_begin() on
+ *                     the handle end an open session too.  decode() / finish() without a session return VTTS_ERR_STATE.
+ * The calls of a session are ordered by the stream(s) they are given: use one stream, or order them yourself.
+ */
+#define VTTS_NAT_POSTNET_HALO 10
+int vtts_nat_acoustic_stream_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, int max_window, size_t* bytes);
+int vtts_nat_acoustic_stream_begin(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
+                                   const int32_t* nframes_dev, int B, int Lmax, int Fmax, const uint8_t* keep_dev, float* mel_dev, void* workspace,
+                                   size_t workspace_bytes, int max_window, void* stream);
+int vtts_nat_acoustic_stream_decode(vtts_nat_acoustic* h, int upto, void* stream);
+int vtts_nat_acoustic_stream_finish(vtts_nat_acoustic* h, int f0, int f1, void* stream);
+int vtts_nat_acoustic_stream_end(vtts_nat_acoustic* h);
+
 #ifdef __cplusplus
 }
 #endif

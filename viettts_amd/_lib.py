@@ -151,7 +151,12 @@ SIGS = {
     "vtts_nat_acoustic_forward_teacher_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
     "vtts_nat_acoustic_forward_teacher": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, sz, vp]),
     "vtts_nat_acoustic_teacher_masks_haiku": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-    "vtts_mel_create": (C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_nat_acoustic_stream_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_nat_acoustic_stream_begin": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, C.c_int, vp]),
+    "vtts_nat_acoustic_stream_decode": (C.c_int, [vp, C.c_int, vp]),
+    "vtts_nat_acoustic_stream_finish": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "vtts_nat_acoustic_stream_end": (C.c_int, [vp]),
+    "vtts_mel_create":(C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
     "vtts_mel_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
     "vtts_mel_filterbank": (C.c_int, [vp, fp]),
     "vtts_mel_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),

@@ -56,6 +56,17 @@ struct vtts_nat_acoustic : NatModel {
     // option "stage_times": timing events on the caller's stream in front of the gate GEMM, the decoder loop, the postnet, and behind it
     int stage_times = 0, stage_valid = 0;
     hipEvent_t ev_stage[4] = {nullptr, nullptr, nullptr, nullptr};
+    // stream_begin() .. stream_end(): the caller's arrays and dimensions, how far the decoder has run (cursor) and how far the mel is final (finished)
+    struct Session {
+        bool open = false;
+        const int32_t *lengths = nullptr, *nframes = nullptr;
+        const float* durations = nullptr;
+        const uint8_t* keep = nullptr;
+        float* mel = nullptr;
+        void* workspace = nullptr;
+        size_t workspace_bytes = 0;
+        int B = 0, Lmax = 0, Fmax = 0, max_window = 0, x3 = 0, cursor = 0, finished = 0;
+    } ss;
     ~vtts_nat_acoustic() {
         for (hipEvent_t e : ev_dec) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_done) (void)hipEventDestroy(e);
@@ -1429,6 +1440,32 @@ size_t nat_enc_lstm_floats(int D, int B, int Lmax) {
     const size_t Bp = (size_t)(B + 63) / 64 * 64;
     return ((size_t)2 * Lmax + 2 * ((size_t)Lmax + 1) + 2) * D * Bp;
 }
+// A streaming session's frame window (vtts_nat_acoustic_stream_finish), in units of 4 channels.  Gather: win[b][p] = full[b][lo + p] for p < n, zeros for
+// n <= p < W, and wl[b] = clamp(nframes[b] - lo, 0, n), the row's length inside the window.  Scatter: full[b][lo + p] = win[b][p] for k0 <= p < k1 where
+// lo + p < nframes[b] (a row's frames past its end stay what the session's memset made them).
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void nat_window_k(const float4* __restrict__ src, float4* __restrict__ dst, const int* __restrict__ nframes, int* __restrict__ wl,
+                                                    int B, int Fmax, int W, int C4, int lo, int n, int k0, int k1) {
+    const size_t gtid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const int span = SCATTER ? k1 - k0 : W;
+    const size_t total = (size_t)B * span * C4;
+    for (size_t i = gtid; i < total; i += stride) {
+        const int c = (int)(i % C4), p = k0 + (int)((i / C4) % span), b = (int)(i / ((size_t)C4 * span));
+        const size_t fi = ((size_t)b * Fmax + lo + p) * C4 + c, wi = ((size_t)b * W + p) * C4 + c;
+        if constexpr (SCATTER) {
+            if (lo + p < nframes[b]) dst[fi] = src[wi];
+        } else {
+            dst[wi] = p < n ? src[fi] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if constexpr (!SCATTER) {
+        for (size_t b = gtid; b < (size_t)B; b += stride) {
+            const int r = nframes[b] - lo;
+            wl[b] = r < 0 ? 0 : (r > n ? n : r);
+        }
+    }
+}
+
 int run_token_encoder(const NatModel& m, const std::string& te, int V, int D, const int32_t* tokens, const int32_t* lengths, int B, int Lmax,
                       float* bufA, float* bufB, float* lstm_ws, float* enc, hipStream_t s) {
     hipLaunchKernelGGL(nat_embed_k, dim3(Lmax, B), dim3(256), 0, s, tokens, lengths, m.dev(te + "embed", "embeddings"), bufA, Lmax, D, V);
@@ -1537,6 +1574,20 @@ struct NatTeacherWs : NatCarver {
     NatTeacherWs(const NatAcousticWs& a, const vtts_nat_acoustic_cfg& c, int B, int Fmax) : NatCarver{a.base, a.bytes} {
         const size_t Bp = (size_t)(B + 63) / 64 * 64, H = c.decoder_dim, BF = (size_t)B * Fmax * 4;
         P1 = take(BF * c.prenet_dim), P2 = take(BF * c.prenet_dim), hseq = take(BF * 2 * H), tstate = take(7 * H * Bp * 4);
+    }
+};
+
+// what a streaming session needs behind forward()'s layout `a`: the compact window [B][W][.] of the decoder's mel, of the postnet's ping-pong buffers and of
+// its result, W = the widest window plus a halo per side, rounded up to the convolutions' 64-frame tiles, and the rows' lengths inside the window
+struct NatStreamWs : NatCarver {
+    float *wmel, *wpA, *wpB, *wout;
+    int32_t* wl;
+    int W;
+    NatStreamWs(const NatAcousticWs& a, const vtts_nat_acoustic_cfg& c, int B, int Fmax, int max_window) : NatCarver{a.base, a.bytes} {
+        W = (std::min(max_window, Fmax) + 2 * VTTS_NAT_POSTNET_HALO + 63) / 64 * 64;
+        const size_t BW = (size_t)B * W * 4;
+        wmel = take(BW * c.mel_dim), wpA = take(BW * c.postnet_dim), wpB = take(BW * c.postnet_dim), wout = take(BW * c.mel_dim);
+        wl = reinterpret_cast<int32_t*>(take((size_t)B * 4));
     }
 };
 
@@ -1885,6 +1936,14 @@ struct NatCall {
     NatAcousticWs ws;
 };
 
+// what a call's dimensions and workspace pointer give: the model's widths, the padded batch, the mix's tiles and the workspace's buffers
+void nat_derive(NatCall& c) {
+    const vtts_nat_acoustic* h = c.h;
+    c.H = h->cfg.decoder_dim, c.PN = h->cfg.prenet_dim, c.MEL = h->cfg.mel_dim, c.PD = h->cfg.postnet_dim;
+    c.E = 2 * h->cfg.encoder_dim, c.G4 = 4 * c.H, c.Bp = (c.B + 63) / 64 * 64, c.mtiles = (c.Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT;
+    c.ws = NatAcousticWs(h->cfg, c.B, c.Lmax, c.Fmax, c.workspace);
+}
+
 int nat_validate(NatCall& c) {
     vtts_nat_acoustic* h = c.h;
     if (!h || (!c.tokens && !c.enc_pre) || !c.lengths || !c.durations || !c.nframes || !c.mel) return failf(VTTS_ERR_INVALID, "null argument");
@@ -1905,9 +1964,7 @@ int nat_validate(NatCall& c) {
                 return failf(VTTS_ERR_INVALID, "group %d: rows [%d, %d), %d frames (every group needs at least one row and 1 <= frames <= Fmax = %d)", g,
                              c.group_row0[g], c.group_row0[g + 1], c.group_frames[g], c.Fmax);
     }
-    c.H = h->cfg.decoder_dim, c.PN = h->cfg.prenet_dim, c.MEL = h->cfg.mel_dim, c.PD = h->cfg.postnet_dim;
-    c.E = 2 * h->cfg.encoder_dim, c.G4 = 4 * c.H, c.Bp = (c.B + 63) / 64 * 64, c.mtiles = (c.Fmax + NAT_MIX_FT - 1) / NAT_MIX_FT;
-    c.ws = NatAcousticWs(h->cfg, c.B, c.Lmax, c.Fmax, c.workspace);
+    nat_derive(c);
     return VTTS_OK;
 }
 
@@ -1993,22 +2050,33 @@ int nat_cond_gates(const NatCall& c, int mfirst) {
 
 // postnet (:113-121) + residual (:151) of rows [r0, r1) over their first `frames` frames: 4 x (Conv1D(PD, 5) + BatchNorm + tanh),
 // Conv1D(MEL, 5), mel + .   A row's result does not depend on the launch it is part of.
-void nat_postnet(const NatCall& c, int r0, int r1, int frames, hipStream_t ps) {
+// The five launches over `nrows` rows of `pitch` positions, the first `npos` of them computed and rows[b] of them real: in = the decoder's mel (the first
+// layer's input and the residual), pp = the ping-pong buffers, out = the result.
+struct NatPostnetBufs {
+    int nrows, npos, pitch;
+    const int32_t* rows;
+    const float* in;
+    float* pp[2];
+    float* out;
+};
+void nat_postnet_run(const NatCall& c, const NatPostnetBufs& p, hipStream_t ps) {
     const vtts_nat_acoustic* h = c.h;
-    const size_t m0 = (size_t)r0 * c.Fmax * c.MEL, p0 = (size_t)r0 * c.Fmax * c.PD;
-    const float* cur = c.ws.mel0 + m0;
-    float* bufs[2] = {c.ws.pA + p0, c.ws.pB + p0};
+    const float* cur = p.in;
     for (int i = 0; i < 5; ++i) {
         const std::string sfx = i ? "_" + std::to_string(i) : "";
         const std::string cv = "conv1_d" + sfx, bn = "batch_norm" + sfx;
         const bool last = i == 4;
-        NatConv o{r1 - r0, frames, c.Fmax, c.nframes + r0, cur, last ? c.mel + m0 : bufs[i & 1], h->extra(cv + (h->x3 ? "#x3" : "#mfma")), h->dev(cv, "b"),
+        NatConv o{p.nrows, p.npos, p.pitch, p.rows, cur, last ? p.out : p.pp[i & 1], h->extra(cv + (h->x3 ? "#x3" : "#mfma")), h->dev(cv, "b"),
                   i == 0 ? c.MEL : c.PD, last ? c.MEL : c.PD, last ? (int)NAT_ACT_NONE : (int)NAT_ACT_TANH};
-        if (last) o.res = c.ws.mel0 + m0;
+        if (last) o.res = p.in;
         else o.inv = h->inv(bn), o.mean = h->dev(bn + "/~/mean_ema", "average"), o.offset = h->dev(bn, "offset");
         nat_conv<5>(o, h->x3, ps);
         cur = o.y;
     }
+}
+void nat_postnet(const NatCall& c, int r0, int r1, int frames, hipStream_t ps) {
+    const size_t m0 = (size_t)r0 * c.Fmax * c.MEL, p0 = (size_t)r0 * c.Fmax * c.PD;
+    nat_postnet_run(c, NatPostnetBufs{r1 - r0, frames, c.Fmax, c.nframes + r0, c.ws.mel0 + m0, {c.ws.pA + p0, c.ws.pB + p0}, c.mel + m0}, ps);
 }
 
 // teacher-forced decoder (model.py:146-167): everything but the two LSTMs' recurrent products ahead of the frame loop
@@ -2102,8 +2170,17 @@ int nat_resident_launch(const NatCall& c, int grid) {
     return VTTS_OK;
 }
 
-// autoregressive decoder (:134-150): per frame LSTM1, LSTM2, projection + next frame's prenet, all sentences at once
-int nat_ar_decoder(const NatCall& c) {
+// frame 0's state: h1 = h2 = 0, c = 0, prenet(0) = 0 (no biases); and a zero decoder mel: rows past a sentence's last frame stay zero
+int nat_dec_reset(const NatCall& c) {
+    HIP_TRY(hipMemsetAsync(c.ws.dstate, 0, nat_dec_state_floats(c.h->cfg, c.B) * 4, c.s));
+    HIP_TRY(hipMemsetAsync(c.ws.mel0, 0, (size_t)c.B * c.Fmax * c.MEL * 4, c.s));
+    return VTTS_OK;
+}
+
+// autoregressive decoder (:134-150), frames [fa, fb): per frame LSTM1, LSTM2, projection + next frame's prenet, all sentences at once.  The state lives in
+// the workspace between launches, its ping-pong indexed by the absolute frame's parity, so a range may start at any frame the previous one ended at.
+// gates_wait: the mix of the frames from 64 on runs on the side stream (nat_cond_gates with mfirst < mtiles) and frame 64 waits for it.
+int nat_dec_frames(const NatCall& c, int fa, int fb, bool gates_wait) {
     vtts_nat_acoustic* h = c.h;
     const NatAcousticWs& ws = c.ws;
     const int B = c.B, Bp = c.Bp, Fmax = c.Fmax, H = c.H, PN = c.PN, MEL = c.MEL, G4 = c.G4, ZW = PN + 2 * H;
@@ -2111,20 +2188,6 @@ int nat_ar_decoder(const NatCall& c) {
     float* Z[2] = {ws.dstate, ws.dstate + (size_t)ZW * Bp};
     float* c1 = ws.dstate + 2 * (size_t)ZW * Bp;
     float* c2 = c1 + (size_t)H * Bp;
-    HIP_TRY(hipMemsetAsync(ws.dstate, 0, nat_dec_state_floats(h->cfg, B) * 4, s));  // frame 0: h1 = h2 = 0, c = 0, prenet(0) = 0 (no biases)
-    HIP_TRY(hipMemsetAsync(ws.mel0, 0, (size_t)B * Fmax * MEL * 4, s));  // rows past a sentence's last frame stay zero
-    const bool stamps = h->stage_times && c.ngroups == 0;
-    h->stage_valid = 0;
-    if (stamps) {
-        for (hipEvent_t& e : h->ev_stage)
-            if (!e) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(h->ev_stage[0], s));
-    }
-    // the gates' mix for frames [0, 64) here and for the rest beside the first 64 steps; all of it here when the resident kernel will run
-    int res_grid = 0;
-    if (int rc = nat_resident_grid(c, &res_grid)) return rc;
-    const int mfirst = res_grid ? c.mtiles : std::min(64 / NAT_MIX_FT, c.mtiles);
-    if (int rc = nat_cond_gates(c, mfirst)) return rc;
     const float4 *w1 = h->extra<float4>("lstm/linear#mfma"), *w2 = h->extra<float4>("lstm_1/linear#mfma");
     const float4 *f1 = h->extra<float4>("linear_1#k4"), *f2 = h->extra<float4>("linear_2#k4"), *wp = h->extra<float4>("linear#k4");
     const float* bp = h->dev("linear", "b");
@@ -2156,11 +2219,8 @@ int nat_ar_decoder(const NatCall& c) {
         if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, f, B, Bp, H);
         else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, f, B, Bp, H);
     };
-    if (stamps) HIP_TRY(hipEventRecord(h->ev_stage[1], s));
-    if (res_grid)  // every frame's gates are on `s` already (mfirst = mtiles)
-        if (int rc = nat_resident_launch(c, res_grid)) return rc;
-    for (int f = 0; f < Fmax && !h->resident_used; ++f) {
-        if (f == 64 && c.mtiles > mfirst) HIP_TRY(hipStreamWaitEvent(s, h->ev_gates, 0));
+    for (int f = fa; f < fb; ++f) {
+        if (f == 64 && gates_wait) HIP_TRY(hipStreamWaitEvent(s, h->ev_gates, 0));
         float* zc = Z[f & 1];
         float* zp = Z[(f + 1) & 1];
         if (dx3) {
@@ -2181,8 +2241,33 @@ int nat_ar_decoder(const NatCall& c) {
     return VTTS_OK;
 }
 
+// forward()'s decoder: every frame, as the resident kernel where the option asks for it and the call allows it
+int nat_ar_decoder(const NatCall& c) {
+    vtts_nat_acoustic* h = c.h;
+    hipStream_t s = c.s;
+    if (int rc = nat_dec_reset(c)) return rc;
+    const bool stamps = h->stage_times && c.ngroups == 0;
+    h->stage_valid = 0;
+    if (stamps) {
+        for (hipEvent_t& e : h->ev_stage)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(h->ev_stage[0], s));
+    }
+    // the gates' mix for frames [0, 64) here and for the rest beside the first 64 steps; all of it here when the resident kernel will run
+    int res_grid = 0;
+    if (int rc = nat_resident_grid(c, &res_grid)) return rc;
+    const int mfirst = res_grid ? c.mtiles : std::min(64 / NAT_MIX_FT, c.mtiles);
+    if (int rc = nat_cond_gates(c, mfirst)) return rc;
+    if (stamps) HIP_TRY(hipEventRecord(h->ev_stage[1], s));
+    if (res_grid)  // every frame's gates are on `s` already (mfirst = mtiles)
+        if (int rc = nat_resident_launch(c, res_grid)) return rc;
+    if (h->resident_used) return VTTS_OK;
+    return nat_dec_frames(c, 0, c.Fmax, c.mtiles > mfirst);
+}
+
 // forward(), forward_groups(), forward_from_encoder() and forward_teacher()
 int nat_acoustic_run(NatCall& c) {
+    if (c.h) c.h->ss.open = false;  // any forward*() ends an open streaming session
     if (int rc = nat_validate(c)) return rc;
     vtts_nat_acoustic* h = c.h;
     if (int rc = nat_side_stream(h, c.ngroups)) return rc;
@@ -2245,6 +2330,7 @@ VTTS_API int vtts_nat_acoustic_forward_teacher(vtts_nat_acoustic* h, const int32
 VTTS_API int vtts_nat_acoustic_encode(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, int B, int Lmax, float* enc_dev,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !tokens_dev || !lengths_dev || !enc_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    h->ss.open = false;  // (its buffers are a session's too)
     if (!h->blob) return failf(VTTS_ERR_STATE, "encode() before pack()/bind_packed()");
     size_t need = 0;
     int rc = vtts_nat_acoustic_workspace_bytes(h, B, Lmax, 1, &need);
@@ -2277,5 +2363,98 @@ VTTS_API int vtts_nat_acoustic_wait_group(vtts_nat_acoustic* h, int group, void*
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     if (group < 0 || group >= h->groups_valid) return failf(VTTS_ERR_STATE, "wait_group(%d): the last forward_groups() call had %d groups", group, h->groups_valid);
     HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_done[group], 0));
+    return VTTS_OK;
+}
+
+// ------------------------------------------------ streaming session ------------------------------------------------
+// forward() cut along time (include/vtts_nat.h): begin = everything ahead of the frame loop, decode = a range of the loop's frames, finish = postnet +
+// residual of a frame window on a compact copy of it.  The launches and their arithmetic are forward()'s; only the postnet's tiles sit elsewhere.
+namespace {
+
+// the session's call on `stream`, or a status: no handle, no session, or the option "bf16x3" changed under it
+int nat_session_call(vtts_nat_acoustic* h, const char* what, void* stream, NatCall* c) {
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    const vtts_nat_acoustic::Session& ss = h->ss;
+    if (!ss.open) return failf(VTTS_ERR_STATE, "%s: no open session (stream_begin() first; any forward*(), encode() or stream_end() closes it)", what);
+    if (h->x3 != ss.x3) return failf(VTTS_ERR_STATE, "%s: the option bf16x3 changed since stream_begin()", what);
+    *c = NatCall{h, nullptr, ss.lengths, ss.durations, ss.nframes, ss.B, ss.Lmax, ss.Fmax, ss.keep, ss.mel, ss.workspace, ss.workspace_bytes, static_cast<hipStream_t>(stream)};
+    nat_derive(*c);
+    return VTTS_OK;
+}
+
+}  // namespace
+
+VTTS_API int vtts_nat_acoustic_stream_workspace_bytes(const vtts_nat_acoustic* h, int B, int Lmax, int Fmax, int max_window, size_t* bytes) {
+    if (int rc = vtts_nat_acoustic_workspace_bytes(h, B, Lmax, Fmax, bytes)) return rc;
+    if (max_window < 1) return failf(VTTS_ERR_INVALID, "max_window must be positive (got %d)", max_window);
+    *bytes = NatStreamWs(NatAcousticWs(h->cfg, B, Lmax, Fmax, nullptr), h->cfg, B, Fmax, max_window).bytes;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_stream_begin(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
+                                            const int32_t* nframes_dev, int B, int Lmax, int Fmax, const uint8_t* keep_dev, float* mel_dev, void* workspace,
+                                            size_t workspace_bytes, int max_window, void* stream) {
+    if (h) h->ss.open = false;
+    if (!tokens_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    NatCall c{h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    if (int rc = nat_validate(c)) return rc;
+    size_t need = 0;
+    if (int rc = vtts_nat_acoustic_stream_workspace_bytes(h, B, Lmax, Fmax, max_window, &need)) return rc;
+    if (workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes (stream_workspace_bytes())", workspace_bytes, need);
+    if ((uintptr_t)mel_dev % 16 != 0) return failf(VTTS_ERR_INVALID, "stream_begin(): mel_dev is written in 16-byte units: align it so");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(c.s, &cap));
+    if (cap != hipStreamCaptureStatusNone) return failf(VTTS_ERR_INVALID, "stream_begin(): the stream is being captured (a session's launches depend on host state)");
+    h->resident_used = 0;
+    h->stage_valid = 0;
+    if (int rc = run_token_encoder(*h, "token_encoder/~/", h->cfg.vocab_size, h->cfg.encoder_dim, c.tokens, c.lengths, c.B, c.Lmax, c.ws.bufA, c.ws.bufB, c.ws.lstm_ws, c.ws.enc, c.s)) return rc;
+    HIP_TRY(hipMemsetAsync(c.mel, 0, (size_t)c.B * c.Fmax * c.MEL * 4, c.s));  // rows past a sentence's last frame
+    if (int rc = nat_dec_reset(c)) return rc;
+    if (int rc = nat_cond_gates(c, c.mtiles)) return rc;  // every frame's mix on the caller's stream: nothing of a session runs on the side stream
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "acoustic model launch failed: %s", hipGetErrorString(e));
+    h->ss = vtts_nat_acoustic::Session{true, lengths_dev, nframes_dev, durations_dev, keep_dev, mel_dev, workspace, workspace_bytes, B, Lmax, Fmax, max_window, h->x3, 0, 0};
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_stream_decode(vtts_nat_acoustic* h, int upto, void* stream) {
+    NatCall c;
+    if (int rc = nat_session_call(h, "stream_decode()", stream, &c)) return rc;
+    const int to = std::min(upto, c.Fmax);
+    if (to <= h->ss.cursor) return VTTS_OK;
+    if (int rc = nat_dec_frames(c, h->ss.cursor, to, false)) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "decoder launch failed: %s", hipGetErrorString(e));
+    h->ss.cursor = to;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_stream_finish(vtts_nat_acoustic* h, int f0, int f1, void* stream) {
+    NatCall c;
+    if (int rc = nat_session_call(h, "stream_finish()", stream, &c)) return rc;
+    vtts_nat_acoustic::Session& ss = h->ss;
+    if (f0 != ss.finished || f1 <= f0 || f0 >= c.Fmax)
+        return failf(VTTS_ERR_INVALID, "stream_finish(%d, %d): windows are issued in order, contiguous and not empty; the next one starts at frame %d of %d", f0, f1, ss.finished, c.Fmax);
+    if (f1 - f0 > ss.max_window) return failf(VTTS_ERR_INVALID, "stream_finish(%d, %d): the session was opened for windows of at most %d frames", f0, f1, ss.max_window);
+    f1 = std::min(f1, c.Fmax);
+    const int lo = std::max(0, f0 - VTTS_NAT_POSTNET_HALO), hi = std::min(c.Fmax, f1 + VTTS_NAT_POSTNET_HALO), n = hi - lo;
+    if (ss.cursor < hi) return failf(VTTS_ERR_STATE, "stream_finish(%d, %d) reads the decoder's frames up to %d: stream_decode() has reached %d", f0, f1, hi, ss.cursor);
+    const NatStreamWs w(c.ws, h->cfg, c.B, c.Fmax, ss.max_window);
+    const int C4 = c.MEL / 4;
+    auto blocks = [](size_t elems) { return (int)std::min<size_t>((elems + 255) / 256, 65535); };
+    hipLaunchKernelGGL(nat_window_k<false>, dim3(blocks((size_t)c.B * w.W * C4)), dim3(256), 0, c.s, reinterpret_cast<const float4*>(c.ws.mel0), reinterpret_cast<float4*>(w.wmel),
+                       c.nframes, w.wl, c.B, c.Fmax, w.W, C4, lo, n, 0, 0);
+    nat_postnet_run(c, NatPostnetBufs{c.B, n, w.W, w.wl, w.wmel, {w.wpA, w.wpB}, w.wout}, c.s);
+    hipLaunchKernelGGL(nat_window_k<true>, dim3(blocks((size_t)c.B * (f1 - f0) * C4)), dim3(256), 0, c.s, reinterpret_cast<const float4*>(w.wout), reinterpret_cast<float4*>(c.mel),
+                       c.nframes, static_cast<int*>(nullptr), c.B, c.Fmax, w.W, C4, lo, n, f0 - lo, f1 - lo);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "postnet window launch failed: %s", hipGetErrorString(e));
+    ss.finished = f1;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_stream_end(vtts_nat_acoustic* h) {
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    h->ss.open = false;
     return VTTS_OK;
 }

@@ -51,15 +51,17 @@ def _run_group(gen, mel: torch.Tensor, chunks: Sequence[Chunk], out: torch.Tenso
 
 
 def synthesize_chunked(gen, mel: torch.Tensor, chunk_frames: int = 512, halo: int = HALO_FRAMES, max_batch: int = 0,
-                       rank: int = 0, world: int = 1, timing: Optional[Dict] = None) -> torch.Tensor:
+                       rank: int = 0, world: int = 1, timing: Optional[Dict] = None, chunks: Optional[Sequence[Chunk]] = None) -> torch.Tensor:
     """mel ``[T, num_mels]`` float32 on the generator's device -> ``[hop*T]`` float32 on the same
     device.  With ``world > 1`` only this rank's chunks (c mod world == rank) are computed; the other
     ranges of the result are left zero (the caller gathers or writes per-rank pieces).
-    ``timing``, if a dict, receives ``first_chunk_s`` (time to the first chunk's samples) and ``total_s``."""
+    ``timing``, if a dict, receives ``first_chunk_s`` (time to the first chunk's samples) and ``total_s``.
+    ``chunks``: a plan of the caller's own that tiles ``[0, T)`` (e.g. the chunks of ``viettts_amd.streaming.stream_plan``) instead of
+    ``plan_chunks(T, chunk_frames, halo)``."""
     if mel.dim() != 2:
         raise ValueError("mel must be [T, num_mels]")
     T = mel.shape[0]
-    chunks = shard_chunks(plan_chunks(T, chunk_frames, halo), world)[rank]
+    chunks = shard_chunks(plan_chunks(T, chunk_frames, halo) if chunks is None else list(chunks), world)[rank]
     out = torch.zeros(gen.hop * T, dtype=torch.float32, device=mel.device)
     t_start = time.perf_counter()
     # the first chunk alone first: streaming latency = time-to-first-chunk

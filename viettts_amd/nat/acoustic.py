@@ -247,6 +247,27 @@ class AcousticModel(NativeHandle):
         self._on_stream("encode", ptr(tok_d), ptr(len_d), B, Lmax, ptr(enc), ptr(ws), ws.numel())
         return enc
 
+    def _device_inputs(self, sentences, durations_frames, n_frames, Lmax: int, Fmax: int, keep_masks, dropout_seeds, dropout_rng, with_tokens: bool = True):
+        """What forward() and stream_begin() read, on the device: padded tokens (None without ``with_tokens``) and durations, lengths, frame counts and
+        the keep masks of whichever dropout argument is given (None for no dropout)."""
+        B = len(sentences)
+        tok, dur = padded_rows(sentences, durations_frames, Lmax)
+        keep_d = None
+        if keep_masks is not None:
+            keep = np.zeros((B, Fmax, 2, self.prenet_dim), dtype=np.uint8)
+            for i, m in enumerate(keep_masks):
+                keep[i, : n_frames[i]] = np.asarray(m, dtype=bool)[: n_frames[i]]
+            keep_d = torch.from_numpy(keep).to(self.device)
+        elif dropout_rng is not None:
+            keep_d = self.device_keep_masks_haiku(dropout_rng, B, Fmax)
+        elif dropout_seeds is not None:
+            keep_d = self.device_keep_masks(dropout_seeds, Fmax)
+        tok_d = torch.from_numpy(tok).to(self.device) if with_tokens else None  # (the C side ignores the tokens when the encoder's output is given)
+        dur_d = torch.from_numpy(dur).to(self.device)
+        len_d = torch.tensor([len(s) for s in sentences], dtype=torch.int32, device=self.device)
+        nf_d = torch.tensor([int(n) for n in n_frames], dtype=torch.int32, device=self.device)
+        return tok_d, dur_d, len_d, nf_d, keep_d
+
     def __call__(self, sentences: Sequence[Sequence[int]], durations_frames: Sequence[np.ndarray], n_frames: Sequence[int],
                  keep_masks: Optional[Sequence[np.ndarray]] = None, dropout_seeds: Optional[Sequence[int]] = None, to_host: bool = True,
                  dropout_rng=None, group_row0: Optional[Sequence[int]] = None, encoded: Optional[torch.Tensor] = None):
@@ -277,21 +298,8 @@ class AcousticModel(NativeHandle):
                 raise ValueError(f"encoded must be float32 [{B}, >= {Lmax}, {2 * self.encoder_dim}] (got {tuple(encoded.shape)} {encoded.dtype})")
             encoded = encoded.contiguous()
             Lmax = int(encoded.shape[1])
-        tok, dur = padded_rows(sentences, durations_frames, Lmax)
-        keep_d = None
-        if keep_masks is not None:
-            keep = np.zeros((B, Fmax, 2, self.prenet_dim), dtype=np.uint8)
-            for i, m in enumerate(keep_masks):
-                keep[i, : n_frames[i]] = np.asarray(m, dtype=bool)[: n_frames[i]]
-            keep_d = torch.from_numpy(keep).to(self.device)
-        elif dropout_rng is not None:
-            keep_d = self.device_keep_masks_haiku(dropout_rng, B, Fmax)
-        elif dropout_seeds is not None:
-            keep_d = self.device_keep_masks(dropout_seeds, Fmax)
-        tok_d = torch.from_numpy(tok).to(self.device) if encoded is None else None  # (the C side ignores the tokens when the encoder's output is given)
-        dur_d = torch.from_numpy(dur).to(self.device)
-        len_d = torch.tensor(lens, dtype=torch.int32, device=self.device)
-        nf_d = torch.tensor([int(n) for n in n_frames], dtype=torch.int32, device=self.device)
+        tok_d, dur_d, len_d, nf_d, keep_d = self._device_inputs(sentences, durations_frames, n_frames, Lmax, Fmax, keep_masks, dropout_seeds, dropout_rng,
+                                                                with_tokens=encoded is None)
         out = torch.empty((B, Fmax, self.mel_dim), dtype=torch.float32, device=self.device)
         n = C.c_size_t(0)
         self._call("workspace_bytes", B, Lmax, Fmax, C.byref(n))
@@ -314,3 +322,75 @@ class AcousticModel(NativeHandle):
         if self.resident_used and self.resident_status():
             raise RuntimeError("the resident decoder kernel gave up: a wait between its workgroups exceeded 100 ms (the mel is incomplete)")
         return [host[i, : n_frames[i]].copy() for i in range(B)]
+
+    def open_stream(self, sentences: Sequence[Sequence[int]], durations_frames: Sequence[np.ndarray], n_frames: Sequence[int], max_window: int,
+                    keep_masks: Optional[Sequence[np.ndarray]] = None, dropout_seeds: Optional[Sequence[int]] = None, dropout_rng=None) -> "MelStream":
+        """:meth:`__call__` cut along time (include/vtts_nat.h: the streaming session): the same arguments and rules; the token encoder and the
+        conditioning of every frame are enqueued now, the decoder's frames and the postnet as the returned :class:`MelStream` is asked for them.
+        ``max_window``: the most frames one :meth:`MelStream.finish` will cover.  One open stream per model: a second ``open_stream`` or any call of
+        the model ends it."""
+        if self._blob is None:
+            raise RuntimeError("no parameters loaded")
+        B = len(sentences)
+        lens = [len(s) for s in sentences]
+        if B == 0 or min(lens) < 1 or min(n_frames) < 1:
+            raise ValueError("empty batch, token sequence or frame count")
+        if int(max_window) < 1:
+            raise ValueError("max_window must be positive")
+        if dropout_seeds is not None and keep_masks is None and dropout_rng is None and len(dropout_seeds) != B:
+            raise ValueError("one dropout seed per sentence")
+        Lmax, Fmax = max(lens), int(max(n_frames))
+        inputs = self._device_inputs(sentences, durations_frames, n_frames, Lmax, Fmax, keep_masks, dropout_seeds, dropout_rng)
+        mel = torch.empty((B, Fmax, self.mel_dim), dtype=torch.float32, device=self.device)
+        n = C.c_size_t(0)
+        self._call("stream_workspace_bytes", B, Lmax, Fmax, int(max_window), C.byref(n))
+        ws = self._workspace(int(n.value))
+        tok_d, dur_d, len_d, nf_d, keep_d = inputs
+        self._session = getattr(self, "_session", 0) + 1
+        self._on_stream("stream_begin", ptr(tok_d), ptr(len_d), ptr(dur_d), ptr(nf_d), B, Lmax, Fmax, ptr(keep_d), ptr(mel), ptr(ws), ws.numel(), int(max_window))
+        return MelStream(self, self._session, mel, (inputs, ws), Fmax)
+
+
+class MelStream:
+    """An open streaming session of an :class:`AcousticModel` (:meth:`AcousticModel.open_stream`).  ``mel`` is the ``[B, Fmax, mel_dim]`` device tensor
+    the windows land in; ``frames_decoded`` the host's copy of the decoder's cursor.  Work is enqueued on torch's current stream of the model's
+    device.  A context manager; :meth:`close` is idempotent and also runs when the object is collected."""
+
+    def __init__(self, model: AcousticModel, ticket: int, mel: torch.Tensor, held, n_frames_max: int):
+        self._model, self._ticket, self.mel, self._held, self.n_frames_max = model, ticket, mel, held, n_frames_max
+        self.frames_decoded = 0
+
+    def _mine(self) -> bool:  # a later open_stream() took the handle's one session: this object must not drive (or end) that one
+        return self._model is not None and self._model._session == self._ticket
+
+    def _on_stream(self, name: str, *args) -> None:
+        if not self._mine():
+            raise _lib.VttsError(-2, f"{name}: this stream is closed")
+        self._model._on_stream(name, *args)
+
+    def decode(self, upto: int) -> None:
+        """Enqueue the decoder's frames up to ``upto`` (exclusive; clipped to the longest row)."""
+        self._on_stream("stream_decode", int(upto))
+        self.frames_decoded = max(self.frames_decoded, min(int(upto), self.n_frames_max))
+
+    def finish(self, f0: int, f1: int) -> None:
+        """Enqueue postnet + residual of the frames ``[f0, f1)`` of every row into :attr:`mel`; the decoder must have reached ``f1 + 10``."""
+        self._on_stream("stream_finish", int(f0), int(f1))
+
+    def close(self) -> None:
+        if self._model is not None:
+            if self._mine() and self._model._h.value:
+                self._model._call("stream_end")
+            self._model = self._held = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

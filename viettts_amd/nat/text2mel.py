@@ -158,6 +158,11 @@ def set_duration_model(model) -> None:
 
 def predict_duration(tokens: Sequence[int]) -> np.ndarray:
     """Reference signature and result (text2mel.py:22-34): float32 ``[1, L]`` seconds per token, computed on the GPU."""
+    return duration_model()([list(tokens)])[0][None, :]
+
+
+def duration_model():
+    """The installed or cached duration model, loaded from ``FLAGS.ckpt_dir`` on first use."""
     global _DURATION_MODEL
     if _DURATION_MODEL is None:
         from .duration import DurationModel
@@ -166,7 +171,7 @@ def predict_duration(tokens: Sequence[int]) -> np.ndarray:
         m = DurationModel()
         m.load_params(params, state)
         _DURATION_MODEL = m
-    return _DURATION_MODEL([list(tokens)])[0][None, :]
+    return _DURATION_MODEL
 
 
 _ACOUSTIC_MODEL = None
@@ -208,14 +213,8 @@ def load_acoustic_checkpoint(path=None, with_rng: bool = False):
     return dic["params"], dic["aux"]
 
 
-def predict_mel(tokens: Sequence[int], durations: np.ndarray, dropout_seed: Optional[int] = 0, dropout_rng=None) -> np.ndarray:
-    """Reference signature and result (text2mel.py:61-82): ``durations`` float32 ``[1, L]`` in SECONDS -> mel
-    ``[1, n_frames, 80]`` with ``n_frames = int(sum(durations * sample_rate / hop))``.
-
-    Prenet dropout (always on in the reference, model.py:95-100): with ``dropout_rng`` (a jax PRNGKey, uint32[2]) — or, by
-    default, the ``rng`` of the checkpoint this function loaded, as text2mel.py:65-73 passes it to ``forward.apply`` — the
-    masks are the reference's own stream (jax.random's classic threefry layout under Haiku's key chain, drawn on the GPU);
-    without a key, ``dropout_seed`` seeds this library's own stream; ``dropout_seed=None`` and no key: no dropout."""
+def acoustic_model():
+    """The installed or cached acoustic model, loaded from ``FLAGS.ckpt_dir`` on first use (``checkpoint_rng``: the checkpoint's PRNG key)."""
     global _ACOUSTIC_MODEL
     if _ACOUSTIC_MODEL is None:
         from .acoustic import AcousticModel
@@ -227,16 +226,28 @@ def predict_mel(tokens: Sequence[int], durations: np.ndarray, dropout_seed: Opti
         if _LOW_LATENCY:
             m.set_option("resident", 1)
         _ACOUSTIC_MODEL = m
+    return _ACOUSTIC_MODEL
+
+
+def predict_mel(tokens: Sequence[int], durations: np.ndarray, dropout_seed: Optional[int] = 0, dropout_rng=None) -> np.ndarray:
+    """Reference signature and result (text2mel.py:61-82): ``durations`` float32 ``[1, L]`` in SECONDS -> mel
+    ``[1, n_frames, 80]`` with ``n_frames = int(sum(durations * sample_rate / hop))``.
+
+    Prenet dropout (always on in the reference, model.py:95-100): with ``dropout_rng`` (a jax PRNGKey, uint32[2]) — or, by
+    default, the ``rng`` of the checkpoint this function loaded, as text2mel.py:65-73 passes it to ``forward.apply`` — the
+    masks are the reference's own stream (jax.random's classic threefry layout under Haiku's key chain, drawn on the GPU);
+    without a key, ``dropout_seed`` seeds this library's own stream; ``dropout_seed=None`` and no key: no dropout."""
+    am = acoustic_model()
     if dropout_rng is None:
-        dropout_rng = getattr(_ACOUSTIC_MODEL, "checkpoint_rng", None)
+        dropout_rng = getattr(am, "checkpoint_rng", None)
     frames = durations_to_frames(durations)  # :78
     n_frames = n_frames_from_durations(durations)  # :79
     if n_frames < 1:
         return np.zeros((1, 0, FLAGS.mel_dim), dtype=np.float32)
     if dropout_rng is not None:  # the reference's own stream
-        return _ACOUSTIC_MODEL([list(tokens)], [frames[0]], [n_frames], dropout_rng=dropout_rng)[0][None]
+        return am([list(tokens)], [frames[0]], [n_frames], dropout_rng=dropout_rng)[0][None]
     seeds = None if dropout_seed is None else [dropout_seed]  # masks drawn on the GPU (include/vtts_nat.h)
-    return _ACOUSTIC_MODEL([list(tokens)], [frames[0]], [n_frames], dropout_seeds=seeds)[0][None]
+    return am([list(tokens)], [frames[0]], [n_frames], dropout_seeds=seeds)[0][None]
 
 
 _MEL_PROVIDER: Optional[Callable] = None

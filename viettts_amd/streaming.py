@@ -1,0 +1,174 @@
+"""One sentence, streamed: audio chunks leave while the acoustic decoder is still running (new capability — the reference computes the whole
+mel, then the whole waveform, vietTTS/synthesizer.py:33-39).
+
+The cut is along time.  The decoder runs up to a frame cursor (``AcousticModel.open_stream``: include/vtts_nat.h, the streaming session), the mel
+is made final for a frame window (postnet + residual: 10 frames of the decoder's mel on either side), and a chunk of that window is vocoded with
+the generator's 13-frame halo (``viettts_amd.dist.plan_chunks``) and copied to pinned host memory while the decoder carries on:
+
+    chunk k keeps frames [t0, t1)  <-  generator on mel[lo, hi), hi = min(T, t1 + 13)  <-  postnet up to hi  <-  decoder up to min(hi + 10, n_frames)
+
+Every kernel is the un-streamed path's and none of its sums depends on where a window or a chunk lies, so the mel equals
+``AcousticModel.__call__``'s bit for bit and the samples equal ``longform.synthesize_chunked`` on that mel with the same chunk plan.
+
+    for pcm in stream_text("xin chào", lexicon, out_dtype="pcm16"):   # int16 arrays, 256 * T samples in all
+        sink.write(pcm.tobytes())
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Iterator, List, Optional, Sequence
+
+import numpy as np
+
+from .dist import HALO_FRAMES, Chunk, plan_chunks
+
+POSTNET_HALO = 10  # include/vtts_nat.h: VTTS_NAT_POSTNET_HALO = 5 layers x (5 - 1) / 2 taps per side
+
+
+@dataclass(frozen=True)
+class StreamStep:
+    chunk: Chunk  # the frames this step's samples cover (t0, t1) and the frames the generator is fed (lo, hi)
+    mel_upto: int  # the mel must be final up to here (= chunk.hi)
+    decode_upto: int  # ... for which the decoder must have produced the frames up to here
+
+
+def stream_plan(T: int, n_frames: int, chunk_frames: int, first_chunk_frames: Optional[int] = None, voc_halo: int = HALO_FRAMES,
+                post_halo: int = POSTNET_HALO) -> List[StreamStep]:
+    """The steps of one streamed sentence.  ``n_frames``: the frames the acoustic model would generate; ``T <= n_frames``: the frames kept (after
+    text2mel's trailing-silence trim, vietTTS/nat/text2mel.py:99-102).  Chunks of ``chunk_frames`` kept frames (``plan_chunks``: a generator halo per
+    side, none at the utterance's true edges), the first of ``first_chunk_frames`` if given — a short first chunk is what an interactive caller
+    hears first.  The decoder is never asked for frames past ``min(T + post_halo, n_frames)``: what the trim would drop is not decoded."""
+    if not 1 <= T <= n_frames:
+        raise ValueError(f"need 1 <= T <= n_frames (got {T}, {n_frames})")
+    if post_halo < 0 or (first_chunk_frames is not None and first_chunk_frames < 1):
+        raise ValueError("post_halo must be >= 0 and first_chunk_frames >= 1")
+    if first_chunk_frames is None:
+        chunks = plan_chunks(T, chunk_frames, voc_halo)
+    else:  # the first chunk of a plan in first_chunk_frames, then a plan of the rest moved behind it: halos are cut at the UTTERANCE's edges only
+        head = plan_chunks(T, int(first_chunk_frames), voc_halo)[0]
+        a = head.t1
+        rest = plan_chunks(T - a, chunk_frames, voc_halo) if a < T else []
+        chunks = [head] + [Chunk(c.index + 1, c.t0 + a, c.t1 + a, max(0, c.t0 + a - voc_halo), min(T, c.t1 + a + voc_halo)) for c in rest]
+    return [StreamStep(c, c.hi, min(c.hi + post_halo, n_frames)) for c in chunks]
+
+
+def _copy_out(w, cur, s_copy):
+    """Device samples -> pinned host memory on the copy stream, behind an event on the compute stream.  Returns (host tensor, landed event)."""
+    import torch
+
+    done = torch.cuda.Event()
+    done.record(cur)
+    host = torch.empty(w.shape, dtype=w.dtype, pin_memory=True)
+    s_copy.wait_event(done)
+    with torch.cuda.stream(s_copy):
+        host.copy_(w, non_blocking=True)
+        landed = torch.cuda.Event()
+        landed.record(s_copy)
+    w.record_stream(s_copy)
+    return host, landed
+
+
+def _vocode(generator, mel, chunk: Chunk, out_dtype: str):
+    """The chunk's kept samples on the device: the generator on ``mel[lo:hi]`` (``[T, num_mels]`` rows), its halo's samples dropped."""
+    hop = generator.hop
+    wav = generator(mel[chunk.lo : chunk.hi].unsqueeze(0).contiguous())
+    w = wav[0, hop * chunk.keep_from : hop * (chunk.keep_from + chunk.t1 - chunk.t0)]
+    if out_dtype == "pcm16":
+        from .audio import to_pcm16
+
+        w = to_pcm16(w.contiguous())
+    return w
+
+
+def _check_dtype(out_dtype: str) -> None:
+    if out_dtype not in ("f32", "pcm16"):
+        raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
+
+
+def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32") -> Iterator[np.ndarray]:
+    """Vocoder-only streaming of a finished mel (``[T, num_mels]`` float32, host array or tensor): the chunks of :func:`stream_plan`, one generator
+    call each, every chunk's read-back under the next chunk's compute.  Yields host arrays (float32, or int16 equal to ``wavio.float_to_pcm16``
+    of the float chunks); their concatenation has ``hop * T`` samples."""
+    import torch
+
+    from .pipeline import _copy_stream
+
+    _check_dtype(out_dtype)
+    if not isinstance(mel, torch.Tensor):
+        mel = torch.from_numpy(np.ascontiguousarray(mel, dtype=np.float32))
+    if mel.dim() != 2:
+        raise ValueError("mel must be [T, num_mels]")
+    mel = mel.to(generator.device)
+    T = int(mel.shape[0])
+    if T < 1:
+        return
+    cur, s_copy = torch.cuda.current_stream(generator.device), _copy_stream(generator.device)
+    pending = None
+    for step in stream_plan(T, T, chunk_frames, first_chunk_frames):
+        nxt = _copy_out(_vocode(generator, mel, step.chunk, out_dtype), cur, s_copy)
+        if pending is not None:
+            pending[1].synchronize()
+            yield pending[0].numpy()
+        pending = nxt
+    pending[1].synchronize()
+    yield pending[0].numpy()
+
+
+def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, generator, silence_duration: float = -1.0, dropout_seed: Optional[int] = 0,
+                      dropout_rng=None, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32",
+                      info: Optional[dict] = None) -> Iterator[np.ndarray]:
+    """A generator over the waveform of ONE sentence (token ids), chunk by chunk, in order: host arrays, float32 or (``out_dtype="pcm16"``) int16 equal
+    to ``wavio.float_to_pcm16`` of the float chunks; ``256 * T`` samples in all, T = the frames text2mel keeps.  The frame rules are text2mel's
+    (``frame_plan``: vietTTS/nat/text2mel.py:78-79, :90-102); dropout as ``predict_mel`` (``dropout_rng``: the reference's stream; else
+    ``dropout_seed``; both None: none).  ``T < 1`` yields nothing.
+
+    Per step of :func:`stream_plan`: decoder up to ``decode_upto``, postnet up to ``mel_upto``, generator on ``mel[lo:hi]``, the kept samples (packed
+    to PCM16 on the device if asked) to pinned memory on a copy stream; the NEXT step's decoder frames are enqueued before the host waits for this
+    step's copy.  ``info`` (a dict) receives ``frames`` (T), ``n_frames`` and ``samples`` before the first chunk is yielded, and
+    ``frames_decoded_at_first_chunk``.  Work is enqueued on torch's current stream."""
+    import torch
+
+    from .nat import text2mel as t2m
+    from .pipeline import _copy_stream
+
+    _check_dtype(out_dtype)
+    toks = [int(t) for t in tokens]
+    secs = duration_model([toks])
+    frames, nfr, trail = t2m.frame_plan([toks], secs, silence_duration)
+    n, T = nfr[0], nfr[0] - trail[0]
+    if info is not None:
+        info.update(frames=max(T, 0), n_frames=n, samples=generator.hop * max(T, 0))
+    if n < 1 or T < 1:
+        return
+    plan = stream_plan(T, n, chunk_frames, first_chunk_frames)
+    windows = [b.mel_upto - a for a, b in zip([0] + [s.mel_upto for s in plan[:-1]], plan)]
+    kw = {"dropout_rng": dropout_rng} if dropout_rng is not None else {"dropout_seeds": None if dropout_seed is None else [dropout_seed]}
+    dev = generator.device
+    cur, s_copy = torch.cuda.current_stream(dev), _copy_stream(dev)
+    with acoustic_model.open_stream([toks], [frames[0]], [n], max(windows), **kw) as st:
+        st.decode(plan[0].decode_upto)
+        final = 0
+        for k, step in enumerate(plan):
+            if step.mel_upto > final:
+                st.finish(final, step.mel_upto)
+                final = step.mel_upto
+            host, landed = _copy_out(_vocode(generator, st.mel[0], step.chunk, out_dtype), cur, s_copy)
+            if info is not None and k == 0:
+                info["frames_decoded_at_first_chunk"] = st.frames_decoded
+            if k + 1 < len(plan):
+                st.decode(plan[k + 1].decode_upto)  # under this chunk's vocoder and copy
+            landed.synchronize()
+            yield host.numpy()
+
+
+def stream_text(text: str, lexicon_fn=None, silence_duration: float = -1.0, **kw) -> Iterator[np.ndarray]:
+    """:func:`synthesize_stream` from text, through the models ``viettts_amd.nat.text2mel`` and ``viettts_amd.hifigan.mel2wave`` cache (the
+    checkpoints under the CWD, as the reference reads them); the dropout stream is ``predict_mel``'s."""
+    from .hifigan.mel2wave import _generator
+    from .nat import text2mel as t2m
+
+    tokens = t2m.text2tokens(text, t2m.FLAGS.data_dir / "lexicon.txt" if lexicon_fn is None else lexicon_fn)
+    am = t2m.acoustic_model()
+    if "dropout_rng" not in kw and getattr(am, "checkpoint_rng", None) is not None:
+        kw["dropout_rng"] = am.checkpoint_rng
+    return synthesize_stream(tokens, t2m.duration_model(), am, _generator(), silence_duration, **kw)

@@ -7,7 +7,10 @@ reference runs the whole pipeline at import time).  One 
 mel->waveform path can be driven on its own (the text path runs the NAT duration and acoustic models of
 ``viettts_amd/nat`` like the reference's), and ``--low-latency`` runs the acoustic decoder's frame loop as one resident kernel
 (``viettts_amd.nat.text2mel.set_low_latency``), and ``--resample`` makes ``--sample-rate R`` a conversion to R on the GPU
-(``viettts_amd.audio.Resampler``) where the reference, and this CLI without the flag, only label the 16 kHz samples with R.
+(``viettts_amd.audio.Resampler``) where the reference, and this CLI without the flag, only label the 16 kHz samples with R, and ``--stream``
+writes the output chunk by chunk while the acoustic decoder is still running (``viettts_amd.streaming``): the WAV header first — the sample count
+is known before the first decoder frame — then PCM16 per chunk of ``--chunk-frames`` mel frames, flushed; ``--output -`` writes the raw PCM16 to
+stdout (the two printed lines go to stderr then).
 
     python -m viettts_amd.synthesizer --text "..." --output clip.wav --lexicon-file assets/infore/lexicon.txt
 """
@@ -50,11 +53,62 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--mel-file", default=None, type=Path, help="(extension) synthesise from a saved mel instead of text")
     p.add_argument("--low-latency", action="store_true", help="(extension) run the acoustic decoder's frame loop as one resident kernel")
     p.add_argument("--resample", action="store_true", help="(extension) convert the samples to --sample-rate on the GPU instead of relabelling them")
+    p.add_argument("--stream", action="store_true", help="(extension) write the audio chunk by chunk while the decoder is still running")
+    p.add_argument("--chunk-frames", default=32, type=int, help="(extension) mel frames per streamed chunk")
     return p
 
 
+def _stream(args) -> int:
+    """``--stream``: header, then PCM16 chunk by chunk.  With ``--mel-file`` only the vocoder streams."""
+    import sys
+
+    from .streaming import stream_mel, stream_text
+    from .wavio import wav_header_pcm16
+
+    raw = str(args.output) == "-"
+    say = (lambda *a: print(*a, file=sys.stderr)) if raw else print
+    info = {}
+    if args.mel_file is not None:
+        from .hifigan.mel2wave import _generator
+
+        mel = np.load(args.mel_file).astype(np.float32)
+        mel = mel[0] if mel.ndim == 3 else mel
+        gen = _generator()
+        info["samples"] = gen.hop * mel.shape[0]
+        chunks = stream_mel(gen, mel, args.chunk_frames, out_dtype="pcm16")
+    else:
+        text = nat_normalize_text(args.text)
+        say("Normalized text input:", text)
+        chunks = stream_text(text, args.lexicon_file, args.silence_duration, chunk_frames=args.chunk_frames, out_dtype="pcm16", info=info)
+    first = next(chunks, None)  # (the text path knows its sample count once the duration model has run: before the first decoder frame)
+    say("writing output to file", args.output)
+    f = sys.stdout.buffer if raw else open(str(args.output), "wb")
+    try:
+        if not raw:
+            f.write(wav_header_pcm16(info["samples"], args.sample_rate))
+        while first is not None:
+            f.write(first.astype("<i2", copy=False).tobytes())
+            f.flush()
+            first = next(chunks, None)
+    finally:
+        if not raw:
+            f.close()
+    return 0
+
+
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.stream:  # argument errors before anything touches a device
+        if args.resample:
+            parser.error("--stream with --resample: a streamed resampler would need a filter state across chunks")
+        if args.low_latency:
+            parser.error("--stream with --low-latency: a streamed decoder runs the per-frame launches, not the resident kernel")
+        if args.chunk_frames < 1:
+            parser.error("--chunk-frames must be positive")
+        if args.mel_file is None and args.text is None:
+            raise SystemExit("--text (or --mel-file) is required")
+        return _stream(args)
     from .hifigan.mel2wave import mel2wave
     from .wavio import write_wav, write_wav_pcm16
 

@@ -17,17 +17,21 @@ def float_to_pcm16(wave: np.ndarray) -> np.ndarray:
     return y.astype("<i2")
 
 
+def wav_header_pcm16(n_samples: int, samplerate: int) -> bytes:
+    """The 44 bytes in front of ``n_samples`` mono PCM16 samples (a streaming writer knows the count before the first sample exists)."""
+    n = 2 * int(n_samples)
+    hdr = b"RIFF" + struct.pack("<I", 36 + n) + b"WAVE"
+    hdr += b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, int(samplerate), int(samplerate) * 2, 2, 16)
+    return hdr + b"data" + struct.pack("<I", n)
+
+
 def write_wav(path, wave: np.ndarray, samplerate: int) -> None:
     wave = np.asarray(wave)
     if wave.ndim != 1:
         raise ValueError("write_wav expects a mono 1-D waveform")
     pcm = float_to_pcm16(wave).tobytes()
-    n = len(pcm)
-    hdr = b"RIFF" + struct.pack("<I", 36 + n) + b"WAVE"
-    hdr += b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, int(samplerate), int(samplerate) * 2, 2, 16)
-    hdr += b"data" + struct.pack("<I", n)
     with open(str(path), "wb") as f:
-        f.write(hdr + pcm)
+        f.write(wav_header_pcm16(len(pcm) // 2, samplerate) + pcm)
 
 
 def write_wav_pcm16(path, pcm: np.ndarray, samplerate: int) -> None:
@@ -36,12 +40,8 @@ def write_wav_pcm16(path, pcm: np.ndarray, samplerate: int) -> None:
     if pcm.ndim != 1 or pcm.dtype != np.int16:
         raise ValueError("write_wav_pcm16 expects a mono 1-D int16 array")
     data = pcm.astype("<i2", copy=False).tobytes()
-    n = len(data)
-    hdr = b"RIFF" + struct.pack("<I", 36 + n) + b"WAVE"
-    hdr += b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, int(samplerate), int(samplerate) * 2, 2, 16)
-    hdr += b"data" + struct.pack("<I", n)
     with open(str(path), "wb") as f:
-        f.write(hdr + data)
+        f.write(wav_header_pcm16(len(data) // 2, samplerate) + data)
 
 
 def read_wav(path):
