@@ -69,13 +69,14 @@ int vtts_nat_duration_forward(vtts_nat_duration* h, const int32_t* tokens_dev, c
  * Acoustic model: replaces predict_mel()'s network apply, vietTTS/nat/text2mel.py:61-82 ==
  * AcousticModel(is_training=False).inference(tokens, durations, n_frames), vietTTS/nat/model.py:128-151.
  * ------------------------------------------------------------------------------------------------------------------ */
-typedef struct vtts_nat_acoustic_cfg { /* vietTTS/nat/config.py:11-17, :42; model.py:88-89 */
-    int32_t vocab_size;   /* 256 */
-    int32_t encoder_dim;  /* acoustic_encoder_dim 256 */
-    int32_t decoder_dim;  /* acoustic_decoder_dim 512 */
-    int32_t prenet_dim;   /* 256 (hk.Linear(256) x 2) */
-    int32_t mel_dim;      /* 80  */
-    int32_t postnet_dim;  /* 512 */
+typedef struct vtts_nat_acoustic_cfg { /* vietTTS/nat/config.py:11-17, :42; model.py:88-89.  The reference's value, then what create() accepts
+                                        * (anything else is VTTS_ERR_INVALID with a message naming the rule; no forward*() refuses a width create() accepted) */
+    int32_t vocab_size;   /* 256; >= 1 */
+    int32_t encoder_dim;  /* acoustic_encoder_dim 256; 64, 128, 192 or 256 */
+    int32_t decoder_dim;  /* acoustic_decoder_dim 512; 256, 512, 768 or 1024 (the gate mix takes 4 * decoder_dim columns in chunks of 1024) */
+    int32_t prenet_dim;   /* 256 (hk.Linear(256) x 2); a multiple of 32 with 2 * encoder_dim + prenet_dim <= 1024 */
+    int32_t mel_dim;      /* 80; a multiple of 4 in 4 .. 128 */
+    int32_t postnet_dim;  /* 512; a multiple of 4 in 4 .. 1024 */
 } vtts_nat_acoustic_cfg;
 
 typedef struct vtts_nat_acoustic vtts_nat_acoustic; /* opaque */

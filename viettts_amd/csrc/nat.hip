@@ -160,7 +160,10 @@ __global__ __launch_bounds__(256) void nat_conv_bn_act_k(const float* __restrict
 // bytes apart (the prenet's [B][F][2][PN] masks, the pointer already at the layer's half); NAT_TF_ACC = y += the result, the previous value read
 // through y itself (res is not used: y is the only pointer to that array).
 enum : int { NAT_TF_SHIFT = 1, NAT_TF_KEEP = 2, NAT_TF_ACC = 4 };
-template <int K, int MR, int TF = 0>
+// FOLD (compile-time, the postnet's layers with more than 512 input channels): the running sums are set aside every 8 steps (8 x 32 x K terms) and the
+// parts added at the end, in step order.  One fp32 chain over all of 5 x 1024 terms carries four to five times the rounding error of a blocked sum
+// (tools/restate_nat_conv_order.py); chains of 1280 terms stay where the narrower layers' are.  Up to 512 channels nothing changes, bit for bit.
+template <int K, int MR, int TF = 0, int FOLD = 0>
 __global__ __launch_bounds__(256, 2) void nat_conv_mfma_k(const float* __restrict__ x, const int* __restrict__ lengths, const float4* __restrict__ wpk,
                                                        const float* __restrict__ bias, const float* __restrict__ inv, const float* __restrict__ mean,
                                                        const float* __restrict__ offset, const float* __restrict__ res, float* __restrict__ y, int Lmax,
@@ -243,6 +246,15 @@ __global__ __launch_bounds__(256, 2) void nat_conv_mfma_k(const float* __restric
         }
     };
     float4 avA[MR][4], avB[MR][4];
+    f32x16 tot[FOLD ? MR : 1][NR];  // FOLD: the sums of the steps set aside so far
+    if constexpr (FOLD != 0) {
+#pragma unroll
+        for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+            for (int nr = 0; nr < NR; ++nr)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[mr][nr][r] = 0.0f;
+    }
     stage_load(0);
     if (mine) load_a(0, 0, avA);
     stage_store(0);
@@ -278,8 +290,29 @@ __global__ __launch_bounds__(256, 2) void nat_conv_mfma_k(const float* __restric
                 __syncthreads();
             }
         }
+        if constexpr (FOLD != 0) {
+            if (((cs0 + 2) & 7) == 0 && cs0 + 2 < NCS) {  // 8 steps done and more to come (uniform)
+#pragma unroll
+                for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+                    for (int nr = 0; nr < NR; ++nr)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            tot[mr][nr][r] += acc[mr][nr][r];
+                            acc[mr][nr][r] = 0.0f;
+                        }
+            }
+        }
     }
     if (!mine) return;
+    if constexpr (FOLD != 0) {
+#pragma unroll
+        for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+            for (int nr = 0; nr < NR; ++nr)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[mr][nr][r] = tot[mr][nr][r] + acc[mr][nr][r];
+    }
     const bool bn = inv != nullptr;
 #pragma unroll
     for (int mr = 0; mr < MR; ++mr)
@@ -1670,9 +1703,13 @@ VTTS_API int vtts_nat_acoustic_create(const vtts_nat_acoustic_cfg* cfg, int devi
     if (!cfg || !out) return failf(VTTS_ERR_INVALID, "null argument");
     const int D = cfg->encoder_dim, V = cfg->vocab_size, H = cfg->decoder_dim, PN = cfg->prenet_dim, MEL = cfg->mel_dim, PD = cfg->postnet_dim;
     if (int rc = check_encoder_dims("acoustic model", D, V)) return rc;
-    if (H < 32 || H > 1024 || H % 32 != 0 || PN < 32 || PN % 32 != 0 || MEL < 4 || MEL > 128 || MEL % 4 != 0 || PD < 4 || PD > 1024 || PD % 4 != 0 || 2 * D + PN > 1024 || (2 * D) % 32 != 0)
-        return failf(VTTS_ERR_INVALID, "acoustic model: decoder_dim and prenet_dim must be multiples of 32 (matrix-core k-steps), decoder_dim <= 1024, "
-                                       "2 * encoder_dim + prenet_dim <= 1024, mel_dim <= 128 and postnet_dim <= 1024 multiples of 4");
+    // decoder_dim in multiples of 256: nat_gates_mix_k takes the 4 * decoder_dim gate columns in chunks of 1024 (256 threads x 4 columns)
+    if (H < 256 || H > 1024 || H % 256 != 0)
+        return failf(VTTS_ERR_INVALID, "acoustic model: decoder_dim must be 256, 512, 768 or 1024 (the gate mix takes 4 * decoder_dim columns in chunks of 1024; got %d)", H);
+    if (PN < 32 || PN % 32 != 0 || 2 * D + PN > 1024)
+        return failf(VTTS_ERR_INVALID, "acoustic model: prenet_dim must be a multiple of 32 (matrix-core k-steps) with 2 * encoder_dim + prenet_dim <= 1024 (got %d, encoder_dim %d)", PN, D);
+    if (MEL < 4 || MEL > 128 || MEL % 4 != 0) return failf(VTTS_ERR_INVALID, "acoustic model: mel_dim must be a multiple of 4 in 4 .. 128 (16-byte rows; got %d)", MEL);
+    if (PD < 4 || PD > 1024 || PD % 4 != 0) return failf(VTTS_ERR_INVALID, "acoustic model: postnet_dim must be a multiple of 4 in 4 .. 1024 (16-byte rows; got %d)", PD);
     auto* h = new (std::nothrow) vtts_nat_acoustic();
     if (!h) return failf(VTTS_ERR_NOMEM, "host allocation failed");
     h->what = "acoustic model";
@@ -2012,6 +2049,13 @@ void nat_conv(const NatConv& o, bool x3, hipStream_t s) {
                 return;
             }
         }
+        if constexpr (K == 5 && TF == 0) {
+            if (o.cin > 512) {  // chains of more than 5 x 512 terms: folded every 8 steps (FOLD at the kernel)
+                hipLaunchKernelGGL((nat_conv_mfma_k<K, MR, TF, 1>), grid, dim3(256), 0, s, o.x, o.rows, reinterpret_cast<const float4*>(o.w), o.bias, o.inv, o.mean,
+                                   o.offset, o.res, o.y, o.pitch, o.cin, o.cout, o.act, 0, o.keep);
+                return;
+            }
+        }
         hipLaunchKernelGGL((nat_conv_mfma_k<K, MR, TF>), grid, dim3(256), 0, s, o.x, o.rows, reinterpret_cast<const float4*>(o.w), o.bias, o.inv, o.mean, o.offset,
                            o.res, o.y, o.pitch, o.cin, o.cout, o.act, 0, o.keep);
     };
@@ -2024,7 +2068,7 @@ void nat_conv(const NatConv& o, bool x3, hipStream_t s) {
 // caller's stream, the rest beside it on the side stream, ev_gates behind them.
 int nat_cond_gates(const NatCall& c, int mfirst) {
     vtts_nat_acoustic* h = c.h;
-    if (c.G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: the gate mix wants 4 * decoder_dim in multiples of 1024", c.H);
+    if (c.G4 % 1024 != 0) return failf(VTTS_ERR_INVALID, "decoder_dim %d: create() admits multiples of 256 only (the gate mix takes 4 * decoder_dim in chunks of 1024)", c.H);
     for (int l = 0; l < 2; ++l) {
         const std::string mod = l ? "lstm_1/linear" : "lstm/linear";
         nat_conv<1>(NatConv{c.B, c.Lmax, c.Lmax, c.lengths, c.ws.enc, l ? c.ws.EG2 : c.ws.EG1, h->extra(mod + (h->x3 ? "#cond#x3" : "#cond")), h->extra(mod + "#zerob"),
@@ -2198,7 +2242,11 @@ int nat_dec_frames(const NatCall& c, int fa, int fb, bool gates_wait) {
         if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, f, B, Bp, H);
         else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, f, B, Bp, H);
     };
-    const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);
+    const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);  // at most 64 KiB: create()'s limits at once (H = 1024, PN = 896, MEL = 128)
+    if (plds > 48 * 1024) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_dec_proj_prenet_k<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_dec_proj_prenet_k<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+    }
     auto group_handover = [&](int frames_done) -> int {  // a group whose last frame was frames_done - 1: its postnet starts now, on the side stream
         for (int g = 0; g < c.ngroups; ++g) {
             if (c.group_frames[g] != frames_done) continue;
