@@ -269,6 +269,48 @@ int vtts_nat_acoustic_stream_decode(vtts_nat_acoustic* h, int upto, void* stream
 int vtts_nat_acoustic_stream_finish(vtts_nat_acoustic* h, int f0, int f1, void* stream);
 int vtts_nat_acoustic_stream_end(vtts_nat_acoustic* h);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Slot pool: the streaming session with a frame cursor PER ROW, for a caller who serves many sentences that do not start together (continuous
+ * batching; the reference has nothing like it).  A frame step costs about the same for 1 row as for 32, so the rows a lone sentence leaves idle
+ * are capacity: a sentence joins the running batch at any tick, in a free slot, and leaves when it is done, while its neighbours carry on.
+ * A TICK is one frame step of every slot: the session's three launches per frame, row b at frame tick - start[b] (start[] on the device, written
+ * by admit()), idle while that is negative or >= its frame count.  The state ping-pong goes by the tick's parity.  Every output element depends
+ * on its own sentence's column only, and every sum is forward()'s chain: a row's decoder mel and, after its windows, its mel equal forward()'s of
+ * that sentence alone in every byte, whatever its slot, its start tick and its neighbours.
+ *
+ *   pool_workspace_bytes()  stream_workspace_bytes(h, slots, Lmax, Fmax, max_window) plus the per-slot words.
+ *   pool_open()     keep_dev [slots, Fmax, 2, prenet_dim] bytes or NULL (no dropout), mel_dev [slots, Fmax, mel_dim] fp32, 16-byte aligned; both and the
+ *                   workspace stay allocated until the pool ends.  Zeroes the state, mel_dev and the slots' words on `stream`; every slot is free.  Ends an
+ *                   open session.  The option "resident" is ignored ("resident_used" reads 0), "bf16x3" is honoured as set at open() (changing it
+ *                   makes every later pool call return VTTS_ERR_STATE).
+ *   pool_admit()    a sentence into a free slot: tokens_dev [Lmax] (`length` of them real) and durations_dev [Lmax] (FRAMES, fp32) must stay allocated
+ *                   until the slot is retired; nframes in 1 .. Fmax.  The caller fills the slot's rows of keep_dev first, in stream order.  Enqueues on
+ *                   `stream`, behind the ticks enqueued so far: the slot's reset (its columns of both state parities and of the cell states, its rows
+ *                   of the decoder's mel and of mel_dev zero; start, frame and token counts set), then the token encoder and the conditioning gates of
+ *                   all of the row's frames, as a one-row call on the slot's rows of the workspace.  The next tick decodes the row's frame 0.
+ *   pool_decode()   enqueues `nticks` ticks for all slots (nticks = 0 does nothing).  The host keeps every slot's start tick, frame count and finished
+ *                   frame; a row's cursor is clamp(tick - start, 0, nframes).
+ *   pool_finish()   mel_dev[slot][f0 .. f1) = postnet + residual for each of the n listed rows (HOST arrays; a slot at most once), all in ONE postnet pass
+ *                   over compact windows.  Per row stream_finish()'s rules: the first f0 is 0, every later f0 the row's previous f1, f1 > f0 (an f1 past
+ *                   the row's frames counts as its frame count), f1 - f0 <= max_window, else VTTS_ERR_INVALID; the row's cursor must have reached
+ *                   min(f1 + VTTS_NAT_POSTNET_HALO, nframes), else VTTS_ERR_STATE.  Rows not listed are untouched.  No host synchronisation.
+ *   pool_retire()   frees a busy slot, finished or not: behind the ticks enqueued so far its row decodes no further frame.  Its rows of mel_dev stay
+ *                   as they are until the slot is admitted again.
+ *   pool_close()    forgets the pool (nothing is enqueued).  forward*(), encode() and stream_begin() on the handle end an open pool too: a handle has
+ *                   a pool or a session, never both.
+ * VTTS_ERR_INVALID: a slot out of range, length > Lmax, nframes outside 1 .. Fmax, a stream that is being captured.  VTTS_ERR_STATE: admit() into a busy
+ * slot, retire() or finish() on a free one, any of open's successors without an open pool, the option "bf16x3" changed since open().  A refused
+ * call enqueues nothing.  The calls of a pool are ordered by the stream(s) they are given: use one stream, or order them yourself.
+ */
+int vtts_nat_acoustic_pool_workspace_bytes(const vtts_nat_acoustic* h, int slots, int Lmax, int Fmax, int max_window, size_t* bytes);
+int vtts_nat_acoustic_pool_open(vtts_nat_acoustic* h, int slots, int Lmax, int Fmax, int max_window, const uint8_t* keep_dev, float* mel_dev, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int vtts_nat_acoustic_pool_admit(vtts_nat_acoustic* h, int slot, const int32_t* tokens_dev, int length, const float* durations_dev, int nframes, void* stream);
+int vtts_nat_acoustic_pool_decode(vtts_nat_acoustic* h, int nticks, void* stream);
+int vtts_nat_acoustic_pool_finish(vtts_nat_acoustic* h, int n, const int32_t* slots, const int32_t* f0, const int32_t* f1, void* stream);
+int vtts_nat_acoustic_pool_retire(vtts_nat_acoustic* h, int slot, void* stream);
+int vtts_nat_acoustic_pool_close(vtts_nat_acoustic* h);
+
 #ifdef __cplusplus
 }
 #endif

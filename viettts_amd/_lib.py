@@ -156,6 +156,13 @@ SIGS = {
     "vtts_nat_acoustic_stream_decode": (C.c_int, [vp, C.c_int, vp]),
     "vtts_nat_acoustic_stream_finish": (C.c_int, [vp, C.c_int, C.c_int, vp]),
     "vtts_nat_acoustic_stream_end": (C.c_int, [vp]),
+    "vtts_nat_acoustic_pool_workspace_bytes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]),
+    "vtts_nat_acoustic_pool_open": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, vp]),
+    "vtts_nat_acoustic_pool_admit": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]),
+    "vtts_nat_acoustic_pool_decode": (C.c_int, [vp, C.c_int, vp]),
+    "vtts_nat_acoustic_pool_finish": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]),
+    "vtts_nat_acoustic_pool_retire": (C.c_int, [vp, C.c_int, vp]),
+    "vtts_nat_acoustic_pool_close": (C.c_int, [vp]),
     "vtts_mel_create":(C.c_int, [C.POINTER(MelCfg), C.c_int, C.POINTER(vp)]),
     "vtts_mel_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
     "vtts_mel_filterbank": (C.c_int, [vp, fp]),

@@ -67,6 +67,21 @@ struct vtts_nat_acoustic : NatModel {
         size_t workspace_bytes = 0;
         int B = 0, Lmax = 0, Fmax = 0, max_window = 0, x3 = 0, cursor = 0, finished = 0;
     } ss;
+    // pool_open() .. pool_close(): the caller's arrays and dimensions, the tick the next pool_decode() starts at, and the host's mirror of every slot
+    struct Pool {
+        bool open = false;
+        const uint8_t* keep = nullptr;
+        float* mel = nullptr;
+        void* workspace = nullptr;
+        size_t workspace_bytes = 0;
+        int slots = 0, Lmax = 0, Fmax = 0, max_window = 0, x3 = 0, tick = 0;
+        struct Slot {
+            bool busy = false;
+            int start = 0, nframes = 0, finished = 0;  // admitted at tick `start`; the mel is final below `finished`
+        };
+        std::vector<Slot> slot;
+        int cursor(int i) const { return std::clamp(tick - slot[i].start, 0, slot[i].nframes); }  // frames of slot i the enqueued ticks decode
+    } pool;
     ~vtts_nat_acoustic() {
         for (hipEvent_t e : ev_dec) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_done) (void)hipEventDestroy(e);
@@ -691,6 +706,37 @@ __device__ __forceinline__ size_t nat_zidx(int row, int b, int Bp) { return ((si
 #endif
 constexpr int NAT_DEC_PD = VTTS_NAT_PD;   // iterations (8 k each) a wave keeps in flight (7 measured no faster: the step is L2-bandwidth-bound)
 
+// Which frame a step is for.  A call's rows all stand at the same frame `f`; a slot pool's rows (vtts_nat_acoustic_pool_*) each stand at their own,
+// f_b = tick - start[b], and a row is idle while f_b < 0 or f_b >= nframes[b].  POOL selects the second form in the three step kernels; whatever a
+// step indexes by its frame (the hoisted gates, the mel row, the keep bytes, the guards) goes through these two functions, so the sums are the
+// same chains in both forms.
+template <bool POOL>
+struct NatFrameArg {
+    int f;
+};
+template <>
+struct NatFrameArg<true> {
+    int tick;
+    const int* start;  // [slots]
+};
+template <bool POOL>
+__device__ __forceinline__ int nat_row_frame(const NatFrameArg<POOL>& a, int b) {
+    if constexpr (POOL) return a.tick - a.start[b];
+    else return a.f;
+}
+// the row decodes a frame in this step
+template <bool POOL>
+__device__ __forceinline__ bool nat_row_live(int fb, int nf) {
+    if constexpr (POOL) return fb >= 0 && fb < nf;
+    else return fb < nf;
+}
+// the hoisted gates of row b at its frame: a call's host has moved ops.gin to frame f already, a pool's rows move it themselves (idle rows read frame 0)
+template <bool POOL>
+__device__ __forceinline__ const float* nat_row_gin(const float* gin, size_t gpitch, int b, int fb, int nf, int G4) {
+    if constexpr (POOL) return gin + (size_t)b * gpitch + (size_t)(nat_row_live<true>(fb, nf) ? fb : 0) * G4;
+    else return gin + (size_t)b * gpitch;
+}
+
 // NT = 32-sentence tiles per wave (one weight fragment feeds NT MFMAs: L2 traffic for the weights / NT), KW = waves per
 // workgroup, each with a contiguous share of K; their partial sums meet in LDS in a fixed tree order.
 // One LSTM's operands; blockIdx.z picks one of two sets (the token encoder steps its forward and backward LSTMs in one launch).
@@ -706,9 +752,9 @@ struct NatLstmOps {
                          // a lane's 16 accumulators are 64 contiguous bytes.  nullptr = start from the bias.
     size_t gpitch;
 };
-template <int NT, int KW, int SL = 1>
-__global__ __launch_bounds__(64 * KW) void nat_dec_lstm_k(NatLstmOps ops0, NatLstmOps ops1, int KA, int KB, const int* __restrict__ nframes, int f, int B,
-                                                          int Bp, int H) {
+template <int NT, int KW, int SL = 1, bool POOL = false>
+__global__ __launch_bounds__(64 * KW) void nat_dec_lstm_k(NatLstmOps ops0, NatLstmOps ops1, int KA, int KB, const int* __restrict__ nframes, NatFrameArg<POOL> fa,
+                                                          int B, int Bp, int H) {
     // SL = slices (8 units each) per workgroup: a wave's state fragments feed SL weight fragments, so the state's share of the L2 -> CU stream
     // (2/3 of it at SL = 1, NT = 2: every slice's workgroup reads the whole state of its sentences) falls by SL.  Each output element's sum is
     // the same chain in the same order whatever SL is.  MEASURED (round 4, 256 sentences): SL = 2 makes the step 19.3 -> 28.9 us — the step is not
@@ -737,6 +783,15 @@ __global__ __launch_bounds__(64 * KW) void nat_dec_lstm_k(NatLstmOps ops0, NatLs
         const int blk = kw + q * KW, sl = blk / (NT * 4), nt = (blk / 4) % NT, rq = blk % 4;
         cold[q] = blk < SL * NT * 4 ? cst[(size_t)(8 * (slice0 + sl) + 2 * rq + lh) * Bp + b0 + 32 * nt + l31] : 0.0f;
     }
+    // a pool's rows look their frame up first: the hoisted gates' address depends on it (one 4-byte load per row in front of the gate loads)
+    int fb[NT], nfb[NT];
+    if constexpr (POOL) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int b = b0 + 32 * nt + l31, bc = b < B ? b : B - 1;
+            fb[nt] = nat_row_frame(fa, bc), nfb[nt] = nframes[bc];
+        }
+    }
     f32x16 acc[SL][NT][2];
     if (ops.gin != nullptr && kw == 0) {
         // the sum starts from the hoisted part (bias + the inputs known ahead of the loop, themselves an MFMA chain in k order)
@@ -745,8 +800,8 @@ __global__ __launch_bounds__(64 * KW) void nat_dec_lstm_k(NatLstmOps ops0, NatLs
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const int b = b0 + 32 * nt + l31;
-                const float4* __restrict__ gp =
-                    reinterpret_cast<const float4*>(ops.gin + (size_t)(b < B ? b : B - 1) * ops.gpitch + (size_t)(2 * (slice0 + sl) + lh) * 16);
+                const float4* __restrict__ gp = reinterpret_cast<const float4*>(
+                    nat_row_gin<POOL>(ops.gin, ops.gpitch, b < B ? b : B - 1, POOL ? fb[nt] : 0, POOL ? nfb[nt] : 0, 4 * H) + (size_t)(2 * (slice0 + sl) + lh) * 16);
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const float4 g4 = gp[rq];
@@ -795,7 +850,8 @@ __global__ __launch_bounds__(64 * KW) void nat_dec_lstm_k(NatLstmOps ops0, NatLs
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int b = b0 + 32 * nt + l31;
-        live[nt] = b < B && f < nframes[b < B ? b : B - 1];
+        if constexpr (POOL) live[nt] = b < B && nat_row_live<true>(fb[nt], nfb[nt]);
+        else live[nt] = b < B && nat_row_live<false>(nat_row_frame(fa, b), nframes[b < B ? b : B - 1]);
         any = any || live[nt];
     }
     if (__ballot(any) == 0ull) return;  // every sentence of these tiles has all its frames (same for all waves)
@@ -896,8 +952,9 @@ struct NatLstmX3Ops {
     unsigned short* hout;      // zc, plane 0: the new hidden state goes to rows out_row0 + unit
     int out_row0;
 };
-template <int NT, int KW>
-__global__ __launch_bounds__(64 * KW) void nat_dec_lstm_x3_k(NatLstmX3Ops ops, int KA, int K, const int* __restrict__ nframes, int f, int B, int Bp, int H) {
+template <int NT, int KW, bool POOL = false>
+__global__ __launch_bounds__(64 * KW) void nat_dec_lstm_x3_k(NatLstmX3Ops ops, int KA, int K, const int* __restrict__ nframes, NatFrameArg<POOL> fa, int B, int Bp,
+                                                             int H) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     using vtts::bf16x8;
     constexpr int PD = 3;
@@ -906,12 +963,21 @@ __global__ __launch_bounds__(64 * KW) void nat_dec_lstm_x3_k(NatLstmX3Ops ops, i
     const int slice = blockIdx.x, b0 = blockIdx.y * 32 * NT;
     const int NST = K / 16, NWMAX = (NST + KW - 1) / KW, st_lo = kw * NWMAX;
     const int NW = st_lo >= NST ? 0 : (NST - st_lo < NWMAX ? NST - st_lo : NWMAX);
+    int fb[NT], nfb[NT];  // (a pool's rows look their frame up first, as in nat_dec_lstm_k)
+    if constexpr (POOL) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int b = b0 + 32 * nt + l31, bc = b < B ? b : B - 1;
+            fb[nt] = nat_row_frame(fa, bc), nfb[nt] = nframes[bc];
+        }
+    }
     f32x16 acc[NT];
     if (kw == 0) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int b = b0 + 32 * nt + l31;
-            const float4* __restrict__ gp = reinterpret_cast<const float4*>(ops.gin + (size_t)(b < B ? b : B - 1) * ops.gpitch + (size_t)(2 * slice + lh) * 16);
+            const float4* __restrict__ gp = reinterpret_cast<const float4*>(
+                nat_row_gin<POOL>(ops.gin, ops.gpitch, b < B ? b : B - 1, POOL ? fb[nt] : 0, POOL ? nfb[nt] : 0, 4 * H) + (size_t)(2 * slice + lh) * 16);
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
                 const float4 g4 = gp[rq];
@@ -956,7 +1022,8 @@ __global__ __launch_bounds__(64 * KW) void nat_dec_lstm_x3_k(NatLstmX3Ops ops, i
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int b = b0 + 32 * nt + l31;
-        live[nt] = b < B && f < nframes[b < B ? b : B - 1];
+        if constexpr (POOL) live[nt] = b < B && nat_row_live<true>(fb[nt], nfb[nt]);
+        else live[nt] = b < B && nat_row_live<false>(nat_row_frame(fa, b), nframes[b < B ? b : B - 1]);
         any = any || live[nt];
     }
     if (__ballot(any) == 0ull) return;
@@ -1161,11 +1228,13 @@ __global__ void nat_keep_masks_haiku_k(unsigned k0, unsigned k1, int mode, unsig
 // mel_f = [h1 ; h2] @ wp + bp, then the prenet of frame f + 1 into the other parity's state.  One
 // 1024-thread workgroup per 4 sentences (weights read once per k for the four).  Every product is split over k into
 // 1024 / width partial sums that are added in chunk order: a frame step is latency-bound, short dependent chains matter.
-template <bool X3>  // X3: the state is the bf16x3 step's (two bf16 planes, nat_zxidx; `plane` elements apart); h = hi + lo exactly, p is split on its way out
+// POOL: every row at its own frame (NatFrameArg); an idle row of a live group is carried through the sums and stores nothing, so a slot's
+// state stays what its reset made it until the row's first frame.
+template <bool X3, bool POOL = false>  // X3: the state is the bf16x3 step's (two bf16 planes, nat_zxidx; `plane` elements apart); h = hi + lo exactly, p is split on its way out
 __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __restrict__ zcur, float* __restrict__ znext,
                                                               const int* __restrict__ nframes, const float4* __restrict__ f1, const float4* __restrict__ f2,
                                                               const float4* __restrict__ wp, const float* __restrict__ bp,
-                                                              const unsigned char* __restrict__ keep, float* __restrict__ mel, int f, int B, int Bp,
+                                                              const unsigned char* __restrict__ keep, float* __restrict__ mel, NatFrameArg<POOL> fa, int B, int Bp,
                                                               int Fmax, int PN, int H, int MEL, size_t plane) {
     extern __shared__ float4 sq[];
     float4* hs = sq;              // [2H]   h1 ; h2 of the 4 sentences
@@ -1173,12 +1242,15 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
     float4* prev = part + 1024;   // [MEL]
     float4* p1 = prev + MEL;      // [PN]
     const int g = threadIdx.x, b0 = blockIdx.x * 4;
-    int nf[4];
+    int nf[4], fs[4];  // the rows' frame counts and the frame each stands at
+    bool live[4];
     bool any = false;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         nf[s] = b0 + s < B ? nframes[b0 + s] : 0;
-        any = any || f < nf[s];
+        fs[s] = nat_row_frame(fa, b0 + s < B ? b0 + s : B - 1);
+        live[s] = nat_row_live<POOL>(fs[s], nf[s]);
+        any = any || live[s];
     }
     if (!any) return;
     // the projection's bias and the keep bytes of frame f + 1, requested before anything else (each was a cold load behind a barrier: 0.7 us of a step)
@@ -1188,7 +1260,8 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
     for (int which = 0; which < 2; ++which)
 #pragma unroll
         for (int s = 0; s < 4; ++s)
-            kp[which][s] = (keep && g < PN && b0 + s < B && f + 1 < Fmax) ? keep[(((size_t)(b0 + s) * Fmax + f + 1) * 2 + which) * PN + g] : (unsigned char)1;
+            kp[which][s] = (keep && g < PN && b0 + s < B && (!POOL || live[s]) && fs[s] + 1 < Fmax) ? keep[(((size_t)(b0 + s) * Fmax + fs[s] + 1) * 2 + which) * PN + g]
+                                                                                                    : (unsigned char)1;
 #pragma clang loop vectorize(disable)  // (it would pair the hi + lo additions of two rows into v_pk_add_f32: build.py)
     for (int k = g; k < 2 * H; k += 1024) {
         if constexpr (X3) {
@@ -1238,10 +1311,20 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
         const float v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
         for (int s = 0; s < 4; ++s)
-            if (f < nf[s]) mel[((size_t)(b0 + s) * Fmax + f) * MEL + g] = v[s];
+            if (live[s]) mel[((size_t)(b0 + s) * Fmax + fs[s]) * MEL + g] = v[s];
     }
     __syncthreads();
-    if (f + 1 >= Fmax) return;
+    if constexpr (POOL) {  // the next frame's prenet for the rows that have a next frame
+        bool more = false;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            live[s] = live[s] && fs[s] + 1 < Fmax;
+            more = more || live[s];
+        }
+        if (!more) return;
+    } else {
+        if (fs[0] + 1 >= Fmax) return;
+    }
     auto masked = [&](float4 a, int which, int col) {  // relu, then hk.dropout(rate 0.5) with the given keep bytes of frame f + 1
         float v[4] = {fmaxf(a.x, 0.0f), fmaxf(a.y, 0.0f), fmaxf(a.z, 0.0f), fmaxf(a.w, 0.0f)};
         if (keep) {
@@ -1265,6 +1348,7 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
             const float v[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
+                if (POOL && !live[s]) continue;
                 const unsigned hp = vtts::pack_bf16x2(v[s], 0.0f);
                 const unsigned lp = vtts::pack_bf16x2(v[s] - vtts::bf16_lo(hp), 0.0f);
                 zw[8 * s] = (unsigned short)(hp & 0xffffu);
@@ -1272,7 +1356,14 @@ __global__ __launch_bounds__(1024) void nat_dec_proj_prenet_k(const float* __res
             }
         } else {
             float* __restrict__ zw = znext + nat_zidx(g, b0, Bp);
-            zw[0] = r.x; zw[4] = r.y; zw[8] = r.z; zw[12] = r.w;
+            if constexpr (POOL) {
+                const float v[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (live[s]) zw[4 * s] = v[s];
+            } else {
+                zw[0] = r.x; zw[4] = r.y; zw[8] = r.z; zw[12] = r.w;
+            }
         }
     }
 }
@@ -1499,6 +1590,67 @@ __global__ __launch_bounds__(256) void nat_window_k(const float4* __restrict__ s
     }
 }
 
+// ---- slot pool (vtts_nat_acoustic_pool_*): rows that start at any tick ----
+// The pool's per-slot words, written on the device in stream order: the tick a slot's row was admitted at, its frame count (0 = idle) and its token count.
+struct NatPoolMeta {
+    int *start, *nframes, *lengths;  // [slots] each
+};
+// A slot as pool_admit() needs it, behind every tick enqueued so far: the slot's columns of both state parities and of both cell states zero (X3: the
+// step's two bf16 planes per parity, nat_zxidx), its rows of the decoder's mel and of the caller's mel zero (C4 = Fmax * MEL / 4), its words set.
+template <bool X3>
+__global__ __launch_bounds__(256) void nat_pool_reset_k(float* __restrict__ dstate, float4* __restrict__ mel0, float4* __restrict__ mel, NatPoolMeta meta, int slot,
+                                                        int start, int nframes, int length, int Bp, int ZW, int H, int C4) {
+    const int gtid = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
+    const size_t zfloats = (size_t)ZW * Bp;
+    for (int i = gtid; i < 2 * ZW; i += stride) {
+        const int par = i / ZW, row = i % ZW;
+        if constexpr (X3) {
+            unsigned short* __restrict__ zx = reinterpret_cast<unsigned short*>(dstate + par * zfloats);
+            zx[nat_zxidx(row, slot, Bp)] = 0;
+            zx[zfloats + nat_zxidx(row, slot, Bp)] = 0;  // the lo plane: ZW * Bp bf16 elements behind the hi plane
+        } else {
+            dstate[par * zfloats + nat_zidx(row, slot, Bp)] = 0.0f;
+        }
+    }
+    float* __restrict__ cst = dstate + 2 * zfloats;  // c1 [H][Bp], c2 [H][Bp]
+    for (int i = gtid; i < 2 * H; i += stride) cst[(size_t)i * Bp + slot] = 0.0f;
+    for (int i = gtid; i < C4; i += stride) {
+        mel0[(size_t)slot * C4 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        mel[(size_t)slot * C4 + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (gtid == 0) meta.start[slot] = start, meta.nframes[slot] = nframes, meta.lengths[slot] = length;
+}
+// pool_retire(): the slot's row decodes no further frame
+__global__ void nat_pool_idle_k(NatPoolMeta meta, int slot) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) meta.nframes[slot] = 0;
+}
+// nat_window_k with a window per row (pool_finish()): list entry j is compact row r0 + j, the frames [lo, lo + n) of slot `slot`.  Gather: win[r0 + j][p] =
+// full[slot][lo + p] for p < n, zeros for n <= p < W, and wl[r0 + j] = n.  Scatter: full[slot][lo + p] = win[r0 + j][p] for k0 <= p < k1 (the host has cut
+// k1 at the row's last frame).  The list travels in the kernel's arguments, NAT_POOL_LIST rows a launch: no host memory is read in stream order.
+constexpr int NAT_POOL_LIST = 48;
+struct NatPoolWindows {
+    int count, r0;
+    int slot[NAT_POOL_LIST], lo[NAT_POOL_LIST], n[NAT_POOL_LIST], k0[NAT_POOL_LIST], k1[NAT_POOL_LIST];
+};
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void nat_pool_window_k(const float4* __restrict__ src, float4* __restrict__ dst, int* __restrict__ wl, NatPoolWindows L, int Fmax, int W,
+                                                         int C4) {
+    const size_t gtid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const size_t total = (size_t)L.count * W * C4;
+    for (size_t i = gtid; i < total; i += stride) {
+        const int c = (int)(i % C4), p = (int)((i / C4) % W), j = (int)(i / ((size_t)C4 * W));
+        const size_t fi = ((size_t)L.slot[j] * Fmax + L.lo[j] + p) * C4 + c, wi = ((size_t)(L.r0 + j) * W + p) * C4 + c;
+        if constexpr (SCATTER) {
+            if (p >= L.k0[j] && p < L.k1[j]) dst[fi] = src[wi];
+        } else {
+            dst[wi] = p < L.n[j] ? src[fi] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if constexpr (!SCATTER) {
+        for (size_t j = gtid; j < (size_t)L.count; j += stride) wl[L.r0 + j] = L.n[j];
+    }
+}
+
 int run_token_encoder(const NatModel& m, const std::string& te, int V, int D, const int32_t* tokens, const int32_t* lengths, int B, int Lmax,
                       float* bufA, float* bufB, float* lstm_ws, float* enc, hipStream_t s) {
     hipLaunchKernelGGL(nat_embed_k, dim3(Lmax, B), dim3(256), 0, s, tokens, lengths, m.dev(te + "embed", "embeddings"), bufA, Lmax, D, V);
@@ -1541,8 +1693,8 @@ int run_token_encoder(const NatModel& m, const std::string& te, int V, int D, co
                 o[dir].inB = hs + ((size_t)dir * (Lmax + 1) + st) * slab;
                 o[dir].hout = hs + ((size_t)dir * (Lmax + 1) + st + 1) * slab;
             }
-            if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o[0], o[1], D, D, lengths, st, B, Bp, D);
-            else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o[0], o[1], D, D, lengths, st, B, Bp, D);
+            if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o[0], o[1], D, D, lengths, NatFrameArg<false>{st}, B, Bp, D);
+            else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o[0], o[1], D, D, lengths, NatFrameArg<false>{st}, B, Bp, D);
         }
         hipLaunchKernelGGL(nat_enc_gather_k, dim3(Lmax, B), dim3(256), 0, s, hs, lengths, enc, Bp, Lmax, D);
     }
@@ -1621,6 +1773,15 @@ struct NatStreamWs : NatCarver {
         const size_t BW = (size_t)B * W * 4;
         wmel = take(BW * c.mel_dim), wpA = take(BW * c.postnet_dim), wpB = take(BW * c.postnet_dim), wout = take(BW * c.mel_dim);
         wl = reinterpret_cast<int32_t*>(take((size_t)B * 4));
+    }
+};
+
+// what a slot pool needs behind a session's layout `s`: the per-slot words
+struct NatPoolWs : NatCarver {
+    NatPoolMeta meta;
+    NatPoolWs(const NatStreamWs& s, int slots) : NatCarver{s.base, s.bytes} {
+        int* w = reinterpret_cast<int*>(take((size_t)3 * slots * 4));
+        meta = NatPoolMeta{w, w ? w + slots : nullptr, w ? w + 2 * slots : nullptr};
     }
 };
 
@@ -2239,8 +2400,8 @@ int nat_dec_frames(const NatCall& c, int fa, int fb, bool gates_wait) {
     const dim3 lgrid(H / 8, wide ? Bp / 64 : 1);
     auto lstm = [&](const float* inA, int KA, const float* inB, const float4* w, const float* gin, float* cst, float* hout, int f) {
         const NatLstmOps o{inA, inB, w, nullptr, cst, hout, gin + (size_t)f * G4, (size_t)Fmax * G4};
-        if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, f, B, Bp, H);
-        else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, f, B, Bp, H);
+        if (wide) hipLaunchKernelGGL((nat_dec_lstm_k<2, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, NatFrameArg<false>{f}, B, Bp, H);
+        else hipLaunchKernelGGL((nat_dec_lstm_k<1, 8>), lgrid, dim3(512), 0, s, o, o, KA, H, c.nframes, NatFrameArg<false>{f}, B, Bp, H);
     };
     const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);  // at most 64 KiB: create()'s limits at once (H = 1024, PN = 896, MEL = 128)
     if (plds > 48 * 1024) {
@@ -2264,8 +2425,8 @@ int nat_dec_frames(const NatCall& c, int fa, int fb, bool gates_wait) {
     const uint4 *w1x = h->extra<uint4>("lstm/linear#x3"), *w2x = h->extra<uint4>("lstm_1/linear#x3");
     auto lstm_x3 = [&](unsigned short* zcx, const unsigned short* zpx, int KA, int K, const uint4* w, const float* gin, float* cst, int out_row0, int f) {
         const NatLstmX3Ops o{zcx, zpx, zplane, w, gin + (size_t)f * G4, (size_t)Fmax * G4, cst, zcx, out_row0};
-        if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, f, B, Bp, H);
-        else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, f, B, Bp, H);
+        if (wide) hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, NatFrameArg<false>{f}, B, Bp, H);
+        else hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8>), lgrid, dim3(512), 0, s, o, KA, K, c.nframes, NatFrameArg<false>{f}, B, Bp, H);
     };
     for (int f = fa; f < fb; ++f) {
         if (f == 64 && gates_wait) HIP_TRY(hipStreamWaitEvent(s, h->ev_gates, 0));
@@ -2276,12 +2437,12 @@ int nat_dec_frames(const NatCall& c, int fa, int fb, bool gates_wait) {
             const unsigned short* zpx = reinterpret_cast<const unsigned short*>(zp);
             lstm_x3(zcx, zpx, PN, PN + H, w1x, ws.G1, c1, PN, f);
             lstm_x3(zcx, zpx, PN + H, PN + 2 * H, w2x, ws.G2, c2, PN + H, f);
-            hipLaunchKernelGGL(nat_dec_proj_prenet_k<true>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, c.nframes, f1, f2, wp, bp, c.keep, ws.mel0, f, B, Bp,
+            hipLaunchKernelGGL(nat_dec_proj_prenet_k<true>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, c.nframes, f1, f2, wp, bp, c.keep, ws.mel0, NatFrameArg<false>{f}, B, Bp,
                                Fmax, PN, H, MEL, zplane);
         } else {
             lstm(zc, PN, zp + (size_t)PN * Bp, w1, ws.G1, c1, zc + (size_t)PN * Bp, f);
             lstm(zc, PN + H, zp + (size_t)(PN + H) * Bp, w2, ws.G2, c2, zc + (size_t)(PN + H) * Bp, f);
-            hipLaunchKernelGGL(nat_dec_proj_prenet_k<false>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, c.nframes, f1, f2, wp, bp, c.keep, ws.mel0, f, B, Bp,
+            hipLaunchKernelGGL(nat_dec_proj_prenet_k<false>, dim3((B + 3) / 4), dim3(1024), plds, s, zc, zp, c.nframes, f1, f2, wp, bp, c.keep, ws.mel0, NatFrameArg<false>{f}, B, Bp,
                                Fmax, PN, H, MEL, (size_t)0);
         }
         if (int rc = group_handover(f + 1)) return rc;  // under the remaining decoder steps
@@ -2315,7 +2476,7 @@ int nat_ar_decoder(const NatCall& c) {
 
 // forward(), forward_groups(), forward_from_encoder() and forward_teacher()
 int nat_acoustic_run(NatCall& c) {
-    if (c.h) c.h->ss.open = false;  // any forward*() ends an open streaming session
+    if (c.h) c.h->ss.open = c.h->pool.open = false;  // any forward*() ends an open streaming session or slot pool
     if (int rc = nat_validate(c)) return rc;
     vtts_nat_acoustic* h = c.h;
     if (int rc = nat_side_stream(h, c.ngroups)) return rc;
@@ -2378,7 +2539,7 @@ VTTS_API int vtts_nat_acoustic_forward_teacher(vtts_nat_acoustic* h, const int32
 VTTS_API int vtts_nat_acoustic_encode(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, int B, int Lmax, float* enc_dev,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !tokens_dev || !lengths_dev || !enc_dev) return failf(VTTS_ERR_INVALID, "null argument");
-    h->ss.open = false;  // (its buffers are a session's too)
+    h->ss.open = h->pool.open = false;  // (its buffers are a session's and a pool's too)
     if (!h->blob) return failf(VTTS_ERR_STATE, "encode() before pack()/bind_packed()");
     size_t need = 0;
     int rc = vtts_nat_acoustic_workspace_bytes(h, B, Lmax, 1, &need);
@@ -2442,7 +2603,7 @@ VTTS_API int vtts_nat_acoustic_stream_workspace_bytes(const vtts_nat_acoustic* h
 VTTS_API int vtts_nat_acoustic_stream_begin(vtts_nat_acoustic* h, const int32_t* tokens_dev, const int32_t* lengths_dev, const float* durations_dev,
                                             const int32_t* nframes_dev, int B, int Lmax, int Fmax, const uint8_t* keep_dev, float* mel_dev, void* workspace,
                                             size_t workspace_bytes, int max_window, void* stream) {
-    if (h) h->ss.open = false;
+    if (h) h->ss.open = h->pool.open = false;
     if (!tokens_dev) return failf(VTTS_ERR_INVALID, "null argument");
     NatCall c{h, tokens_dev, lengths_dev, durations_dev, nframes_dev, B, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     if (int rc = nat_validate(c)) return rc;
@@ -2504,5 +2665,244 @@ VTTS_API int vtts_nat_acoustic_stream_finish(vtts_nat_acoustic* h, int f0, int f
 VTTS_API int vtts_nat_acoustic_stream_end(vtts_nat_acoustic* h) {
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
     h->ss.open = false;
+    return VTTS_OK;
+}
+
+// ------------------------------------------------ slot pool ------------------------------------------------
+// The session's cut along time with a frame cursor PER ROW (include/vtts_nat.h): a tick is one frame step of every slot, the three launches of
+// nat_dec_frames() in their POOL form, row b at frame tick - start[b].  The state ping-pong goes by the TICK's parity: a row admitted at an odd
+// tick reads as "previous" what the tick before it left, which for its frame 0 is the zeros of its reset, in both parities.
+namespace {
+
+int nat_not_capturing(const char* what, hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone) return failf(VTTS_ERR_INVALID, "%s: the stream is being captured (a pool's launches depend on host state)", what);
+    return VTTS_OK;
+}
+
+// the pool's call on `stream` (B = every slot), or a status: no handle, no pool, the option "bf16x3" changed under it, a stream that is being captured
+int nat_pool_call(vtts_nat_acoustic* h, const char* what, void* stream, NatCall* c) {
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    const vtts_nat_acoustic::Pool& p = h->pool;
+    if (!p.open) return failf(VTTS_ERR_STATE, "%s: no open pool (pool_open() first; any forward*(), encode(), stream_begin() or pool_close() closes it)", what);
+    if (h->x3 != p.x3) return failf(VTTS_ERR_STATE, "%s: the option bf16x3 changed since pool_open()", what);
+    if (int rc = nat_not_capturing(what, static_cast<hipStream_t>(stream))) return rc;
+    *c = NatCall{h, nullptr, nullptr, nullptr, nullptr, p.slots, p.Lmax, p.Fmax, p.keep, p.mel, p.workspace, p.workspace_bytes, static_cast<hipStream_t>(stream)};
+    nat_derive(*c);
+    return VTTS_OK;
+}
+NatPoolWs nat_pool_ws(const NatCall& c) {
+    return NatPoolWs(NatStreamWs(c.ws, c.h->cfg, c.B, c.Fmax, c.h->pool.max_window), c.B);
+}
+int nat_pool_slot(const NatCall& c, const char* what, int slot, bool busy) {
+    if (slot < 0 || slot >= c.B) return failf(VTTS_ERR_INVALID, "%s: slot %d of a pool of %d", what, slot, c.B);
+    if (c.h->pool.slot[slot].busy != busy) return failf(VTTS_ERR_STATE, "%s: slot %d is %s", what, slot, busy ? "free" : "busy (pool_retire() frees it)");
+    return VTTS_OK;
+}
+// whether the decoder runs the split-state step (nat_dec_frames: dx3)
+bool nat_dec_x3(const NatCall& c) {
+    return c.h->x3 && c.PN % 16 == 0 && c.H % 16 == 0 && ((c.PN + c.H) / 16) % 8 == 0 && ((c.PN + 2 * c.H) / 16) % 8 == 0;
+}
+
+// ticks [ta, tb) for every slot: nat_dec_frames()'s operands and launches, the frame argument per row
+int nat_pool_ticks(const NatCall& c, const NatPoolMeta& meta, int ta, int tb) {
+    vtts_nat_acoustic* h = c.h;
+    const NatAcousticWs& ws = c.ws;
+    const int B = c.B, Bp = c.Bp, Fmax = c.Fmax, H = c.H, PN = c.PN, MEL = c.MEL, G4 = c.G4, ZW = PN + 2 * H;
+    hipStream_t s = c.s;
+    float* Z[2] = {ws.dstate, ws.dstate + (size_t)ZW * Bp};
+    float* c1 = ws.dstate + 2 * (size_t)ZW * Bp;
+    float* c2 = c1 + (size_t)H * Bp;
+    const float4 *w1 = h->extra<float4>("lstm/linear#mfma"), *w2 = h->extra<float4>("lstm_1/linear#mfma");
+    const float4 *f1 = h->extra<float4>("linear_1#k4"), *f2 = h->extra<float4>("linear_2#k4"), *wp = h->extra<float4>("linear#k4");
+    const uint4 *w1x = h->extra<uint4>("lstm/linear#x3"), *w2x = h->extra<uint4>("lstm_1/linear#x3");
+    const float* bp = h->dev("linear", "b");
+    const bool wide = B > 32, dx3 = nat_dec_x3(c);
+    const dim3 lgrid(H / 8, wide ? Bp / 64 : 1), pgrid((B + 3) / 4);
+    const size_t gp = (size_t)Fmax * G4, zplane = (size_t)ZW * Bp;
+    const size_t plds = ((size_t)2 * H + 1024 + MEL + PN) * sizeof(float4);
+    if (plds > 48 * 1024) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_dec_proj_prenet_k<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nat_dec_proj_prenet_k<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+    }
+    for (int t = ta; t < tb; ++t) {
+        const NatFrameArg<true> fa{t, meta.start};
+        float* zc = Z[t & 1];
+        float* zp = Z[(t + 1) & 1];
+        if (dx3) {
+            unsigned short* zcx = reinterpret_cast<unsigned short*>(zc);
+            const unsigned short* zpx = reinterpret_cast<const unsigned short*>(zp);
+            const NatLstmX3Ops o1{zcx, zpx, zplane, w1x, ws.G1, gp, c1, zcx, PN}, o2{zcx, zpx, zplane, w2x, ws.G2, gp, c2, zcx, PN + H};
+            if (wide) {
+                hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8, true>), lgrid, dim3(512), 0, s, o1, PN, PN + H, meta.nframes, fa, B, Bp, H);
+                hipLaunchKernelGGL((nat_dec_lstm_x3_k<2, 8, true>), lgrid, dim3(512), 0, s, o2, PN + H, PN + 2 * H, meta.nframes, fa, B, Bp, H);
+            } else {
+                hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8, true>), lgrid, dim3(512), 0, s, o1, PN, PN + H, meta.nframes, fa, B, Bp, H);
+                hipLaunchKernelGGL((nat_dec_lstm_x3_k<1, 8, true>), lgrid, dim3(512), 0, s, o2, PN + H, PN + 2 * H, meta.nframes, fa, B, Bp, H);
+            }
+            hipLaunchKernelGGL((nat_dec_proj_prenet_k<true, true>), pgrid, dim3(1024), plds, s, zc, zp, meta.nframes, f1, f2, wp, bp, c.keep, ws.mel0, fa, B, Bp, Fmax, PN, H,
+                               MEL, zplane);
+        } else {
+            const NatLstmOps o1{zc, zp + (size_t)PN * Bp, w1, nullptr, c1, zc + (size_t)PN * Bp, ws.G1, gp};
+            const NatLstmOps o2{zc, zp + (size_t)(PN + H) * Bp, w2, nullptr, c2, zc + (size_t)(PN + H) * Bp, ws.G2, gp};
+            if (wide) {
+                hipLaunchKernelGGL((nat_dec_lstm_k<2, 8, 1, true>), lgrid, dim3(512), 0, s, o1, o1, PN, H, meta.nframes, fa, B, Bp, H);
+                hipLaunchKernelGGL((nat_dec_lstm_k<2, 8, 1, true>), lgrid, dim3(512), 0, s, o2, o2, PN + H, H, meta.nframes, fa, B, Bp, H);
+            } else {
+                hipLaunchKernelGGL((nat_dec_lstm_k<1, 8, 1, true>), lgrid, dim3(512), 0, s, o1, o1, PN, H, meta.nframes, fa, B, Bp, H);
+                hipLaunchKernelGGL((nat_dec_lstm_k<1, 8, 1, true>), lgrid, dim3(512), 0, s, o2, o2, PN + H, H, meta.nframes, fa, B, Bp, H);
+            }
+            hipLaunchKernelGGL((nat_dec_proj_prenet_k<false, true>), pgrid, dim3(1024), plds, s, zc, zp, meta.nframes, f1, f2, wp, bp, c.keep, ws.mel0, fa, B, Bp, Fmax, PN, H,
+                               MEL, (size_t)0);
+        }
+    }
+    return VTTS_OK;
+}
+
+}  // namespace
+
+VTTS_API int vtts_nat_acoustic_pool_workspace_bytes(const vtts_nat_acoustic* h, int slots, int Lmax, int Fmax, int max_window, size_t* bytes) {
+    if (int rc = vtts_nat_acoustic_stream_workspace_bytes(h, slots, Lmax, Fmax, max_window, bytes)) return rc;
+    *bytes = NatPoolWs(NatStreamWs(NatAcousticWs(h->cfg, slots, Lmax, Fmax, nullptr), h->cfg, slots, Fmax, max_window), slots).bytes;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_pool_open(vtts_nat_acoustic* h, int slots, int Lmax, int Fmax, int max_window, const uint8_t* keep_dev, float* mel_dev, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    if (h) h->ss.open = h->pool.open = false;
+    if (!h || !mel_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h->blob) return failf(VTTS_ERR_STATE, "pool_open() before pack()/bind_packed()");
+    size_t need = 0;
+    if (int rc = vtts_nat_acoustic_pool_workspace_bytes(h, slots, Lmax, Fmax, max_window, &need)) return rc;
+    if (!workspace || workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes (pool_workspace_bytes())", workspace_bytes, need);
+    if (Lmax > 2048) return failf(VTTS_ERR_INVALID, "at most 2048 tokens per sentence (upsampling weights live in LDS)");
+    if ((uintptr_t)mel_dev % 16 != 0) return failf(VTTS_ERR_INVALID, "pool_open(): mel_dev is written in 16-byte units: align it so");
+    if (int rc = nat_not_capturing("pool_open()", static_cast<hipStream_t>(stream))) return rc;
+    NatCall c{h, nullptr, nullptr, nullptr, nullptr, slots, Lmax, Fmax, keep_dev, mel_dev, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    nat_derive(c);
+    h->resident_used = 0;
+    h->stage_valid = 0;
+    h->pool.max_window = max_window;
+    const NatPoolWs pw = nat_pool_ws(c);
+    // every slot idle (nframes 0) over a zero state, a zero decoder mel and a zero mel
+    HIP_TRY(hipMemsetAsync(pw.meta.start, 0, (size_t)3 * slots * 4, c.s));
+    HIP_TRY(hipMemsetAsync(c.mel, 0, (size_t)slots * Fmax * c.MEL * 4, c.s));
+    if (int rc = nat_dec_reset(c)) return rc;
+    vtts_nat_acoustic::Pool& p = h->pool;
+    p.keep = keep_dev, p.mel = mel_dev, p.workspace = workspace, p.workspace_bytes = workspace_bytes;
+    p.slots = slots, p.Lmax = Lmax, p.Fmax = Fmax, p.x3 = h->x3, p.tick = 0;
+    p.slot.assign(slots, vtts_nat_acoustic::Pool::Slot{});
+    p.open = true;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_pool_admit(vtts_nat_acoustic* h, int slot, const int32_t* tokens_dev, int length, const float* durations_dev, int nframes, void* stream) {
+    NatCall c;
+    if (int rc = nat_pool_call(h, "pool_admit()", stream, &c)) return rc;
+    if (!tokens_dev || !durations_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (length < 1 || length > c.Lmax) return failf(VTTS_ERR_INVALID, "pool_admit(): %d tokens; the pool was opened for 1 .. %d", length, c.Lmax);
+    if (nframes < 1 || nframes > c.Fmax) return failf(VTTS_ERR_INVALID, "pool_admit(): %d frames; the pool was opened for 1 .. %d", nframes, c.Fmax);
+    if (int rc = nat_pool_slot(c, "pool_admit()", slot, false)) return rc;
+    vtts_nat_acoustic::Pool& p = h->pool;
+    const NatPoolWs pw = nat_pool_ws(c);
+    // the reset goes first: it writes the slot's token and frame counts, which the row's encoder and gate mix read
+    const int ZW = c.PN + 2 * c.H, C4 = c.Fmax * c.MEL / 4;
+    const dim3 rgrid(std::max(1, std::min(64, (std::max(2 * ZW, C4) + 255) / 256)));
+    float4* mel0 = reinterpret_cast<float4*>(c.ws.mel0);
+    float4* mel = reinterpret_cast<float4*>(c.mel);
+    if (nat_dec_x3(c)) hipLaunchKernelGGL(nat_pool_reset_k<true>, rgrid, dim3(256), 0, c.s, c.ws.dstate, mel0, mel, pw.meta, slot, p.tick, nframes, length, c.Bp, ZW, c.H, C4);
+    else hipLaunchKernelGGL(nat_pool_reset_k<false>, rgrid, dim3(256), 0, c.s, c.ws.dstate, mel0, mel, pw.meta, slot, p.tick, nframes, length, c.Bp, ZW, c.H, C4);
+    // a one-row call on the slot's rows of the pool's buffers ([B][...] row-major: offset pointers); the encoder LSTMs' scratch is the pool's, one admission at a time
+    NatCall r = c;
+    const size_t LD = (size_t)slot * c.Lmax * h->cfg.encoder_dim, LG = (size_t)slot * c.Lmax * c.G4, FG = (size_t)slot * c.Fmax * c.G4;
+    r.tokens = tokens_dev, r.durations = durations_dev, r.lengths = pw.meta.lengths + slot, r.nframes = pw.meta.nframes + slot;
+    r.B = 1, r.Bp = 64;
+    r.ws.bufA += LD, r.ws.bufB += LD, r.ws.enc += 2 * LD, r.ws.EG1 += LG, r.ws.EG2 += LG, r.ws.G1 += FG, r.ws.G2 += FG;
+    if (int rc = run_token_encoder(*h, "token_encoder/~/", h->cfg.vocab_size, h->cfg.encoder_dim, r.tokens, r.lengths, 1, r.Lmax, r.ws.bufA, r.ws.bufB, r.ws.lstm_ws, r.ws.enc, r.s)) return rc;
+    if (int rc = nat_cond_gates(r, r.mtiles)) return rc;  // every frame's mix on the caller's stream, as stream_begin()
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "pool admission launch failed: %s", hipGetErrorString(e));
+    p.slot[slot] = vtts_nat_acoustic::Pool::Slot{true, p.tick, nframes, 0};
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_pool_decode(vtts_nat_acoustic* h, int nticks, void* stream) {
+    NatCall c;
+    if (int rc = nat_pool_call(h, "pool_decode()", stream, &c)) return rc;
+    vtts_nat_acoustic::Pool& p = h->pool;
+    if (nticks < 0 || nticks > INT32_MAX - p.tick) return failf(VTTS_ERR_INVALID, "pool_decode(%d): the pool stands at tick %d; ticks are counted in 31 bits", nticks, p.tick);
+    if (int rc = nat_pool_ticks(c, nat_pool_ws(c).meta, p.tick, p.tick + nticks)) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "decoder launch failed: %s", hipGetErrorString(e));
+    p.tick += nticks;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_pool_finish(vtts_nat_acoustic* h, int n, const int32_t* slots, const int32_t* f0, const int32_t* f1, void* stream) {
+    NatCall c;
+    if (int rc = nat_pool_call(h, "pool_finish()", stream, &c)) return rc;
+    vtts_nat_acoustic::Pool& p = h->pool;
+    if (n < 1 || n > c.B || !slots || !f0 || !f1) return failf(VTTS_ERR_INVALID, "pool_finish(): 1 .. %d rows and their windows (got %d)", c.B, n);
+    // every row is checked before anything is enqueued
+    std::vector<int> end(n);
+    std::vector<char> seen(c.B, 0);
+    for (int j = 0; j < n; ++j) {
+        if (int rc = nat_pool_slot(c, "pool_finish()", slots[j], true)) return rc;
+        const vtts_nat_acoustic::Pool::Slot& sl = p.slot[slots[j]];
+        if (seen[slots[j]]) return failf(VTTS_ERR_INVALID, "pool_finish(): slot %d is listed twice", slots[j]);
+        seen[slots[j]] = 1;
+        if (f0[j] != sl.finished || f1[j] <= f0[j] || f0[j] >= sl.nframes)
+            return failf(VTTS_ERR_INVALID, "pool_finish(): slot %d, [%d, %d): windows are issued in order, contiguous and not empty; the next one starts at frame %d of %d",
+                         slots[j], f0[j], f1[j], sl.finished, sl.nframes);
+        if (f1[j] - f0[j] > p.max_window) return failf(VTTS_ERR_INVALID, "pool_finish(): slot %d, [%d, %d): the pool was opened for windows of at most %d frames", slots[j], f0[j], f1[j], p.max_window);
+        end[j] = std::min(f1[j], sl.nframes);
+        const int hi = std::min(sl.nframes, end[j] + VTTS_NAT_POSTNET_HALO);
+        if (p.cursor(slots[j]) < hi)
+            return failf(VTTS_ERR_STATE, "pool_finish(): slot %d, [%d, %d) reads the decoder's frames up to %d: the slot's row has reached %d", slots[j], f0[j], f1[j], hi, p.cursor(slots[j]));
+    }
+    const NatStreamWs w(c.ws, h->cfg, c.B, c.Fmax, p.max_window);
+    const int C4 = c.MEL / 4;
+    auto blocks = [](size_t elems) { return (int)std::min<size_t>((elems + 255) / 256, 65535); };
+    // the list in launches of NAT_POOL_LIST rows; one postnet pass over all of them in between
+    int npos = 0;
+    auto windows = [&](bool scatter) {
+        for (int j0 = 0; j0 < n; j0 += NAT_POOL_LIST) {
+            NatPoolWindows L{};
+            L.count = std::min(NAT_POOL_LIST, n - j0), L.r0 = j0;
+            for (int q = 0; q < L.count; ++q) {
+                const int j = j0 + q, nf = p.slot[slots[j]].nframes;
+                const int lo = std::max(0, f0[j] - VTTS_NAT_POSTNET_HALO), hi = std::min(nf, end[j] + VTTS_NAT_POSTNET_HALO);
+                L.slot[q] = slots[j], L.lo[q] = lo, L.n[q] = hi - lo, L.k0[q] = f0[j] - lo, L.k1[q] = end[j] - lo;
+                npos = std::max(npos, hi - lo);
+            }
+            const dim3 grid(blocks((size_t)L.count * w.W * C4));
+            if (scatter) hipLaunchKernelGGL(nat_pool_window_k<true>, grid, dim3(256), 0, c.s, reinterpret_cast<const float4*>(w.wout), reinterpret_cast<float4*>(c.mel), static_cast<int*>(nullptr), L, c.Fmax, w.W, C4);
+            else hipLaunchKernelGGL(nat_pool_window_k<false>, grid, dim3(256), 0, c.s, reinterpret_cast<const float4*>(c.ws.mel0), reinterpret_cast<float4*>(w.wmel), w.wl, L, c.Fmax, w.W, C4);
+        }
+    };
+    windows(false);
+    nat_postnet_run(c, NatPostnetBufs{n, npos, w.W, w.wl, w.wmel, {w.wpA, w.wpB}, w.wout}, c.s);
+    windows(true);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "postnet window launch failed: %s", hipGetErrorString(e));
+    for (int j = 0; j < n; ++j) p.slot[slots[j]].finished = end[j];
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_pool_retire(vtts_nat_acoustic* h, int slot, void* stream) {
+    NatCall c;
+    if (int rc = nat_pool_call(h, "pool_retire()", stream, &c)) return rc;
+    if (int rc = nat_pool_slot(c, "pool_retire()", slot, true)) return rc;
+    hipLaunchKernelGGL(nat_pool_idle_k, dim3(1), dim3(64), 0, c.s, nat_pool_ws(c).meta, slot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return failf(VTTS_ERR_HIP, "pool_retire() launch failed: %s", hipGetErrorString(e));
+    h->pool.slot[slot].busy = false;
+    return VTTS_OK;
+}
+
+VTTS_API int vtts_nat_acoustic_pool_close(vtts_nat_acoustic* h) {
+    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
+    h->pool.open = false;
     return VTTS_OK;
 }

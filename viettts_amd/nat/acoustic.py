@@ -350,6 +350,112 @@ class AcousticModel(NativeHandle):
         self._on_stream("stream_begin", ptr(tok_d), ptr(len_d), ptr(dur_d), ptr(nf_d), B, Lmax, Fmax, ptr(keep_d), ptr(mel), ptr(ws), ws.numel(), int(max_window))
         return MelStream(self, self._session, mel, (inputs, ws), Fmax)
 
+    def open_pool(self, slots: int, Lmax: int, Fmax: int, max_window: int, dropout: bool = True) -> "MelPool":
+        """A slot pool (include/vtts_nat.h): ``slots`` rows of at most ``Lmax`` tokens and ``Fmax`` frames that sentences enter and leave one by one
+        while the decoder steps all of them (:class:`MelPool`).  ``max_window``: the most frames of a row one :meth:`MelPool.finish` covers.
+        ``dropout=False``: no keep masks, no row has dropout.  One pool or stream per model: opening another, or any call of the model, ends it."""
+        if self._blob is None:
+            raise RuntimeError("no parameters loaded")
+        slots, Lmax, Fmax, max_window = int(slots), int(Lmax), int(Fmax), int(max_window)
+        if min(slots, Lmax, Fmax, max_window) < 1:
+            raise ValueError("slots, Lmax, Fmax and max_window must be positive")
+        mel = torch.empty((slots, Fmax, self.mel_dim), dtype=torch.float32, device=self.device)
+        keep = torch.ones((slots, Fmax, 2, self.prenet_dim), dtype=torch.uint8, device=self.device) if dropout else None
+        n = C.c_size_t(0)
+        self._call("pool_workspace_bytes", slots, Lmax, Fmax, max_window, C.byref(n))
+        ws = self._workspace(int(n.value))
+        self._session = getattr(self, "_session", 0) + 1
+        self._on_stream("pool_open", slots, Lmax, Fmax, max_window, ptr(keep), ptr(mel), ptr(ws), ws.numel())
+        return MelPool(self, self._session, mel, keep, ws, slots, Lmax, Fmax, max_window)
+
+
+class MelPool:
+    """An open slot pool of an :class:`AcousticModel` (:meth:`AcousticModel.open_pool`).  ``mel`` is the ``[slots, Fmax, mel_dim]`` device tensor the
+    windows land in.  The host's copy of the pool's clock: ``tick``, and per slot ``busy``, ``start``, ``n_frames``, ``finished`` and
+    :meth:`cursor`.  Work is enqueued on torch's current stream of the model's device.  A context manager; :meth:`close` is idempotent."""
+
+    def __init__(self, model: AcousticModel, ticket: int, mel: torch.Tensor, keep, ws, slots: int, Lmax: int, Fmax: int, max_window: int):
+        self._model, self._ticket, self.mel, self._keep, self._ws = model, ticket, mel, keep, ws
+        self.slots, self.Lmax, self.Fmax, self.max_window = slots, Lmax, Fmax, max_window
+        self.tick = 0
+        self.busy = [False] * slots
+        self.start, self.n_frames, self.finished = [0] * slots, [0] * slots, [0] * slots
+        self._held = [None] * slots  # a slot's tokens and durations on the device: the library reads them until the slot is retired
+
+    def _mine(self) -> bool:  # a later open_pool() / open_stream() took the handle: this object must not drive (or end) that one
+        return self._model is not None and self._model._session == self._ticket
+
+    def _on_stream(self, name: str, *args) -> None:
+        if not self._mine():
+            raise _lib.VttsError(-2, f"{name}: this pool is closed")
+        self._model._on_stream(name, *args)
+
+    def cursor(self, slot: int) -> int:
+        """Frames of the slot's row the ticks enqueued so far decode."""
+        return min(max(self.tick - self.start[slot], 0), self.n_frames[slot]) if self.busy[slot] else 0
+
+    def admit(self, slot: int, tokens: Sequence[int], durations_frames, n_frames: int, dropout_seed: Optional[int] = None, keep_mask=None) -> None:
+        """A sentence into the free slot ``slot``: token ids, per-token durations in FRAMES, its frame count; its first frame is decoded by the next
+        tick.  Dropout as :meth:`AcousticModel.__call__`: ``keep_mask`` (``[n_frames, 2, prenet_dim]`` host array) or ``dropout_seed``, else none."""
+        m, slot, n_frames = self._model, int(slot), int(n_frames)
+        if not self._mine():
+            raise _lib.VttsError(-2, "pool_admit: this pool is closed")
+        if (keep_mask is not None or dropout_seed is not None) and self._keep is None:
+            raise ValueError("the pool was opened with dropout=False")
+        tok, dur = padded_rows([list(tokens)], [np.asarray(durations_frames, dtype=np.float32)], max(self.Lmax, len(tokens)))
+        tok_d, dur_d = torch.from_numpy(tok[0]).to(m.device), torch.from_numpy(dur[0]).to(m.device)
+        fill = self._keep is not None and 0 <= slot < self.slots and not self.busy[slot] and 1 <= n_frames <= self.Fmax and 1 <= len(tokens) <= self.Lmax
+        if fill:  # the slot's keep rows, in stream order in front of the admission (a call the library will refuse fills nothing)
+            if keep_mask is not None:
+                row = np.ones((self.Fmax, 2, m.prenet_dim), dtype=np.uint8)
+                row[:n_frames] = np.asarray(keep_mask, dtype=bool)[:n_frames]
+                self._keep[slot].copy_(torch.from_numpy(row).to(m.device))
+            elif dropout_seed is not None:
+                self._keep[slot].copy_(m.device_keep_masks([dropout_seed], self.Fmax)[0])
+            else:
+                self._keep[slot].fill_(1)
+        self._on_stream("pool_admit", slot, ptr(tok_d), len(tokens), ptr(dur_d), n_frames)
+        self._held[slot] = (tok_d, dur_d)
+        self.busy[slot], self.start[slot], self.n_frames[slot], self.finished[slot] = True, self.tick, n_frames, 0
+
+    def decode(self, nticks: int) -> None:
+        """Enqueue ``nticks`` frame steps of every slot."""
+        self._on_stream("pool_decode", int(nticks))
+        self.tick += int(nticks)
+
+    def finish(self, windows: Sequence[tuple]) -> None:
+        """``windows``: ``(slot, f0, f1)`` each, a slot at most once.  Enqueue postnet + residual of those frames of those rows into :attr:`mel`, all in
+        one pass; per row the windows come in order and contiguous, and the row's cursor must have reached ``min(f1 + 10, n_frames)``."""
+        n = len(windows)
+        arr = [(C.c_int32 * max(n, 1))(*[int(w[k]) for w in windows]) for k in range(3)]
+        self._on_stream("pool_finish", n, *arr)
+        for sl, _, f1 in windows:
+            self.finished[sl] = min(int(f1), self.n_frames[sl])
+
+    def retire(self, slot: int) -> None:
+        """Free the slot; its row decodes no further frame."""
+        self._on_stream("pool_retire", int(slot))
+        self.busy[int(slot)] = False
+        self._held[int(slot)] = None
+
+    def close(self) -> None:
+        if self._model is not None:
+            if self._mine() and self._model._h.value:
+                self._model._call("pool_close")
+            self._model = self._held = self._keep = self._ws = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class MelStream:
     """An open streaming session of an :class:`AcousticModel` (:meth:`AcousticModel.open_stream`).  ``mel`` is the ``[B, Fmax, mel_dim]`` device tensor
