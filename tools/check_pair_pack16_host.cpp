@@ -1,5 +1,5 @@
 // Host-only check of vtts::pair_g_pack16 (viettts_amd/csrc/vtts_internal.h): the weight order that resblock_pair_g_bf16_k's 16 x 16 x 32 loops read.
-// For (C, K) = (128, 3) and (256, 11) it packs random weights into a buffer of exactly the old geometry's byte count (an overrun is the sanitizer's
+// For (C, K) = (64, 7), (64, 11), (128, 3) and (256, 11) it packs random weights into a buffer of exactly the old geometry's byte count (an overrun is the sanitizer's
 // to report), then looks every (tap, ci, co) up where the fragment map says it is — [q = tap*(C/32) + ks][mblk16][lane][8], co = 16 mblk + (lane & 15),
 // ci = 32 ks + 8 (lane >> 4) + e — and counts the elements visited: each exactly once.  Links nothing of the HIP runtime and needs no GPU:
 //
@@ -39,4 +39,4 @@ static int check(int C, int K) {
     return bad != 0;
 }
 
-int main() { return check(128, 3) | check(256, 11); }
+int main() { return check(64, 7) | check(64, 11) | check(128, 3) | check(256, 11); }

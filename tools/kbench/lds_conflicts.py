@@ -53,6 +53,20 @@ def check16(SPR, off):
     return rd, wr, st
 
 
+def check16_blocked(SPR, off):
+    """the 16x16x32 kernel's accesses on the blocked tiles (C = 64: SPR = 8): the same fragment reads and epilogue writes as check16, and the
+    blocked tiles' staging writes (lane -> row l % RW, slot l / RW)"""
+    rd = wr = st = 0
+    rw = 64 // SPR
+    for r0 in range(64):
+        for ks in range(SPR // 4):
+            rd += conflicts([off(r0 + (l & 15), 4 * ks + (l >> 4)) for l in range(64)], RG, 16)
+        for s0 in range(0, SPR, 2):
+            wr += conflicts([off(r0 + 16 * ((l >> 4) & 1) + (l & 15), s0 + (l >> 5)) for l in range(64)], WG, 8)
+        st += conflicts([off(r0 + l % rw, l // rw) for l in range(64)], WG, 8)
+    return rd, wr, st
+
+
 def check(SPR, off, stage_blocked):
     rd = wr = st = 0
     for r0 in range(64):
@@ -73,7 +87,9 @@ if __name__ == "__main__":
     for SPR in (4, 8, 16, 32):
         print(f"SPR {SPR:2d}  XOR swizzle {check(SPR, xor_off(SPR), False)}", end="")
         if SPR <= 8:
-            print(f"   blocked {check(SPR, blocked_off(SPR), True)}")
+            print(f"   blocked {check(SPR, blocked_off(SPR), True)}", end="" if SPR == 8 else "\n")
+            if SPR == 8:
+                print(f"   | 16x16x32 accesses: XOR swizzle {check16_blocked(SPR, xor_off(SPR))}   blocked {check16_blocked(SPR, blocked_off(SPR))}")
         else:
             print(f"   | 16x16x32 accesses: XOR swizzle {check16(SPR, xor_off(SPR))}   16-block image {check16(SPR, blk16_off(SPR))}"
                   f"   | 32x32x16 accesses on the 16-block image {check(SPR, blk16_off(SPR), False)}")

@@ -62,7 +62,7 @@ struct GTile {
     static constexpr int KS32 = C / 32, KSX32 = XC / 32;  // k = 32 steps per tap: of the convolution / of one X channel chunk
         static constexpr int LA16 = 3, RA16 = LA16 + 1;      // weight look-ahead in k = 32 steps and its register ring
     static_assert(BLK == 32 || BLK == 16, "MFMA block shape");
-    static_assert(BLK == 32 || (XC >= 128 && C / WM == 64 && (N1 / WN) % 64 == 0 && KSX32 % 4 == 0 && 4 % RA16 == 0), "16-block tiles: C >= 128, 64-row wave tiles");
+    static_assert(BLK == 32 || (XC >= 64 && C / WM == 64 && (N1 / WN) % 64 == 0 && (KSX32 % 4 == 0 || (NXC == 1 && 4 % KSX32 == 0)) && 4 % RA16 == 0), "16-block tiles: C >= 64, 64-row wave tiles");
     static constexpr int THREADS = 64 * WM * WN;
     static constexpr int MR = C / WM / 32, NR = N1 / WN / 32;
     static constexpr int H2 = (KS - 1) / 2;             // c2 halo (rate 1); c1's is H2 * rate
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     constexpr int BLK = T::BLK;
     constexpr bool B16 = BLK == 16;
     constexpr int MR16 = T::MR16, NR16 = T::NR16, NH = T::NH;
-    static_assert(!B16 || (!T::RAWRES && !T::TAIL && !T::WREG && !T::UNROLL_ALL), "16-block tiles are the rolled-loop C >= 128 tiles");
+    static_assert(!B16 || (!T::RAWRES && !T::TAIL && !T::WREG && !T::UNROLL_ALL), "16-block tiles are the rolled-loop C >= 64 tiles");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* xt = lds;  // X tile, later the xt tile
@@ -467,12 +467,15 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     // blocks, behind them the 4 ds_read_b128 of the next unit and the unit's share of the 4 weight fragments of the step LA16 steps ahead.
     // A fragment (tap, ks, mblk): 16 bytes per lane at  wconv + (((tap*KS32 + ks0 + ks)*(C/16) + wm*4 + mr)*64 + lane)*16   (pair_g_pack)
     // B fragment (tap, ks, nr):   tile row  n + tap*dl  (n = 16 nr + l15), 16-byte slot 4*ks + lg of that row
+    // C = 64 has two k = 32 steps per tap: a block of UB = 4 steps (one turn of the weight ring) then spans two taps, and the k = 7 / 11 passes
+    // (14 / 22 steps) end in a peeled half block that requests nothing further.
     const int rowbase16 = wn * (N1 / WN) + l15;
     auto conv_phase16 = [&](const unsigned char* __restrict__ wconv, int dl, auto sprb_tag, auto nks_tag, int ks0, auto fresh_tag) {
         constexpr int SPRB = decltype(sprb_tag)::value, PB = SPRB * 16, NKS = decltype(nks_tag)::value;  // NKS: this pass's k = 32 steps per tap
         constexpr bool FRESH = decltype(fresh_tag)::value;
         constexpr int NSTEPS = KS * NKS, LA = T::LA16, RA = T::RA16, UB = 4, APU = MR16 / NH;  // APU: A fragments loaded per unit
-        static_assert(NKS % UB == 0 && UB % RA == 0 && (UB * NH) % 2 == 0, "ring slot / B parity must be compile-time in the block loop");
+        constexpr int REM = NSTEPS % UB;  // steps of the peeled last block
+        static_assert((NKS % UB == 0 || UB % NKS == 0) && UB % RA == 0 && (UB * NH) % 2 == 0, "ring slot / B parity must be compile-time in the block loop");
         const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(wconv), 0, (int)T::CONV_BYTES, 0x00020000);
         const unsigned a_voff = (unsigned)((wm * MR16) * 64 + lane) * 16;
         bf16x8 af[RA][MR16], bf[2][4];
@@ -486,23 +489,29 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         };
         auto tap_terms = [&](int tap, unsigned& tapaddr, unsigned& xs) {
             const int row = rowbase16 + tap * dl;
-            tapaddr = (unsigned)row * PB;
-            xs = (unsigned)(swz_of<SPRB, 16>(row) ^ lg) << 4;  // the same for rows 16 apart
+            if constexpr (SPRB >= 16) {
+                tapaddr = (unsigned)row * PB;
+                xs = (unsigned)(swz_of<SPRB, 16>(row) ^ lg) << 4;  // the same for rows 16 apart
+            } else {  // blocked tile: slot 4*ks + lg is 1024*ks + 256*lg bytes into the row's block; rows 16 apart are one block (16 * PB bytes) apart
+                tapaddr = (unsigned)tile_off<SPRB, BLK>(row, lg);
+                xs = 0;
+            }
         };
         auto load_b = [&](unsigned tapaddr, unsigned xs, int ks, int h, auto par_tag) {
-            const unsigned addr = tapaddr + (xs ^ (unsigned)(ks << 6));
+            const unsigned addr = SPRB >= 16 ? tapaddr + (xs ^ (unsigned)(ks << 6)) : tapaddr + (unsigned)(ks << 10);
 #pragma unroll
             for (int nr = 0; nr < 4; ++nr) bf[decltype(par_tag)::value][nr] = *reinterpret_cast<const bf16x8*>(xt + addr + (4 * h + nr) * 16 * PB);
         };
-        auto pin_unit = [&]() {  // pin_step's rule: an MFMA, then the memory instruction due.  The LDS fragments first: they are due one unit on
+        auto pin_unit = [&](auto nds_tag, auto nvm_tag) {  // pin_step's rule: an MFMA, then the memory instruction due.  The LDS fragments first: they are due one unit on
+            constexpr int NDS = decltype(nds_tag)::value, NVM = decltype(nvm_tag)::value;
             int done = 0;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                const int upto = (i + 1) * (4 + APU) / 16;
+                const int upto = (i + 1) * (NDS + NVM) / 16;
 #pragma unroll
                 for (; done < upto; ++done) {
-                    if (done < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    if (done < NDS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
             }
@@ -516,28 +525,34 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         load_b(ta0, xs0, 0, 0, std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_group_barrier(0x020, MR16 * LA, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        auto block = [&](int s0) {  // UB steps of one tap
-            const int tap = s0 / NKS, ksb = s0 - tap * NKS;
-            unsigned ta, xs, tn, xn;
-            tap_terms(tap, ta, xs);
-            const bool wrap = ksb + UB >= NKS;  // the block's last look-ahead B fragments are the next tap's first
-            const int tapn = tap + 1 < KS ? tap + 1 : KS - 1;
+        auto block = [&](int s0, auto nu_tag) {  // NU steps: UB of one tap or of UB / NKS taps, or the peeled REM (nothing left to request but its own B fragments)
+            constexpr int NU = decltype(nu_tag)::value, NT = NKS >= UB ? 1 : (NU + NKS - 1) / NKS;  // NT: the taps its steps span
+            constexpr bool PEEL = NU < UB;
+            const int tap = s0 / NKS, ksb = s0 - tap * NKS;  // NKS < UB: ksb = 0
+            unsigned ta[NT], xs[NT], tn, xn;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) tap_terms(tap + t, ta[t], xs[t]);
+            const bool wrap = ksb + UB >= NKS;  // the block's last look-ahead B fragments are a later tap's first
+            const int tapn = tap + NT < KS ? tap + NT : KS - 1;
             tap_terms(wrap ? tapn : tap, tn, xn);
             const int ksn = wrap ? 0 : ksb + UB;
-            static_for(std::make_integer_sequence<int, UB * NH>{}, [&](auto v) {
+            static_for(std::make_integer_sequence<int, NU * NH>{}, [&](auto v) {
                 constexpr int u = decltype(v)::value, i = u / NH, h = u % NH;
-                load_a(s0 + i + LA, std::integral_constant<int, h>{}, std::integral_constant<int, (i + LA) % RA>{});
+                constexpr int ti = NKS >= UB ? 0 : i / NKS, ki = i - ti * NKS;          // step i: tap + ti, k-step ksb + ki
+                constexpr int tj = NKS >= UB ? 0 : (i + 1) / NKS, kj = i + 1 - tj * NKS;  // step i + 1
+                constexpr bool last = h + 1 == NH && i + 1 == NU;
+                if constexpr (!PEEL) load_a(s0 + i + LA, std::integral_constant<int, h>{}, std::integral_constant<int, (i + LA) % RA>{});
                 constexpr auto par = std::integral_constant<int, (u + 1) & 1>{};
-                if constexpr (h + 1 < NH) load_b(ta, xs, ksb + i, h + 1, par);
-                else if constexpr (i + 1 < UB) load_b(ta, xs, ksb + i + 1, 0, par);
-                else load_b(tn, xn, ksn, 0, par);
+                if constexpr (h + 1 < NH) load_b(ta[ti], xs[ti], ksb + ki, h + 1, par);
+                else if constexpr (i + 1 < NU) load_b(ta[tj], xs[tj], ksb + kj, 0, par);
+                else if constexpr (!PEEL) load_b(tn, xn, ksn, 0, par);
                 // column block outermost: the unit's last fragment read is first needed 12 MFMAs into the next unit
 #pragma unroll
                 for (int nr = 0; nr < 4; ++nr)
 #pragma unroll
                     for (int mr = 0; mr < MR16; ++mr)
                         acc16[mr][4 * h + nr] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i % RA][mr], bf[u & 1][nr], acc16[mr][4 * h + nr], 0, 0, 0);
-                pin_unit();
+                pin_unit(std::integral_constant<int, PEEL && last ? 0 : 4>{}, std::integral_constant<int, PEEL ? 0 : APU>{});
             });
         };
         // The bias block as the first step's C operand (as in the 32-block loop) needs that step's block peeled, and the peeled copy — ring full, bias
@@ -550,7 +565,8 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                 for (int nr = 0; nr < NR16; ++nr) acc16[mr][nr] = bblk16[mr];
         }
 #pragma nounroll
-        for (int s0 = 0; s0 < NSTEPS; s0 += UB) block(s0);
+        for (int s0 = 0; s0 < NSTEPS - REM; s0 += UB) block(s0, std::integral_constant<int, UB>{});
+        if constexpr (REM != 0) block(NSTEPS - REM, std::integral_constant<int, REM>{});
     };
 
     // ---------------- phase 1: xt = c1(lrelu(x)); column n <-> xt time t0 - H2 + n; tap j reads X row n + j*dil ----------------
@@ -848,15 +864,18 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 #define VTTS_G128K3_WG 2
 #endif
 // MFMA block shape of the pair kernel's loops per (C, KS) class: 16 where the class, measured per launch on one device against the 32-block
-// build, is faster by wall time (profiles/mfma16_pair_findings.md); C <= 64 is not clock-capped and stays on 32.  A class's wide and narrow
-// tiles carry the SAME shape (a batch row must equal the utterance run alone, bit for bit), and so does the packer (pair_g_pack below).
+// build, is faster by wall time by more than three times the 32-block build's spread (profiles/mfma16_pair_findings.md, sections 3 and 5).
+// C = 64, k = 3 runs inside the whole-ResBlock kernel on the default path and C = 32 keeps its weights in registers (another loop): both stay
+// on 32.  A class's wide and narrow tiles carry the SAME shape (a batch row must equal the utterance run alone, bit for bit), and so does the
+// packer (pair_g_pack below).
 constexpr int g_mfma_blk(int C, int KS) {
-    return C == 256 ? (KS == 3 ? 32 : KS == 7 ? 32 : 16)
-         : C == 128 ? (KS == 3 ? 32 : KS == 7 ? 16 : 16)
+    return C == 256 ? (KS == 3 ? 16 : KS == 7 ? 32 : 16)
+         : C == 128 ? (KS == 3 ? 16 : KS == 7 ? 16 : 16)
+         : C == 64  ? (KS == 3 ? 32 : KS == 7 ? 16 : 16)
                     : 32;
 }
 template <int KS> using G128 = GTile<128, KS, KS == 3 ? VTTS_G128K3_N1 : 256, 2, 2, 3, KS == 3 ? VTTS_G128K3_WG : 2, 128, g_mfma_blk(128, KS)>;
-template <int KS> using G64 = GTile<64, KS, VTTS_G64_N1, 1, 4, 3, VTTS_G64_WG>;
+template <int KS> using G64 = GTile<64, KS, VTTS_G64_N1, 1, 4, 3, VTTS_G64_WG, 64, g_mfma_blk(64, KS)>;
 #ifndef VTTS_G32_PA
 #define VTTS_G32_PA 3
 #endif
@@ -867,7 +886,7 @@ template <int KS> using G256 = GTile<256, KS, 128, 4, 1, 3, 2, 128, g_mfma_blk(2
 // accumulation order (the k loop), so the samples are bit-identical to the wide tiles'.
 template <int KS> using G256S = GTile<256, KS, 64, 4, 1, 3, 2, 128, g_mfma_blk(256, KS)>;
 template <int KS> using G128S = GTile<128, KS, 128, 2, 2, 3, 2, 128, g_mfma_blk(128, KS)>;
-template <int KS> using G64S = GTile<64, KS, 256, 1, 4, 3, 2>;
+template <int KS> using G64S = GTile<64, KS, 256, 1, 4, 3, 2, 64, g_mfma_blk(64, KS)>;
 template <int KS> using G32S = GTile<32, KS, 256, 1, 4, 3, 2>;
 constexpr long G_MIN_WGS = 384;  // below this many wide-tile workgroups (1.5 per CU slot pair) the narrow tile is launched
 template <class T>
