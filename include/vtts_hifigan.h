@@ -179,6 +179,26 @@ int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const float* x_de
                           float* y_dev, vtts_stream stream);
 
 /*
+ * Test hook: run ONE ResBlock1 (model.py:44-51: three pairs) named by its first convolution's key (convs1_0) the way the engine launches it,
+ * with the MRF bookkeeping of model.py:115-121 in the last epilogue:  v = rb(x) (+ y);  v = v / div;  y = leaky_relu(v, slope_out).
+ *   route     0 = the whole-ResBlock kernel, whatever "fuse" says (VTTS_BF16: where it exists — C = 32; C = 64 / 128 at k = 3; VTTS_BF16X3: where
+ *                 the split-operand one exists; VTTS_F32 has none), VTTS_ERR_INVALID elsewhere;
+ *             1 = three fused-pair launches as a forward issues them: the first two store into scratch, the third carries
+ *                 slope_out / acc_add / div into y_dev; no stage-4 tail is attached
+ *   rows_dev  NULL, or [B] int32 on the device: utterance b's valid rows of the L allocated (clamped into [0, L] by the kernels, as the frame
+ *             counts of forward_ragged): the rest reads as zero padding and is not written
+ *   acc_add   1 = y_dev's content is added first; div = the MRF divisor (1 = none); slope_out = the consumer's LeakyReLU (1 = none)
+ *   y_dev     in-out
+ * VTTS_BF16: arrays are fp32 channels-last [B, L, C]; x_dev and the initial y_dev are rounded to bf16 into buffers of the hook's own and the
+ * result is converted back (rows no kernel writes come back as the rounded values that went in); slope_out in (0, 1]; the call synchronises.
+ * VTTS_F32 / VTTS_BF16X3: arrays are [B, C, L] channel-major, y_dev is used directly, slope_out must be 1 (these engines' consumers activate on
+ * load) and div != 1 needs acc_add; enqueued on `stream` (route 1 waits for the device when it frees its scratch).
+ * The hook allocates and frees its own scratch; options "tiles", "zigzag" and "kernels" act as in a forward.
+ */
+int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, int route, const float* x_dev, const int32_t* rows_dev, int B, int L,
+                              float slope_out, int acc_add, float div, float* y_dev, vtts_stream stream);
+
+/*
  * Engine options (tests / benchmarks):
  *   "kernels"   0 = auto (MFMA kernels where the shape allows, generic otherwise), 1 = generic only
  *   "microbatch" utterances processed per pass through the network (0 = auto)

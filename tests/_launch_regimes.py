@@ -83,9 +83,14 @@ def x3_pair_tiles(C: int, k: int, L: int) -> int:
     return cdiv(L, X3_PAIR_N1[C][k] - (k - 1))
 
 
-def rb_window_nt(W: int, k: int, dils=(1, 3, 5)) -> int:
+def rb_margin(k: int, dils=(1, 3, 5)) -> int:
+    """M = H (d0 + d1 + d2) + 3 H: the rows per window side whose dependency cone left the window after the three pairs (H = (k - 1) / 2)"""
     h = (k - 1) // 2
-    return W - 2 * (h * sum(dils) + 3 * h)
+    return h * sum(dils) + 3 * h
+
+
+def rb_window_nt(W: int, k: int, dils=(1, 3, 5)) -> int:
+    return W - 2 * rb_margin(k, dils)
 
 
 def length_for_tiles(n: int, nt: int, mult: int = 1) -> int:

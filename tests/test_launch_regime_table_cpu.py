@@ -133,3 +133,17 @@ def test_upsampler_tiles_match_the_sources():
         cin, cout, sh, n1, wm = (_tile_arg(x3, f"UX{i}", j) for j in (0, 1, 2, 3, 4))
         rows16 = -(-(n1 + 2) // 16) * 16
         assert sh == 1 and wm * 32 * (2 * n1 + 4) * 4 <= 2 * rows16 * cin * 2, i
+
+
+def test_whole_resblock_margin_matches_the_sources():
+    """rb_margin / rb_window_nt restate M = H (d0 + d1 + d2) + 3 H and NT = W - 2 M of both whole-ResBlock kernels and of their launchers
+    (tests/_bf16_rb_ref.py computes the window-edge lengths of tests/test_gpu_bf16_resblock.py from them)"""
+    for name in ("kernels_bf16_rbk.hip", "kernels_x3_rb.hip"):
+        src = _src(name)
+        assert len(re.findall(r"const int M = H \* \(d0 \+ d1 \+ d2\) \+ 3 \* H;", src)) == 1, name
+        assert len(re.findall(r"const int NT = W - 2 \* M;", src)) == 1, name
+        assert len(re.findall(r"const int NT = T::W - 2 \* \(T::H \* dsum \+ 3 \* T::H\);", src)) == 1, name
+        assert re.search(r"static constexpr int H = \(KS - 1\) / 2[;,]", src), name
+    assert [R.rb_margin(k) for k in (3, 7, 11)] == [12, 36, 60]
+    assert R.rb_window_nt(256, 3) == 232 and R.rb_window_nt(512, 7) == 440 and R.rb_window_nt(512, 11) == 392 and R.rb_window_nt(128, 3) == 104
+    assert R.rb_margin(7, (1, 2, 4)) == 3 * 7 + 9 and R.rb_window_nt(512, 7, (1, 2, 4)) == 512 - 60

@@ -126,6 +126,7 @@ SIGS = {
     "vtts_hifigan_forward_tap": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, sz, vp, cp, vp]),
     "vtts_hifigan_run_module": (C.c_int, [vp, cp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
     "vtts_hifigan_run_pair": (C.c_int, [vp, cp, vp, C.c_int, C.c_int, vp, vp]),
+    "vtts_hifigan_run_resblock": (C.c_int, [vp, cp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp, vp]),
     "vtts_hifigan_set_option": (C.c_int, [vp, cp, i64]),
     "vtts_hifigan_get_option": (C.c_int, [vp, cp, C.POINTER(i64)]),
     "vtts_hifigan_profile_read": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double), C.c_int]),

@@ -507,14 +507,19 @@ bool pair_x3_wanted(const vtts_hifigan* h, const Layer& c1, const Layer& c2, int
            pair_x3_supported(c1.cin, c1.k, c1.dil, L);
 }
 
-// VTTS_BF16X3: a whole ResBlock1 (three pairs + the MRF bookkeeping) in one launch where the kernel exists and is the faster choice
-// (kernels_x3_rb.hip; fuse = 2: C = 32 and C = 64, k = 3; fuse = 3: wherever it exists); bit-identical to the three pair launches
-bool resblock_x3_wanted(const vtts_hifigan* h, const Layer* rb, int L) {
-    if (!h->x3 || h->opt_kernels != 0 || h->opt_fuse < 2) return false;
+// VTTS_BF16X3: where the whole-ResBlock kernel (kernels_x3_rb.hip) can run at all (vtts_hifigan_run_resblock takes it there whatever "fuse" says)
+bool resblock_x3_runnable(const vtts_hifigan* h, const Layer* rb, int L) {
+    if (!h->x3 || h->opt_kernels != 0) return false;
     for (int q = 0; q < 6; ++q)
         if (!rb[q].has_x3 || rb[q].cin != rb[0].cin || rb[q].cout != rb[0].cin || rb[q].k != rb[0].k || ((q & 1) && rb[q].dil != 1)) return false;
     const int dils[3] = {rb[0].dil, rb[2].dil, rb[4].dil};
-    if (!resblock_x3_supported(rb[0].cin, rb[0].k, dils, L)) return false;
+    return resblock_x3_supported(rb[0].cin, rb[0].k, dils, L);
+}
+
+// VTTS_BF16X3: a whole ResBlock1 (three pairs + the MRF bookkeeping) in one launch where the kernel exists and is the faster choice
+// (kernels_x3_rb.hip; fuse = 2: C = 32 and C = 64, k = 3; fuse = 3: wherever it exists); bit-identical to the three pair launches
+bool resblock_x3_wanted(const vtts_hifigan* h, const Layer* rb, int L) {
+    if (h->opt_fuse < 2 || !resblock_x3_runnable(h, rb, L)) return false;
     return h->opt_fuse >= 3 || resblock_x3_preferred(rb[0].cin, rb[0].k);
 }
 
@@ -1534,6 +1539,94 @@ VTTS_API int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const fl
     if (!rc && launch_bf16_to_f32(yb, y_dev, n, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
     hipError_t e = hipStreamSynchronize(st);
     if (!rc && e != hipSuccess) rc = failf(VTTS_ERR_HIP, "run_pair failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+// the ragged state of a test hook's launches (set_ragged reads it): rows_dev as a.lens with len_mul = 1; cleared on every return path
+struct RowsScope {
+    vtts_hifigan* h;
+    RowsScope(vtts_hifigan* h_, const int32_t* rows_dev, int L) : h(h_) {
+        h->cur_lens = rows_dev;
+        h->cur_T = rows_dev ? L : 0;
+        h->cur_b0 = 0;
+    }
+    ~RowsScope() {
+        h->cur_lens = nullptr;
+        h->cur_T = 0;
+        h->cur_b0 = 0;
+    }
+};
+
+VTTS_API int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, int route, const float* x_dev, const int32_t* rows_dev, int B, int L,
+                                       float slope_out, int acc_add, float div, float* y_dev, vtts_stream stream) {
+    if (!h || !key_c1_0 || !x_dev || !y_dev) return failf(VTTS_ERR_INVALID, "null argument");
+    if (!h->blob) return failf(VTTS_ERR_STATE, "run_resblock() before pack()/bind_packed()");
+    if (B <= 0 || L <= 0) return failf(VTTS_ERR_INVALID, "B and L must be positive");
+    if (B > 65535) return failf(VTTS_ERR_INVALID, "at most 65535 utterances per launch (got %d)", B);
+    if (route != 0 && route != 1) return failf(VTTS_ERR_INVALID, "route must be 0 (the whole-ResBlock kernel) or 1 (three pair launches), got %d", route);
+    if ((acc_add != 0 && acc_add != 1) || !(div > 0.0f) || !std::isfinite(div))
+        return failf(VTTS_ERR_INVALID, "run_resblock(): acc_add must be 0 or 1 and div a positive number (got %d, %g)", acc_add, div);
+    const Layer* rb = nullptr;  // rb[0..5] = c1_0, c2_0, c1_1, c2_1, c1_2, c2_2
+    for (size_t r = 0; r < h->idx_res.size() && h->cfg.resblock != 2; ++r)
+        if (h->layers[h->idx_res[r]].key == key_c1_0) rb = &h->layers[h->idx_res[r]];
+    if (!rb) return failf(VTTS_ERR_INVALID, "'%s' is not the first convolution (convs1_0) of a ResBlock1", key_c1_0);
+    const int C = rb[0].cin;
+    if ((size_t)L * C * elem_bytes(h) >= ((size_t)1 << 31))
+        return failf(VTTS_ERR_INVALID, "L=%d rows of %d channels are too long for one launch (limit 2^31 bytes per utterance)", L, C);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)B * L * C;
+    RowsScope rows(h, rows_dev, L);
+    if (h->dtype == VTTS_F32) {
+        // fp32 / bf16x3 handle: x_dev / y_dev are [B, C, L] channel-major, y_dev is the launch's own in-out tensor.  These engines' epilogues
+        // have no output activation (the consumer applies it on load)
+        if (slope_out != 1.0f) return failf(VTTS_ERR_INVALID, "run_resblock(): slope_out must be 1 on an fp32 / bf16x3 handle (got %g)", slope_out);
+        if (!acc_add && div != 1.0f) return failf(VTTS_ERR_INVALID, "run_resblock(): div without acc_add is not an accumulate mode of the fp32 engine");
+        const int mode = !acc_add ? ACC_STORE : (div != 1.0f ? ACC_MEAN : ACC_ADD);
+        if (route == 0) {
+            if (!resblock_x3_runnable(h, rb, L))
+                return failf(VTTS_ERR_INVALID, "'%s': no whole-ResBlock kernel for this ResBlock on this handle (bf16x3, C = 32 / 64 / 128)", key_c1_0);
+            return run_resblock_x3(h, rb, x_dev, B, L, y_dev, mode, div, st);
+        }
+        bool x3 = h->x3 && h->opt_kernels == 0, fp = h->opt_kernels == 0;  // the split-operand pair kernel, else the fp32 one, as route_f32 picks them
+        for (int z = 0; z < 3; ++z) {
+            const Layer &c1 = rb[2 * z], &c2 = rb[2 * z + 1];
+            x3 = x3 && c1.has_x3 && c2.has_x3 && c2.k == c1.k && c2.dil == 1 && c2.cin == c1.cin && pair_x3_supported(c1.cin, c1.k, c1.dil, L);
+            fp = fp && pair_f32_fusable(c1, c2, L);
+        }
+        if (!x3 && !fp) return failf(VTTS_ERR_INVALID, "'%s': the fused pair kernels do not cover this ResBlock at L=%d", key_c1_0, L);
+        DevBuf tbuf, cbuf;  // X -> T -> C -> y, as mrf_f32; released (hipFree waits for the device) on every path
+        HIP_TRY(hipMalloc(&tbuf.p, n * sizeof(float)));
+        HIP_TRY(hipMalloc(&cbuf.p, n * sizeof(float)));
+        float *tT = static_cast<float*>(tbuf.p), *tC = static_cast<float*>(cbuf.p);
+        int rc;
+        if ((rc = run_pair_f32(h, rb[0], rb[1], x3, x_dev, B, L, tT, ACC_STORE, 1.f, st))) return rc;
+        if ((rc = run_pair_f32(h, rb[2], rb[3], x3, tT, B, L, tC, ACC_STORE, 1.f, st))) return rc;
+        return run_pair_f32(h, rb[4], rb[5], x3, tC, B, L, y_dev, mode, div, st);
+    }
+    // bf16 handle: fp32 channels-last [B, L, C] in and out through bf16 buffers of the hook's own; synchronises (as run_pair)
+    if (!(slope_out > 0.0f && slope_out <= 1.0f)) return failf(VTTS_ERR_INVALID, "run_resblock(): slope_out must lie in (0, 1] on a bf16 handle (got %g)", slope_out);
+    if (route == 0 && !rb[0].has_rb) return failf(VTTS_ERR_INVALID, "'%s': no whole-ResBlock kernel for this ResBlock (C = 32; C = 64 / 128 at k = 3)", key_c1_0);
+    if (route == 1 && !(rb[0].has_pair && rb[2].has_pair && rb[4].has_pair))
+        return failf(VTTS_ERR_INVALID, "'%s': the fused pair kernel does not cover this ResBlock", key_c1_0);
+    DevBuf xbuf, ybuf, tbuf, cbuf;
+    HIP_TRY(hipMalloc(&xbuf.p, n * 2));
+    HIP_TRY(hipMalloc(&ybuf.p, n * 2));
+    if (route == 1) {
+        HIP_TRY(hipMalloc(&tbuf.p, n * 2));
+        HIP_TRY(hipMalloc(&cbuf.p, n * 2));
+    }
+    int rc = VTTS_OK;
+    if (launch_f32_to_bf16(x_dev, xbuf.p, n, st) != hipSuccess || launch_f32_to_bf16(y_dev, ybuf.p, n, st) != hipSuccess)
+        rc = failf(VTTS_ERR_HIP, "conversion launch failed");
+    if (!rc && route == 0) rc = run_resblock_bf16(h, rb, xbuf.p, B, L, slope_out, ybuf.p, acc_add, div, st);
+    if (!rc && route == 1) {  // X -> T -> C -> y, as mrf_bf16 (no tail)
+        rc = run_pair_bf16(h, rb[0], xbuf.p, B, L, 1.0f, tbuf.p, 0, 1.f, st);
+        if (!rc) rc = run_pair_bf16(h, rb[2], tbuf.p, B, L, 1.0f, cbuf.p, 0, 1.f, st);
+        if (!rc) rc = run_pair_bf16(h, rb[4], cbuf.p, B, L, slope_out, ybuf.p, acc_add, div, st);
+    }
+    if (!rc && launch_bf16_to_f32(ybuf.p, y_dev, n, st) != hipSuccess) rc = failf(VTTS_ERR_HIP, "conversion launch failed");
+    hipError_t e = hipStreamSynchronize(st);
+    if (!rc && e != hipSuccess) rc = failf(VTTS_ERR_HIP, "run_resblock failed: %s", hipGetErrorString(e));
     return rc;
 }
 

@@ -174,6 +174,29 @@ class Generator(NativeHandle):
         self._on_stream("run_pair", key_c1.encode(), ptr(x), B, L, ptr(y))
         return y
 
+    def run_resblock(self, key_c1_0: str, x: torch.Tensor, route: int = 0, rows=None, slope_out: float = 1.0, acc_add: bool = False,
+                     div: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One ResBlock1 named by its ``convs1_0`` key, launched as the engine launches it (test hook): ``route`` 0 = the whole-ResBlock
+        kernel, 1 = three fused-pair launches; then ``v = rb(x) (+ out)``, ``v / div``, ``leaky_relu(v, slope_out)``.
+        bf16 handles: ``x`` fp32 ``[B, L, C]`` channels-last (``x`` and ``out`` rounded to bf16 on the way in); fp32 / bf16x3 handles:
+        ``[B, C, L]``, ``slope_out`` must be 1.  ``rows``: per-utterance valid row counts (int sequence or int32 device tensor) or None.
+        ``out`` is in-out (checked as in ``__call__``): rows no kernel writes keep what went in; ``acc_add`` needs it."""
+        x = x.contiguous()
+        if self.dtype_name == "bf16":
+            B, L, _ = x.shape
+        else:
+            B, _, L = x.shape
+        if acc_add and out is None:
+            raise ValueError("acc_add needs the accumulator in `out`")
+        y = self._check_out(out, tuple(x.shape), "[" + ", ".join(str(d) for d in x.shape) + "]")
+        if rows is not None:
+            rows = torch.as_tensor(rows).to(device=self.device, dtype=torch.int32).contiguous()
+            if rows.numel() != B:
+                raise ValueError("rows must hold one count per utterance")
+        self._on_stream("run_resblock", key_c1_0.encode(), int(route), ptr(x), ptr(rows), B, L, C.c_float(slope_out), int(bool(acc_add)),
+                        C.c_float(div), ptr(y))
+        return y
+
     # ---- dominant-kernel timing (bench.py roofline) ----------------------------------------------
     def profile_read(self, reset: bool = True):
         ms, n, fl = C.c_double(0), C.c_int64(0), C.c_double(0)
