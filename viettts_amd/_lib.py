@@ -48,9 +48,16 @@ VTTS_MEL_PCM16 = 1
 MEL_FRAMES_PER_BLOCK = 8  # include/vtts_mel.h: VTTS_MEL_FRAMES_PER_BLOCK
 MEL_MIN_SAMPLES = 385  # include/vtts_mel.h: VTTS_MEL_MIN_SAMPLES
 
+DTW_MAX_FEAT = 128  # include/vtts_dtw.h: VTTS_DTW_MAX_FEAT
+DTW_MAX_FRAMES = 4096  # include/vtts_dtw.h: VTTS_DTW_MAX_FRAMES
+
 
 class MelCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
+
+
+class DtwCfg(C.Structure):
+    _fields_ = [("n_feat", C.c_int32), ("band", C.c_int32), ("max_frames", C.c_int32)]
 
 
 class AudioCfg(C.Structure):
@@ -183,6 +190,15 @@ SIGS = {
 }
 
 
+# include/vtts_dtw.h, a table of its own: SIGS stays the list of the five headers above (tests/test_handle_cpu.py checks it against their *_EXPORTS).
+DTW_SIGS = {
+    "vtts_dtw_create": (C.c_int, [C.POINTER(DtwCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_dtw_destroy": (None, [vp]),
+    "vtts_dtw_workspace_bytes": (C.c_int, [vp, C.c_int, i64, i64, C.POINTER(sz)]),
+    "vtts_dtw_forward": (C.c_int, [vp, vp, vp, C.c_int, i64, i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp, sz, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -192,6 +208,7 @@ NAT_EXPORTS = _exports("vtts_nat_")  # include/vtts_nat.h
 MEL_EXPORTS = _exports("vtts_mel_")  # include/vtts_mel.h
 DISC_EXPORTS = _exports("vtts_disc_")  # include/vtts_disc.h
 AUDIO_EXPORTS = _exports("vtts_audio_")  # include/vtts_audio.h
+DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
 
 
 def default_lib_path() -> Path:
@@ -245,7 +262,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in SIGS.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
