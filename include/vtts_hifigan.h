@@ -224,6 +224,10 @@ int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, int route, 
  *   "tail"      VTTS_BF16: 1 (default) = the generator's last pair launch (stage 4, C = 32, k = 11) also runs conv_post + tanh on the rows it
  *               produces — the stage output is never written and the streaming conv_post kernel is not launched; bit-identical samples;
  *               0 = the separate kernel.  (forward_tap always takes the separate kernel: a tap wants the stage output.)
+ *   "upfuse"    VTTS_BF16: a bit mask, default 3.  Bit 0 = the pair launch that ends the C = 128 stage (k = 11) also runs the next stage's
+ *               transposed convolution ups_2 (128 -> 2 x 64) on the rows it produces, bit 1 = the same at C = 64 with ups_3 (64 -> 2 x 32): the
+ *               stage output is neither written nor read back and the upsampler is not launched; bit-identical samples
+ *               (profiles/upfuse_findings.md).  A forward_tap of that stage's output ("mrf_1" / "mrf_2") takes the separate launches.
  *   "stage"     0 only (kept so that callers which set it keep working): the whole-stage kernel it once selected was removed after it measured
  *               30 % slower than the launches it replaces (profiles/r06_a_stage_kernel_findings.md); any other value is VTTS_ERR_INVALID.
  *   "tiles"     MFMA time-tile width: 0 = by problem size, 1 = wide, 2 = narrow

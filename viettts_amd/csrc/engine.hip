@@ -110,6 +110,7 @@ struct vtts_hifigan {
     int64_t opt_zigzag = 1;          // consecutive launches walk the batch in alternating directions (see next_zrev)
     unsigned zrev_count = 0;
     int64_t opt_tail = 1;            // bf16: conv_post + tanh inside the generator's last pair launch (0 = the separate streaming kernel)
+    int64_t opt_upfuse = 3;          // bf16: bit 0 / 1 = ups_2 / ups_3 inside the pair launch that ends the stage before it (up_fused_bf16)
     int64_t opt_chains = 1;          // small launches: the MRF's ResBlocks of a stage on parallel streams (0 = one after the other, 2 = always)
     hipEvent_t ev_chain[3] = {nullptr, nullptr, nullptr};  // bf16: ResBlock j's output is in the shared accumulator (orders the accumulating epilogues)
     hipStream_t side_streams[3] = {nullptr, nullptr, nullptr};
@@ -618,8 +619,13 @@ BConvArgs resblock_args_bf16(vtts_hifigan* h, const Layer& c1, const void* x, in
 }
 
 int run_pair_bf16(vtts_hifigan* h, const Layer& c1, const void* x, int B, int L, float slope_out, void* y, int acc_add, float div,
-                  hipStream_t s, float* tail_wav = nullptr) {
+                  hipStream_t s, float* tail_wav = nullptr, const Layer* up = nullptr, void* up_y = nullptr) {
     BConvArgs a = resblock_args_bf16(h, c1, x, B, L, slope_out, y, acc_add, div);
+    if (up) {  // the next stage's transposed convolution rides on this launch (kernels_bf16_rbg.hip: GUp): y is only read (the MRF accumulator), z = up(.) -> up_y
+        a.up_wp = h->blob + up->off_ug;
+        a.up_bias = reinterpret_cast<const float*>(h->blob + up->off_b);
+        a.up_y = up_y;
+    }
     a.wp = h->blob + c1.off_pw;
     a.bias = reinterpret_cast<const float*>(h->blob + c1.off_pb);
     a.dil = c1.dil;
@@ -631,7 +637,8 @@ int run_pair_bf16(vtts_hifigan* h, const Layer& c1, const void* x, int B, int L,
         a.tail_wf = reinterpret_cast<const float*>(h->blob + post.off_w);
         a.tail_bias = reinterpret_cast<const float*>(h->blob + post.off_b);
     }
-    return launch_timed(h, c1, 2, B, L, s, "fused pair launch", [&] { return launch_pair_g_bf16(c1.cin, c1.k, a, s); });
+    // (a launch that carries an upsampler is another kernel with other work: it is not timed as one of the dominant class's pair launches)
+    return launch_timed(h, c1, up ? 0 : 2, B, L, s, "fused pair launch", [&] { return launch_pair_g_bf16(c1.cin, c1.k, a, s); });
 }
 
 int run_resblock_bf16(vtts_hifigan* h, const Layer* rb, const void* x, int B, int L, float slope_out, void* y, int acc_add, float div,
@@ -660,6 +667,19 @@ bool tail_fused_bf16(const vtts_hifigan* h) {
     const Layer* rb = &h->layers[h->idx_res.back()];
     const Layer& post = h->layers[h->idx_post];
     return route_bf16(h, rb) == ROUTE_PAIRS && pair_tail_bf16_supported(rb[0].cin, rb[0].k, post.cin, post.cout, post.k);
+}
+
+// Option "upfuse" (bit 0: ups_2, bit 1: ups_3): the pair launch that ends stage i also runs ups_{i+1} on the rows its epilogue forms, writes the next
+// stage's X and never writes stage i's output; upsample_bf16 is then skipped for stage i + 1.  Where the stage's last ResBlock runs as pairs and its
+// last pair can carry that layer (V1: C = 128 / 64, k = 11, a stride-2 k = 4 transposed convolution to C / 2 channels on the register-streamed
+// packing); the caller also requires that no tap needs stage i's output itself.  Otherwise the un-fused path runs, as with tail_fused_bf16.
+bool up_fused_bf16(const vtts_hifigan* h, int i) {
+    if (i < 1 || i > 2 || i + 1 >= h->cfg.num_upsamples || !((h->opt_upfuse >> (i - 1)) & 1) || h->cfg.resblock != 1 || h->opt_fuse < 1) return false;
+    const int nk = h->cfg.num_kernels;
+    const Layer* rb = &h->layers[h->idx_res[i * nk + nk - 1]];
+    const Layer& up = h->layers[h->idx_ups[i + 1]];
+    return route_bf16(h, rb) == ROUTE_PAIRS && up.has_ug &&
+           pair_up_bf16_supported(rb[0].cin, rb[0].k, up.bcls, up.cin, up.cout, up.k, up.stride);
 }
 
 // ---- the pass plan: micro-batches, streams, workspace -------------------------------------------------------
@@ -838,6 +858,7 @@ struct MicroBatch {
     bool par;    // the MRF's ResBlocks as parallel chains
     float* wav;  // this micro-batch's waveform [nb][hop * T]
     bool tail;   // bf16: conv_post + tanh ride on the last pair launch (tail_fused_bf16)
+    unsigned upfuse;  // bf16: bit i = ups_{i+1} rides on the pair launch that ends stage i (up_fused_bf16)
 };
 
 // tap copies: the engine's activation (bf16 channels-last or fp32 channel-major, its own layout) into the caller's fp32 tensor
@@ -985,6 +1006,11 @@ int mrf_bf16(vtts_hifigan* h, const MicroBatch& m, int i, int L) {
                 if ((rc = run_pair_bf16(h, rb[0], cur, m.nb, L, 1.0f, tT, 0, 1.f, cs))) return rc;
                 if ((rc = run_pair_bf16(h, rb[2], tT, m.nb, L, 1.0f, tC, 0, 1.f, cs))) return rc;
                 if ((rc = before_last())) return rc;
+                // upfuse: z = ups_{i+1}(.) goes into X, which every chain's first pair has finished reading by now: this chain's ran earlier on this
+                // stream, and in the parallel schedule before_last() has just made this launch wait for the previous chain's LAST kernel (and that one
+                // for the chain before it), each of which follows its own chain's first pair in stream order
+                if (last_rb && ((m.upfuse >> i) & 1))
+                    return run_pair_bf16(h, rb[4], tC, m.nb, L, slope, m.buf.S, acc, div, cs, nullptr, &h->layers[h->idx_ups[i + 1]], m.buf.X);
                 return run_pair_bf16(h, rb[4], tC, m.nb, L, slope, m.buf.S, acc, div, cs, last_stage && last_rb && m.tail ? m.wav : nullptr);
             default:
                 for (int z = 0; z < 2; ++z) {
@@ -1054,7 +1080,8 @@ int run_micro_batch(vtts_hifigan* h, const Engine& e, const MicroBatch& m, const
     long L = T;
     for (int i = 0; i < c.num_upsamples; ++i) {
         const Layer& up = h->layers[h->idx_ups[i]];
-        if ((rc = e.upsample(h, m, i, (int)L))) return rc;
+        const bool up_done = i > 0 && ((m.upfuse >> (i - 1)) & 1);  // X already holds ups_i's output: it ran inside stage i - 1's last pair launch
+        if (!up_done && (rc = e.upsample(h, m, i, (int)L))) return rc;
         L *= up.stride;
         const size_t CL = (size_t)up.cout * L;
         if (tap.is("ups_", i) && (rc = tap_copy(h, m, m.buf.X, tap.out + (size_t)m.b0 * CL, (size_t)m.nb * CL))) return rc;
@@ -1079,11 +1106,14 @@ int forward_impl(vtts_hifigan* h, const float* mel, int B, int T, float* wav, vo
     }
     const Engine& e = h->dtype == VTTS_BF16 ? ENGINE_BF16 : ENGINE_F32;
     const bool tail = h->dtype == VTTS_BF16 && !tap.name && tail_fused_bf16(h);
+    unsigned upfuse = 0;
+    for (int i = 1; h->dtype == VTTS_BF16 && i + 1 < h->cfg.num_upsamples; ++i)
+        if (up_fused_bf16(h, i) && !tap.is("mrf_", i)) upfuse |= 1u << i;
     hipStream_t streams[4];
     int rc = fork_streams(h, p.nstr, s0, streams);
     for (int b0 = 0; b0 < B && !rc; b0 += p.mb) {
         const int si = (b0 / p.mb) % p.nstr;
-        const MicroBatch m{b0, std::min(p.mb, B - b0), streams[si], p.buffers(ws, si, h->cfg.num_kernels), p.par, wav + (size_t)b0 * h->hop * T, tail};
+        const MicroBatch m{b0, std::min(p.mb, B - b0), streams[si], p.buffers(ws, si, h->cfg.num_kernels), p.par, wav + (size_t)b0 * h->hop * T, tail, upfuse};
         h->cur_b0 = b0;
         rc = run_micro_batch(h, e, m, mel, T, tap);
     }
@@ -1633,7 +1663,7 @@ VTTS_API int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, in
 VTTS_API int vtts_hifigan_set_option(vtts_hifigan* h, const char* name, int64_t value) {
     if (!h || !name) return failf(VTTS_ERR_INVALID, "null argument");
     {  // setting a WRITABLE option to the value it has changes nothing: captured graphs stay valid (read-only and unknown names fall through to their errors)
-        static const char* const writable[] = {"kernels", "microbatch", "fuse", "streams", "graph", "zigzag", "chains", "tiles", "tail", "stage"};
+        static const char* const writable[] = {"kernels", "microbatch", "fuse", "streams", "graph", "zigzag", "chains", "tiles", "tail", "upfuse", "stage"};
         for (const char* w : writable) {
             int64_t cur = 0;
             if (!strcmp(name, w) && vtts_hifigan_get_option(h, name, &cur) == VTTS_OK && cur == value) return VTTS_OK;
@@ -1667,6 +1697,9 @@ VTTS_API int vtts_hifigan_set_option(vtts_hifigan* h, const char* name, int64_t 
     } else if (!strcmp(name, "tail")) {
         if (value != 0 && value != 1) return failf(VTTS_ERR_INVALID, "tail must be 0 or 1");
         h->opt_tail = value;
+    } else if (!strcmp(name, "upfuse")) {
+        if (value < 0 || value > 3) return failf(VTTS_ERR_INVALID, "upfuse must be 0..3 (bit 0: ups_2, bit 1: ups_3 inside the pair launch that ends the stage before it)");
+        h->opt_upfuse = value;
     } else if (!strcmp(name, "stage")) {  // kept for callers that still set it: 0 is the only path there is
         if (value != 0) return failf(VTTS_ERR_INVALID, "stage must be 0: the whole-stage kernel was removed (it measured slower, profiles/r06_a_stage_kernel_findings.md)");
     } else if (!strcmp(name, "profile")) {
@@ -1691,6 +1724,7 @@ VTTS_API int vtts_hifigan_get_option(const vtts_hifigan* h, const char* name, in
     else if (!strcmp(name, "chains")) *value = h->opt_chains;
     else if (!strcmp(name, "graph")) *value = h->opt_graph;
     else if (!strcmp(name, "tail")) *value = h->opt_tail;
+    else if (!strcmp(name, "upfuse")) *value = h->opt_upfuse;
     else if (!strcmp(name, "stage")) *value = 0;
     else if (!strcmp(name, "graphs_cached")) {
         *value = 0;

@@ -100,6 +100,9 @@ struct GTile {
     static constexpr bool TAIL = false;
     static constexpr int TAIL_KS = 7, TAIL_H = 3;
     static constexpr int TAIL_BYTES = 0;
+    // UP (GUp below): the next stage's transposed convolution run by this kernel on its own output rows (the pair launch that ends stage 2 / stage 3)
+    static constexpr bool UP = false;
+    static constexpr int OH = 0;  // output halo: rows per side of the tile's own output that only the fused consumer (TAIL, UP) reads
     static int lds_bytes(int dil) { return tile_bytes(dil) + RAW_BYTES; }
     static_assert(tile_rows16(ROWSX_MAX) * P1 + RAW_BYTES <= 80 * 1024 || !RAWRES, "two workgroups per CU");
     static_assert(tile_rows16(ROWSX_MAX) * P1 <= 160 * 1024 && tile_rows16(ROWST) * P2 <= 160 * 1024, "LDS budget");
@@ -116,9 +119,36 @@ template <class B>
 struct GTail : B {
     static constexpr bool TAIL = true;
     static constexpr int TAIL_BYTES = 1024;  // conv_post's 7 x 32 fp32 weights behind the residual region
+    static constexpr int OH = B::TAIL_H;
     static int lds_bytes(int dil) { return B::tile_bytes(dil) + B::RAW_BYTES + TAIL_BYTES; }
     static_assert(B::RAWRES && B::C == 32 && B::WM == 1, "the tail lives on the C = 32 tile with the LDS-resident residual rows");
     static_assert(B::tile_bytes(B::MAXDIL) + B::RAW_BYTES + TAIL_BYTES <= 80 * 1024, "two workgroups per CU");
+};
+
+// The stage-ending upsampler (option "upfuse"): the LAST pair launch of stage 2 / stage 3 — whose epilogue 2 holds the finished stage output (MRF mean,
+// the consumer's LeakyReLU, bf16) in registers — keeps those rows in LDS (the xt tile is dead once every wave has left phase 2) and runs the next
+// stage's transposed convolution on them (ups_2: 128 -> 2 x 64, ups_3: 64 -> 2 x 32; stride 2, k = 4, model.py:112-114): the stage output (1.07 GB at
+// 64 x 1024 frames) is neither written nor read back, convt_g_bf16_k is not launched.  The launch stores z = [L][2 * C/2] = the next stage's [2 L][C / 2],
+// as many bytes as the y it no longer stores.  A tile then yields NT2 - 2 frames: the neighbours q - 1 and q + 1 the polyphase form reads come out of
+// the tile's own rows (tile 0 starts at time -1; rows outside the utterance are the transposed convolution's zero padding).
+// The GEMM is convt_g_bf16_k's (kernels_bf16_up.hip), element for element: rows of phase 0 (chunk 0) read frames (q - 1, q), those of phase 1
+// (q, q + 1); per chunk two taps ascending x C / 16 k-steps ascending of v_mfma_f32_32x32x16_bf16 — whatever block shape the pair's own loops use —
+// the bias block as the first MFMA's C operand, the weights from the upsampler's own packing (convt_g_pack_geom), no activation on the way out.  An
+// output element's chain does not depend on which wave or tile computes it, so z is bit-identical to the separate launch's
+// (tests/test_gpu_bf16_upfuse.py).  Here all four waves lie along the frames and each runs every row of a chunk.
+template <class B>
+struct GUp : B {
+    static constexpr bool UP = true;
+    static constexpr int OH = 1;
+    static constexpr int UWN = B::WM * B::WN;       // waves along the frames
+    static constexpr int UNR = B::N1 / UWN / 32;    // a wave's 32-frame column blocks
+    static constexpr int UMR = B::C / 2 / 32;       // a chunk = one phase = C / 2 rows: its 32-row blocks
+    static constexpr int UKS = B::C / 16;           // k-steps per tap
+    static constexpr int UP_BYTES = 3 * B::C * B::C * 2;  // the 3-tap polyphase form's packed weights
+    static_assert(B::BLK == 16 && !B::RAWRES && !B::TAIL && B::NXC == 1 && (B::C == 128 || B::C == 64), "the stage-ending k = 11 classes (both run 16-blocks)");
+    static_assert(B::N1 % (UWN * 32) == 0 && UMR >= 1 && UKS % 2 == 0, "whole 32 x 32 blocks");
+    static_assert(B::N1 + 2 <= B::ROWST, "frames t0 - 1 .. t0 + N1 fit the xt tile");
+    static_assert(B::tile_bytes(B::MAXDIL) <= 80 * 1024, "two workgroups per CU");
 };
 
 template <class T>
@@ -157,13 +187,13 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     // Only launches whose utterance slots hold at least XCD_MAP_MIN_TILES tiles do this (the launcher pads gridDim.x for exactly those):
     // with a few tiles per eighth the saving is small, and a padded grid sends tile t of EVERY utterance to XCD t % 8, which on the
     // 256-sentence pipeline (15-140 tiles per utterance and stage) left the last XCDs a tile short per utterance: 2-4 % slower.
-    constexpr int TS = T::TAIL ? NT2 - 2 * T::TAIL_H : NT2;  // tile stride (TAIL: conv_post's halo comes out of the tile's own rows)
+    constexpr int OH = T::OH, TS = NT2 - 2 * OH;  // tile stride (TAIL / UP: the fused consumer's halo comes out of the tile's own rows)
     const bool xmap = (a.L + TS - 1) / TS >= XCD_MAP_MIN_TILES;
     const int nt = (L + TS - 1) / TS, r = (int)((blockIdx.x + b) & 7), lo = (r * nt) >> 3, hi = ((r + 1) * nt) >> 3;
     const int tile = xmap ? lo + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (xmap && tile >= hi) return;
-    const int t0 = tile * TS - (T::TAIL ? T::TAIL_H : 0);   // first output time step (row 0 of c2's output) of this workgroup
-    if (t0 + (T::TAIL ? T::TAIL_H : 0) >= L) return;        // a tile past this utterance's end: nothing reads its rows
+    const int t0 = tile * TS - OH;   // first output time step (row 0 of c2's output) of this workgroup
+    if (t0 + OH >= L) return;        // a tile past this utterance's end: nothing reads its rows
     const int dil = a.dil;
     const int h1 = H2 * dil;                 // c1's symmetric pad (model.py:8-10)
     const int rowsx = N1 + 2 * h1;           // X rows: times t0 - H2 - h1 ... t0 - H2 - h1 + rowsx - 1
@@ -750,6 +780,10 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         }
         if (a.acc_add != 0) add_rows(yg);                                   // xs += rb(x)       (model.py:118-120)
         VTTS_TL(a, wg_lin, 12);
+        if constexpr (T::UP) {
+            __syncthreads();  // every wave is done reading the xt tile: it becomes the fused upsampler's input tile
+            VTTS_TL(a, wg_lin, 5);
+        }
         if constexpr (B16) {
 #pragma unroll
             for (int mr = 0; mr < MR16; ++mr) {
@@ -758,7 +792,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                 for (int j = 0; j < NR16 / 2; ++j) {
                     const int row = col16 + 32 * j;
                     const int t = t0 + row;
-                    const bool ok = row < NT2 && t >= 0 && t < L;
+                    const bool ok = (T::UP || row < NT2) && t >= 0 && t < L;
                     float v[8];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -777,7 +811,15 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                     unsigned q0 = pack_bf16x2(v[4], v[5]), q1 = pack_bf16x2(v[6], v[7]);
                     swap_pair16(p0, q0);
                     swap_pair16(p1, q1);
-                    if (ok) *reinterpret_cast<uint4*>(yg + (size_t)t * C + cb + 8 * (lg >> 1)) = make_uint4(p0, p1, q0, q1);
+                    if constexpr (T::UP) {
+                        // the row stays in LDS: tile row n = time t0 + n = frame q - 1 of the tile's n-th output frame, [frame][C] in the 32-block image
+                        // (the image convt_g_bf16_k reads); rows outside the utterance are the transposed convolution's zero padding.  Rows from NT2 on
+                        // are only read by the discarded frames.
+                        const uint4 o = ok ? make_uint4(p0, p1, q0, q1) : make_uint4(0u, 0u, 0u, 0u);
+                        *reinterpret_cast<uint4*>(xt + tile_off<SPR2, 32>(row, (cb >> 3) + (lg >> 1))) = o;
+                    } else {
+                        if (ok) *reinterpret_cast<uint4*>(yg + (size_t)t * C + cb + 8 * (lg >> 1)) = make_uint4(p0, p1, q0, q1);
+                    }
                 }
             }
         } else {
@@ -818,6 +860,78 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             }
         }
         }
+    }
+    if constexpr (T::UP) {
+        // ---------------- upsampler: z = ups(.) over the rows just written; convt_g_bf16_k's arithmetic, in its order (GUp above) ----------------
+        constexpr int UNR = T::UNR, UMR = T::UMR, UKS = T::UKS, UMB = C / 32, NQ = 2 * UKS, UPA = 3, URA = UPA + 1;
+        typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+        const auto rs_u = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.up_wp), 0, T::UP_BYTES, 0x00020000);
+        const unsigned u_voff = (unsigned)lane * 16;       // lane's bytes inside a k-step's [UMB][64][16 B]
+        const int ucol = wave * (N1 / T::UWN) + l31;        // + 32 nr: this lane's output frame in the tile = the tile row of frame q - 1
+        unsigned short* __restrict__ zg = static_cast<unsigned short*>(a.up_y) + (size_t)b * Lp * C;
+        f32x16 uacc[UMR][UNR], ub[2][UMR];
+        bf16x8 uaf[URA][UMR], ubf[2][UNR];
+        // chunk c's bias block: rows c * C/2 + 32 mr + 8 rq + 4 lh + i  (r = 4 rq + i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int mr = 0; mr < UMR; ++mr) {
+                typedef float f32x8 __attribute__((ext_vector_type(8)));
+                const float* __restrict__ bp = a.up_bias + c * (C / 2) + mr * 32 + 4 * lh;
+                const f32x4 q0 = *reinterpret_cast<const f32x4*>(bp), q1 = *reinterpret_cast<const f32x4*>(bp + 8);
+                const f32x4 q2 = *reinterpret_cast<const f32x4*>(bp + 16), q3 = *reinterpret_cast<const f32x4*>(bp + 24);
+                const f32x8 lo = __builtin_shufflevector(q0, q1, 0, 1, 2, 3, 4, 5, 6, 7), hi = __builtin_shufflevector(q2, q3, 0, 1, 2, 3, 4, 5, 6, 7);
+                ub[c][mr] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+            }
+        // A fragments of flat step g = c * NQ + tap * UKS + ks: chunk c's taps are frames c + tap of the 3-tap form; the weight stream runs across the chunks
+        auto uload_a = [&](auto g_tag) {
+            constexpr int g = decltype(g_tag)::value, c = g / NQ, s = g % NQ, f = c + s / UKS, ks = s % UKS;
+            constexpr int soff = ((f * UKS + ks) * UMB + c * UMR) * 1024;
+#pragma unroll
+            for (int mr = 0; mr < UMR; ++mr) uaf[g % URA][mr] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_u, u_voff + mr * 1024, soff, 0));
+        };
+        auto uload_b = [&](auto g_tag) {
+            constexpr int g = decltype(g_tag)::value, c = g / NQ, s = g % NQ, f = c + s / UKS, ks = s % UKS;
+#pragma unroll
+            for (int nr = 0; nr < UNR; ++nr) ubf[g & 1][nr] = *reinterpret_cast<const bf16x8*>(xt + tile_off<SPR2, 32>(ucol + 32 * nr + f, 2 * ks + lh));
+        };
+        static_for(std::make_integer_sequence<int, UPA>{}, uload_a);  // in flight across the barrier
+        __syncthreads();  // the tile's rows are written
+        VTTS_TL(a, wg_lin, 13);
+        uload_b(std::integral_constant<int, 0>{});
+        static_for(std::make_integer_sequence<int, 2 * NQ>{}, [&](auto g_tag) {
+            constexpr int g = decltype(g_tag)::value, c = g / NQ, s = g % NQ;
+            constexpr bool more_a = g + UPA < 2 * NQ, more_b = g + 1 < 2 * NQ;
+            if constexpr (more_a) uload_a(std::integral_constant<int, g + UPA>{});
+            if constexpr (more_b) uload_b(std::integral_constant<int, g + 1>{});
+#pragma unroll
+            for (int mr = 0; mr < UMR; ++mr)
+#pragma unroll
+                for (int nr = 0; nr < UNR; ++nr)
+                    uacc[mr][nr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(uaf[g % URA][mr], ubf[g & 1][nr], s == 0 ? ub[c][mr] : uacc[mr][nr], 0, 0, 0);
+            pin_loads<UMR * UNR, more_a ? UMR : 0, more_b ? UNR : 0>();
+            if constexpr (s + 1 == NQ) {
+                // chunk c is done: bf16 (the ResBlocks activate on load), 8 consecutive rows (phase c, co) of frame q per lane, 16-byte stores straight
+                // from the accumulator layout.  UTile::STAGE_OUT's form (both chunks held, whole rows out through LDS behind two more barriers) was
+                // built and measured: 25 / 21 us per launch faster at C = 128 / 64, inside three times the spread, and the pass no shorter
+                // (profiles/upfuse_findings.md section 3) — this launch is not HBM-bound as the separate upsampler was
+#pragma unroll
+                for (int mr = 0; mr < UMR; ++mr)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        const int rb = c * (C / 2) + mr * 32 + 16 * p;
+#pragma unroll
+                        for (int nr = 0; nr < UNR; ++nr) {
+                            const int n = ucol + 32 * nr, q = t0 + OH + n;
+                            unsigned p0 = pack_bf16x2(uacc[mr][nr][8 * p + 0], uacc[mr][nr][8 * p + 1]), p1 = pack_bf16x2(uacc[mr][nr][8 * p + 2], uacc[mr][nr][8 * p + 3]);
+                            unsigned q0 = pack_bf16x2(uacc[mr][nr][8 * p + 4], uacc[mr][nr][8 * p + 5]), q1 = pack_bf16x2(uacc[mr][nr][8 * p + 6], uacc[mr][nr][8 * p + 7]);
+                            swap_pair(p0, q0);
+                            swap_pair(p1, q1);
+                            if (n < TS && q < L) *reinterpret_cast<uint4*>(zg + (size_t)q * C + rb + 8 * lh) = make_uint4(p0, p1, q0, q1);
+                        }
+                    }
+            }
+        });
     }
     if constexpr (T::TAIL) {
         // ---------------- tail: tanh(conv_post(.)) over the rows just written (model.py:123-124); conv_post_bf16_k's arithmetic, in its order ----------------
@@ -894,7 +1008,7 @@ static hipError_t launch_g(const BConvArgs& a, hipStream_t s) {
     static DynLdsOnce once;  // per device (vtts_internal.h)
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&resblock_pair_g_bf16_k<T>), T::lds_bytes(T::MAXDIL) + VTTS_EXP_LDS_PAD, once); e != hipSuccess) return e;
     if (a.dil < 1 || a.dil > T::MAXDIL) return hipErrorInvalidValue;
-    constexpr int TS = T::TAIL ? T::NT2 - 2 * T::TAIL_H : T::NT2;
+    constexpr int TS = T::NT2 - 2 * T::OH;
     dim3 grid((a.L + TS - 1) / TS, 1, a.B);
     if ((int)grid.x >= XCD_MAP_MIN_TILES) grid.x = (grid.x + 7) / 8 * 8;  // whole rounds of the 8 XCDs; a tile index past the utterance exits at once
     hipLaunchKernelGGL(resblock_pair_g_bf16_k<T>, grid, dim3(T::THREADS), T::lds_bytes(a.dil) + VTTS_EXP_LDS_PAD, s, a);
@@ -914,6 +1028,12 @@ static hipError_t launch_g_ks(const BConvArgs& a, int K, hipStream_t s) {
 hipError_t launch_pair_g_bf16(int C, int K, const BConvArgs& a, hipStream_t s) {
     // narrow tiles for small launches (a.tile_pref: 1 forces the wide tile, 2 the narrow one)
     auto narrow = [&](int nt2) { return a.tile_pref == 2 || (a.tile_pref != 1 && (long)((a.L + nt2 - 1) / nt2) * a.B < G_MIN_WGS); };
+    if (a.up_y) {  // the next stage's transposed convolution rides on this launch (engine.hip: only where pair_up_bf16_supported); same width rule as the plain launch
+        if (K != 11 || a.tail_wav) return hipErrorInvalidValue;
+        if (C == 128) return narrow(G128<11>::NT2) ? launch_g<GUp<G128S<11>>>(a, s) : launch_g<GUp<G128<11>>>(a, s);
+        if (C == 64) return narrow(G64<11>::NT2) ? launch_g<GUp<G64S<11>>>(a, s) : launch_g<GUp<G64<11>>>(a, s);
+        return hipErrorInvalidValue;
+    }
     switch (C) {
         case 256: return narrow(G256<11>::NT2) ? launch_g_ks<G256S>(a, K, s) : launch_g_ks<G256>(a, K, s);
         case 128: return narrow(G128<11>::NT2) ? launch_g_ks<G128S>(a, K, s) : launch_g_ks<G128>(a, K, s);
@@ -930,6 +1050,12 @@ hipError_t launch_pair_g_bf16(int C, int K, const BConvArgs& a, hipStream_t s) {
 
 // where the last pair of the last stage can carry conv_post + tanh: C = 32 pairs at k = 11 (the V1 generator's last ResBlock), conv_post 32 -> 1, k = 7
 bool pair_tail_bf16_supported(int C, int K, int post_cin, int post_cout, int post_k) { return C == 32 && K == 11 && post_cin == 32 && post_cout == 1 && post_k == 7; }
+
+// where a stage's last pair can carry the next stage's transposed convolution (GUp): the k = 11 pairs at C = 128 / 64 in front of ups_2 / ups_3
+// (stride 2, k = 4, C -> C / 2: two taps per phase, M = C rows, the packing of convt_g_pack_geom(BCLS_UP2 / BCLS_UP3))
+bool pair_up_bf16_supported(int C, int K, int up_cls, int up_cin, int up_cout, int up_k, int up_stride) {
+    return K == 11 && ((C == 128 && up_cls == BCLS_UP2) || (C == 64 && up_cls == BCLS_UP3)) && up_cin == C && 2 * up_cout == C && up_k == 4 && up_stride == 2;
+}
 
 // one convolution = [q = tap*KSTEPS + ks][mblk][lane][8] bf16: bf16_pack with (ckc = C, tg = 1, mt = C)
 BPackGeom pair_g_pack_geom(int C, int K) { return BPackGeom{C, C, C, K, C, 1}; }

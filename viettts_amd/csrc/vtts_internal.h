@@ -201,6 +201,11 @@ struct BConvArgs {
     float* tail_wav;
     const float* tail_wf;
     const float* tail_bias;
+    // the next stage's transposed convolution fused into the stage-ending pair launch (kernels_bf16_rbg.hip: GUp): its weights in convt_g_pack_geom's
+    // order, its bias [C] and its output [B][L][C] (= the next stage's [B][2 L][C / 2]); nullptr = a plain pair launch.  y is then only read.
+    const void* up_wp;
+    const float* up_bias;
+    void* up_y;
 };
 
 struct BPackGeom { int cinp, ckc, coutp, ks, mt, tg; };
@@ -218,6 +223,8 @@ void bf16_pack(const float* Wc, int cin_real, const BPackGeom& g, unsigned short
 // a.x = raw pair input (also the residual), a.dil/a.pad = c1's rate / pad.
 bool pair_bf16_supported(int C, int K, int dil);
 bool pair_tail_bf16_supported(int C, int K, int post_cin, int post_cout, int post_k);
+// where a pair launch (accumulate, mean, LeakyReLU epilogue) can carry the stride-2 transposed convolution that follows its stage (a.up_y): BCLS_UP2 / BCLS_UP3
+bool pair_up_bf16_supported(int C, int K, int up_cls, int up_cin, int up_cout, int up_k, int up_stride);
 hipError_t launch_pair_g_bf16(int C, int K, const BConvArgs& a, hipStream_t s);
 BPackGeom pair_g_pack_geom(int C, int K);
 // resblock_pair_g_bf16_k's own weights: pair_g_pack_geom's order on the classes whose loops run 32 x 32 x 16 blocks, the 16 x 16 x 32 fragment order
