@@ -51,6 +51,9 @@ MEL_MIN_SAMPLES = 385  # include/vtts_mel.h: VTTS_MEL_MIN_SAMPLES
 DTW_MAX_FEAT = 128  # include/vtts_dtw.h: VTTS_DTW_MAX_FEAT
 DTW_MAX_FRAMES = 4096  # include/vtts_dtw.h: VTTS_DTW_MAX_FRAMES
 
+PITCH_FRAMES_PER_BLOCK = 8  # include/vtts_pitch.h: VTTS_PITCH_FRAMES_PER_BLOCK
+PITCH_MAX_LAG = 512  # include/vtts_pitch.h: VTTS_PITCH_MAX_LAG
+
 
 class MelCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
@@ -58,6 +61,10 @@ class MelCfg(C.Structure):
 
 class DtwCfg(C.Structure):
     _fields_ = [("n_feat", C.c_int32), ("band", C.c_int32), ("max_frames", C.c_int32)]
+
+
+class PitchCfg(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float)]
 
 
 class AudioCfg(C.Structure):
@@ -199,6 +206,16 @@ DTW_SIGS = {
 }
 
 
+# include/vtts_pitch.h, likewise a table of its own
+PITCH_SIGS = {
+    "vtts_pitch_create": (C.c_int, [C.POINTER(PitchCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_pitch_destroy": (None, [vp]),
+    "vtts_pitch_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_pitch_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_pitch_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, vp, i64, vp, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -209,6 +226,7 @@ MEL_EXPORTS = _exports("vtts_mel_")  # include/vtts_mel.h
 DISC_EXPORTS = _exports("vtts_disc_")  # include/vtts_disc.h
 AUDIO_EXPORTS = _exports("vtts_audio_")  # include/vtts_audio.h
 DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
+PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 
 
 def default_lib_path() -> Path:
@@ -262,7 +280,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

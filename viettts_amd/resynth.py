@@ -2,11 +2,12 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0]
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
-``FileNotFoundError`` without them.
+``FileNotFoundError`` without them.  ``--f0`` adds one line: F0 RMSE in cents, voicing error and gross error of the result against the input
+(``viettts_amd.pitch``).
 """
 from __future__ import annotations
 
@@ -91,6 +92,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output", required=True)
     ap.add_argument("--dtype", default="f32", choices=("f32", "bf16", "bf16x3"))
     ap.add_argument("--output-rate", type=int, default=None, help="convert the result to this rate on the GPU (default: the model's rate)")
+    ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of the result against the input (viettts_amd.pitch)")
     return ap
 
 
@@ -116,6 +118,10 @@ def main(argv=None) -> None:
         out = resampler(model_rate, a.output_rate, gen.device)(wav[0, :n].contiguous(), out_dtype="pcm16")
         wavio.write_wav_pcm16(a.output, out.cpu().numpy(), a.output_rate)
     print(f"wrote {a.output}: {n} samples, log-mel L1 against the input {log_mel_l1(wav[:, :n], y[:, :n].contiguous()):.4f}")
+    if a.f0:
+        from .pitch import default_tracker, format_metrics, wav_f0_metrics
+
+        print(format_metrics(wav_f0_metrics(wav[:, :n].contiguous(), y[:, :n].contiguous(), tracker=default_tracker(gen.device, model_rate))))
 
 
 if __name__ == "__main__":

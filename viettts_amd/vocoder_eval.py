@@ -1,13 +1,14 @@
 """Score a vocoder checkpoint with the objective HiFi-GAN optimises, on the GPU: wav -> log-mel (``MelFilter``) -> generator ->
 (y, y_hat) through the discriminators (``Discriminators``, include/vtts_disc.h), segment by segment.
 
-    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192]
+    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0]
 
 prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
 MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono (any rate but the model's is converted
 on the GPU first: ``viettts_amd.audio.Resampler``), the
 generator as ``mel2wave`` reads it (``assets/hifigan/config.json`` + a Haiku pickle) and upstream's ``do_*`` file; raises
 ``FileNotFoundError`` without them, before any input is touched.  Forward only: nothing is trained.
+``--f0`` adds one line: F0 RMSE in cents, voicing error and gross error of ``y_hat`` against ``y`` (``viettts_amd.pitch``), averaged over the passes.
 """
 from __future__ import annotations
 
@@ -21,17 +22,26 @@ from . import wavio
 from .nat.config import FLAGS as NAT_FLAGS
 
 MEL_WEIGHT = 45.0
+F0_KEYS = ("f0_rmse_cents", "voicing_error", "gross_error")  # what score_segments adds with a tracker
 
 
-def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None) -> dict:
-    """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction."""
+def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None) -> dict:
+    """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction.
+    With ``tracker`` (a ``viettts_amd.pitch.PitchTracker``) the result also holds ``f0_rmse_cents``, ``voicing_error`` and ``gross_error`` of
+    ``y_hat`` against ``y`` (``pitch.f0_metrics``)."""
     from .resynth import default_mel_filter, log_mel_l1
 
     mf = mel_filter or default_mel_filter(generator.device)
     y_hat = generator(mf(y))[:, : y.shape[1]].contiguous()
     L = discriminators.losses(y, y_hat)
     mel = log_mel_l1(y_hat, y, mel_filter=mf)
-    return {"adv": L.gen, "fm": L.feature, "mel": mel, "total": L.gen + L.feature + MEL_WEIGHT * mel, "disc": L.disc}
+    out = {"adv": L.gen, "fm": L.feature, "mel": mel, "total": L.gen + L.feature + MEL_WEIGHT * mel, "disc": L.disc}
+    if tracker is not None:
+        from .pitch import wav_f0_metrics
+
+        m = wav_f0_metrics(y_hat, y, tracker=tracker)
+        out.update({k: m[k] for k in F0_KEYS})
+    return out
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -42,6 +52,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--config", default="assets/hifigan/config.json")
     ap.add_argument("--segment", type=int, default=8192, help="samples per scored segment (a multiple of 256)")
     ap.add_argument("--batch", type=int, default=16, help="segments per pass")
+    ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of y_hat against y (viettts_amd.pitch)")
     return ap
 
 
@@ -75,16 +86,29 @@ def main(argv=None) -> None:
         segs += [x[i : i + a.segment] for i in range(0, len(x) - a.segment + 1, a.segment)]
     if not segs:
         raise ValueError(f"no input holds a whole segment of {a.segment} samples")
-    tot, n = {}, 0
+    trk = None
+    if a.f0:
+        from .pitch import default_tracker
+
+        trk = default_tracker(dev, NAT_FLAGS.sample_rate)
+    tot, n, f0_tot, f0_n = {}, 0, {}, {}
     for i in range(0, len(segs), a.batch):
         y = torch.from_numpy(np.stack(segs[i : i + a.batch])).to(dev)
-        r = score_segments(y, gen, disc)
+        r = score_segments(y, gen, disc, tracker=trk)
+        f0 = {k: r.pop(k) for k in F0_KEYS if k in r}
         for k, v in r.items():
             tot[k] = tot.get(k, 0.0) + v * y.shape[0]
         n += y.shape[0]
+        for k, v in f0.items():  # a pass without a frame voiced in both has no F0 figure (nan): it is left out of that figure's mean
+            if v == v:
+                f0_tot[k], f0_n[k] = f0_tot.get(k, 0.0) + v * y.shape[0], f0_n.get(k, 0) + y.shape[0]
     m = {k: v / n for k, v in tot.items()}
     print(f"{n} segments of {a.segment} samples: adversarial {m['adv']:.4f}  feature matching {m['fm']:.4f}  log-mel L1 {m['mel']:.4f}  "
           f"adv + fm + {MEL_WEIGHT:g} * mel = {m['total']:.4f}  (discriminator loss {m['disc']:.4f})")
+    if trk is not None:
+        f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in F0_KEYS}
+        print(f"F0 of y_hat against y, mean over the passes: RMSE {f['f0_rmse_cents']:.1f} cents  voicing error {100 * f['voicing_error']:.2f} %  "
+              f"gross error {100 * f['gross_error']:.2f} %")
 
 
 if __name__ == "__main__":
