@@ -54,6 +54,10 @@ DTW_MAX_FRAMES = 4096  # include/vtts_dtw.h: VTTS_DTW_MAX_FRAMES
 PITCH_FRAMES_PER_BLOCK = 8  # include/vtts_pitch.h: VTTS_PITCH_FRAMES_PER_BLOCK
 PITCH_MAX_LAG = 512  # include/vtts_pitch.h: VTTS_PITCH_MAX_LAG
 
+LOUDNESS_CHUNK = 32  # include/vtts_loudness.h: VTTS_LOUDNESS_CHUNK
+LOUDNESS_SEGMENT = 8192  # include/vtts_loudness.h: VTTS_LOUDNESS_SEGMENT
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 96000  # include/vtts_loudness.h: VTTS_LOUDNESS_MIN_RATE / _MAX_RATE
+
 
 class MelCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
@@ -65,6 +69,10 @@ class DtwCfg(C.Structure):
 
 class PitchCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float)]
+
+
+class LoudnessCfg(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32)]
 
 
 class AudioCfg(C.Structure):
@@ -216,6 +224,19 @@ PITCH_SIGS = {
 }
 
 
+# include/vtts_loudness.h, likewise
+LOUDNESS_SIGS = {
+    "vtts_loudness_create": (C.c_int, [C.POINTER(LoudnessCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_loudness_destroy": (None, [vp]),
+    "vtts_loudness_coefficients": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "vtts_loudness_num_blocks": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_loudness_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_loudness_measure": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+    "vtts_loudness_normalize": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, C.c_float, C.c_float, C.c_float, vp, C.c_int, i64,
+                                          vp, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -227,6 +248,7 @@ DISC_EXPORTS = _exports("vtts_disc_")  # include/vtts_disc.h
 AUDIO_EXPORTS = _exports("vtts_audio_")  # include/vtts_audio.h
 DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
 PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
+LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 
 
 def default_lib_path() -> Path:
@@ -280,7 +302,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

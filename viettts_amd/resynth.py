@@ -2,7 +2,7 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23]
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
@@ -93,6 +93,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dtype", default="f32", choices=("f32", "bf16", "bf16x3"))
     ap.add_argument("--output-rate", type=int, default=None, help="convert the result to this rate on the GPU (default: the model's rate)")
     ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of the result against the input (viettts_amd.pitch)")
+    ap.add_argument("--loudness", type=float, default=None, help="write the result at this BS.1770 integrated loudness in LUFS (viettts_amd.loudness); the figures printed are of the result before the gain")
     return ap
 
 
@@ -110,12 +111,18 @@ def main(argv=None) -> None:
         y = resampler(sr, model_rate, gen.device)(y)
     wav = resynthesize(y, gen)
     n = 256 * (y.shape[1] // 256)
+    written = wav
+    if a.loudness is not None:
+        from .loudness import default_meter
+
+        written, gains = default_meter(gen.device, model_rate).normalize(wav, lengths=[n], target=a.loudness)
+        print(f"loudness: gain {20.0 * np.log10(float(gains[0])):+.2f} dB to {a.loudness:.1f} LUFS")
     if a.output_rate is None or a.output_rate == model_rate:
-        wavio.write_wav(a.output, wav[0, :n].cpu().numpy(), model_rate)
+        wavio.write_wav(a.output, written[0, :n].cpu().numpy(), model_rate)
     else:
         from .audio import resampler
 
-        out = resampler(model_rate, a.output_rate, gen.device)(wav[0, :n].contiguous(), out_dtype="pcm16")
+        out = resampler(model_rate, a.output_rate, gen.device)(written[0, :n].contiguous(), out_dtype="pcm16")
         wavio.write_wav_pcm16(a.output, out.cpu().numpy(), a.output_rate)
     print(f"wrote {a.output}: {n} samples, log-mel L1 against the input {log_mel_l1(wav[:, :n], y[:, :n].contiguous()):.4f}")
     if a.f0:

@@ -55,6 +55,7 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--resample", action="store_true", help="(extension) convert the samples to --sample-rate on the GPU instead of relabelling them")
     p.add_argument("--stream", action="store_true", help="(extension) write the audio chunk by chunk while the decoder is still running")
     p.add_argument("--chunk-frames", default=32, type=int, help="(extension) mel frames per streamed chunk")
+    p.add_argument("--loudness", default=None, type=float, help="(extension) bring the clip to this BS.1770 integrated loudness in LUFS, on the GPU")
     return p
 
 
@@ -104,6 +105,8 @@ def main(argv=None) -> int:
             parser.error("--stream with --resample: a streamed resampler would need a filter state across chunks")
         if args.low_latency:
             parser.error("--stream with --low-latency: a streamed decoder runs the per-frame launches, not the resident kernel")
+        if args.loudness is not None:
+            parser.error("--stream with --loudness: integrated loudness needs the whole utterance")
         if args.chunk_frames < 1:
             parser.error("--chunk-frames must be positive")
         if args.mel_file is None and args.text is None:
@@ -127,6 +130,13 @@ def main(argv=None) -> int:
         print("Normalized text input:", text)
         mel = text2mel(text, args.lexicon_file, args.silence_duration)
     wave = mel2wave(mel)
+    if args.loudness is not None:
+        from .loudness import default_meter
+
+        meter = default_meter("cuda", FLAGS.sample_rate)
+        out, gains = meter.normalize(np.asarray(wave, dtype=np.float32).reshape(1, -1), target=args.loudness)
+        print(f"loudness: gain {20.0 * np.log10(float(gains[0])):+.2f} dB to {args.loudness:.1f} LUFS")
+        wave = out[0].cpu().numpy()
     print("writing output to file", args.output)
     if args.resample and args.sample_rate != FLAGS.sample_rate:
         from .audio import Resampler

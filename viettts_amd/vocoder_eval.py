@@ -1,7 +1,7 @@
 """Score a vocoder checkpoint with the objective HiFi-GAN optimises, on the GPU: wav -> log-mel (``MelFilter``) -> generator ->
 (y, y_hat) through the discriminators (``Discriminators``, include/vtts_disc.h), segment by segment.
 
-    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0]
+    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness]
 
 prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
 MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono (any rate but the model's is converted
@@ -23,12 +23,14 @@ from .nat.config import FLAGS as NAT_FLAGS
 
 MEL_WEIGHT = 45.0
 F0_KEYS = ("f0_rmse_cents", "voicing_error", "gross_error")  # what score_segments adds with a tracker
+LOUDNESS_KEYS = ("lufs_y", "lufs_y_hat")  # ... and with a meter
 
 
-def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None) -> dict:
+def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None) -> dict:
     """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction.
     With ``tracker`` (a ``viettts_amd.pitch.PitchTracker``) the result also holds ``f0_rmse_cents``, ``voicing_error`` and ``gross_error`` of
-    ``y_hat`` against ``y`` (``pitch.f0_metrics``)."""
+    ``y_hat`` against ``y`` (``pitch.f0_metrics``); with ``meter`` (a ``viettts_amd.loudness.LoudnessMeter``) ``lufs_y`` and ``lufs_y_hat``: the
+    BS.1770 integrated loudness of the pass's segments laid end to end (nan when no block passes the gates)."""
     from .resynth import default_mel_filter, log_mel_l1
 
     mf = mel_filter or default_mel_filter(generator.device)
@@ -41,6 +43,10 @@ def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, 
 
         m = wav_f0_metrics(y_hat, y, tracker=tracker)
         out.update({k: m[k] for k in F0_KEYS})
+    if meter is not None:  # one row: a segment alone may be shorter than a 400 ms block
+        for k, w in zip(LOUDNESS_KEYS, (y, y_hat)):
+            v = float(meter(w.reshape(1, -1)).integrated[0])
+            out[k] = v if v > float("-inf") else float("nan")
     return out
 
 
@@ -53,6 +59,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--segment", type=int, default=8192, help="samples per scored segment (a multiple of 256)")
     ap.add_argument("--batch", type=int, default=16, help="segments per pass")
     ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of y_hat against y (viettts_amd.pitch)")
+    ap.add_argument("--loudness", action="store_true", help="also print the BS.1770 integrated loudness of y and y_hat and their difference (viettts_amd.loudness)")
     return ap
 
 
@@ -91,11 +98,16 @@ def main(argv=None) -> None:
         from .pitch import default_tracker
 
         trk = default_tracker(dev, NAT_FLAGS.sample_rate)
+    meter = None
+    if a.loudness:
+        from .loudness import default_meter
+
+        meter = default_meter(dev, NAT_FLAGS.sample_rate)
     tot, n, f0_tot, f0_n = {}, 0, {}, {}
     for i in range(0, len(segs), a.batch):
         y = torch.from_numpy(np.stack(segs[i : i + a.batch])).to(dev)
-        r = score_segments(y, gen, disc, tracker=trk)
-        f0 = {k: r.pop(k) for k in F0_KEYS if k in r}
+        r = score_segments(y, gen, disc, tracker=trk, meter=meter)
+        f0 = {k: r.pop(k) for k in F0_KEYS + LOUDNESS_KEYS if k in r}
         for k, v in r.items():
             tot[k] = tot.get(k, 0.0) + v * y.shape[0]
         n += y.shape[0]
@@ -109,6 +121,10 @@ def main(argv=None) -> None:
         f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in F0_KEYS}
         print(f"F0 of y_hat against y, mean over the passes: RMSE {f['f0_rmse_cents']:.1f} cents  voicing error {100 * f['voicing_error']:.2f} %  "
               f"gross error {100 * f['gross_error']:.2f} %")
+    if meter is not None:
+        f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in LOUDNESS_KEYS}
+        print(f"integrated loudness, mean over the passes: y {f['lufs_y']:.2f} LUFS  y_hat {f['lufs_y_hat']:.2f} LUFS  "
+              f"difference {f['lufs_y_hat'] - f['lufs_y']:+.2f} LU")
 
 
 if __name__ == "__main__":
