@@ -58,6 +58,10 @@ LOUDNESS_CHUNK = 32  # include/vtts_loudness.h: VTTS_LOUDNESS_CHUNK
 LOUDNESS_SEGMENT = 8192  # include/vtts_loudness.h: VTTS_LOUDNESS_SEGMENT
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 96000  # include/vtts_loudness.h: VTTS_LOUDNESS_MIN_RATE / _MAX_RATE
 
+STOI_MAX_SAMPLES = 1 << 24  # include/vtts_stoi.h: VTTS_STOI_MAX_SAMPLES
+STOI_FRAMES_PER_BLOCK = 8  # include/vtts_stoi.h: VTTS_STOI_FRAMES_PER_BLOCK
+STOI_FRAME, STOI_HOP, STOI_BANDS, STOI_SEG = 256, 128, 15, 30  # include/vtts_stoi.h: VTTS_STOI_FRAME / _HOP / _BANDS / _SEG
+
 
 class MelCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
@@ -237,6 +241,17 @@ LOUDNESS_SIGS = {
 }
 
 
+# include/vtts_stoi.h, likewise
+STOI_SIGS = {
+    "vtts_stoi_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+    "vtts_stoi_destroy": (None, [vp]),
+    "vtts_stoi_window": (C.c_int, [vp, fp]),
+    "vtts_stoi_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_stoi_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_stoi_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, sz, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -249,6 +264,7 @@ AUDIO_EXPORTS = _exports("vtts_audio_")  # include/vtts_audio.h
 DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
 PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
+STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
 
 
 def default_lib_path() -> Path:
@@ -302,7 +318,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -2,7 +2,7 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23] [--stoi]
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
@@ -94,6 +94,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output-rate", type=int, default=None, help="convert the result to this rate on the GPU (default: the model's rate)")
     ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of the result against the input (viettts_amd.pitch)")
     ap.add_argument("--loudness", type=float, default=None, help="write the result at this BS.1770 integrated loudness in LUFS (viettts_amd.loudness); the figures printed are of the result before the gain")
+    ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of the result against the input at 10 kHz (viettts_amd.stoi); NaN below 30 analysis frames")
     return ap
 
 
@@ -129,6 +130,10 @@ def main(argv=None) -> None:
         from .pitch import default_tracker, format_metrics, wav_f0_metrics
 
         print(format_metrics(wav_f0_metrics(wav[:, :n].contiguous(), y[:, :n].contiguous(), tracker=default_tracker(gen.device, model_rate))))
+    if a.stoi:
+        from .stoi import format_result, wav_stoi
+
+        print(format_result(wav_stoi(y[:, :n].contiguous(), wav[:, :n].contiguous(), rate=model_rate)))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Score a vocoder checkpoint with the objective HiFi-GAN optimises, on the GPU: wav -> log-mel (``MelFilter``) -> generator ->
 (y, y_hat) through the discriminators (``Discriminators``, include/vtts_disc.h), segment by segment.
 
-    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness]
+    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness] [--stoi]
 
 prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
 MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono (any rate but the model's is converted
@@ -9,6 +9,7 @@ on the GPU first: ``viettts_amd.audio.Resampler``), the
 generator as ``mel2wave`` reads it (``assets/hifigan/config.json`` + a Haiku pickle) and upstream's ``do_*`` file; raises
 ``FileNotFoundError`` without them, before any input is touched.  Forward only: nothing is trained.
 ``--f0`` adds one line: F0 RMSE in cents, voicing error and gross error of ``y_hat`` against ``y`` (``viettts_amd.pitch``), averaged over the passes.
+``--stoi`` adds one line: STOI and ESTOI of ``y_hat`` against ``y`` (``viettts_amd.stoi``), each pass's segments laid end to end as one row.
 """
 from __future__ import annotations
 
@@ -24,13 +25,16 @@ from .nat.config import FLAGS as NAT_FLAGS
 MEL_WEIGHT = 45.0
 F0_KEYS = ("f0_rmse_cents", "voicing_error", "gross_error")  # what score_segments adds with a tracker
 LOUDNESS_KEYS = ("lufs_y", "lufs_y_hat")  # ... and with a meter
+STOI_KEYS = ("stoi", "estoi")  # ... and with a stoi_meter
 
 
-def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None) -> dict:
+def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None, stoi_meter=None, rate=None) -> dict:
     """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction.
     With ``tracker`` (a ``viettts_amd.pitch.PitchTracker``) the result also holds ``f0_rmse_cents``, ``voicing_error`` and ``gross_error`` of
     ``y_hat`` against ``y`` (``pitch.f0_metrics``); with ``meter`` (a ``viettts_amd.loudness.LoudnessMeter``) ``lufs_y`` and ``lufs_y_hat``: the
-    BS.1770 integrated loudness of the pass's segments laid end to end (nan when no block passes the gates)."""
+    BS.1770 integrated loudness of the pass's segments laid end to end (nan when no block passes the gates); with ``stoi_meter`` (a
+    ``viettts_amd.stoi.StoiMeter``) ``stoi`` and ``estoi`` of ``y_hat`` against ``y``, likewise laid end to end as one row at ``rate`` (the
+    model's without it) and converted to 10 kHz on the device (nan when the row holds no 30-frame segment)."""
     from .resynth import default_mel_filter, log_mel_l1
 
     mf = mel_filter or default_mel_filter(generator.device)
@@ -47,6 +51,11 @@ def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, 
         for k, w in zip(LOUDNESS_KEYS, (y, y_hat)):
             v = float(meter(w.reshape(1, -1)).integrated[0])
             out[k] = v if v > float("-inf") else float("nan")
+    if stoi_meter is not None:  # one row: a segment alone may hold fewer than 30 frames
+        from .stoi import wav_stoi
+
+        r = wav_stoi(y.reshape(1, -1), y_hat.reshape(1, -1), rate=int(rate or NAT_FLAGS.sample_rate), meter=stoi_meter)
+        out.update(stoi=float(r.stoi[0]), estoi=float(r.estoi[0]))
     return out
 
 
@@ -60,6 +69,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch", type=int, default=16, help="segments per pass")
     ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of y_hat against y (viettts_amd.pitch)")
     ap.add_argument("--loudness", action="store_true", help="also print the BS.1770 integrated loudness of y and y_hat and their difference (viettts_amd.loudness)")
+    ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of y_hat against y at 10 kHz (viettts_amd.stoi), each pass's segments laid end to end as "
+                    "one row: the default --segment 8192 is 5120 samples or 38 frames at 10 kHz, and a pass whose row holds fewer than 30 frames "
+                    "after its silent ones are dropped (one segment much shorter than 8192) gives NaN and is left out of the mean")
     return ap
 
 
@@ -103,11 +115,16 @@ def main(argv=None) -> None:
         from .loudness import default_meter
 
         meter = default_meter(dev, NAT_FLAGS.sample_rate)
+    stoi_meter = None
+    if a.stoi:
+        from .stoi import default_stoi_meter
+
+        stoi_meter = default_stoi_meter(dev)
     tot, n, f0_tot, f0_n = {}, 0, {}, {}
     for i in range(0, len(segs), a.batch):
         y = torch.from_numpy(np.stack(segs[i : i + a.batch])).to(dev)
-        r = score_segments(y, gen, disc, tracker=trk, meter=meter)
-        f0 = {k: r.pop(k) for k in F0_KEYS + LOUDNESS_KEYS if k in r}
+        r = score_segments(y, gen, disc, tracker=trk, meter=meter, stoi_meter=stoi_meter)
+        f0 = {k: r.pop(k) for k in F0_KEYS + LOUDNESS_KEYS + STOI_KEYS if k in r}
         for k, v in r.items():
             tot[k] = tot.get(k, 0.0) + v * y.shape[0]
         n += y.shape[0]
@@ -125,6 +142,9 @@ def main(argv=None) -> None:
         f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in LOUDNESS_KEYS}
         print(f"integrated loudness, mean over the passes: y {f['lufs_y']:.2f} LUFS  y_hat {f['lufs_y_hat']:.2f} LUFS  "
               f"difference {f['lufs_y_hat'] - f['lufs_y']:+.2f} LU")
+    if stoi_meter is not None:
+        f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in STOI_KEYS}
+        print(f"intelligibility of y_hat against y, mean over the passes: STOI {f['stoi']:.4f}  ESTOI {f['estoi']:.4f}")
 
 
 if __name__ == "__main__":
