@@ -32,7 +32,8 @@
  *   normalise    g = min(10^((target_lufs - I) / 20), 10^(max_gain_db / 20), 10^(ceiling_dbfs / 20) / sample_peak), each term computed
  *                in double and rounded to fp32 before the min; g = 1 when I = -inf (or NaN).  Output sample = x * g, one fp32 multiply,
  *                stored as fp32 or as PCM16 by vtts_audio.h's rule (clip to [-1, 1], times 32767 in double, round half to even, NaN -> 0).
- *                ceiling_dbfs acts on the SAMPLE peak: there is no true-peak (oversampled) measurement and no limiter.
+ *                ceiling_dbfs acts on the SAMPLE peak, and the gain is one number per row: the true-peak (4x oversampled) measurement and
+ *                the look-ahead limiter are a separate component, vtts_limiter.h, which takes `integrated` from here.
  *
  * Same conventions as vtts_audio.h (vtts_status and vtts_last_error() of vtts_hifigan.h): plain pointers and sizes, 0 or a negative
  * vtts_status, device memory owned by the caller, asynchronous on the given stream.  The handle owns nothing on the device: the filter's

@@ -62,6 +62,12 @@ STOI_MAX_SAMPLES = 1 << 24  # include/vtts_stoi.h: VTTS_STOI_MAX_SAMPLES
 STOI_FRAMES_PER_BLOCK = 8  # include/vtts_stoi.h: VTTS_STOI_FRAMES_PER_BLOCK
 STOI_FRAME, STOI_HOP, STOI_BANDS, STOI_SEG = 256, 128, 15, 30  # include/vtts_stoi.h: VTTS_STOI_FRAME / _HOP / _BANDS / _SEG
 
+LIMITER_TILE = 4096  # include/vtts_limiter.h: VTTS_LIMITER_TILE
+LIMITER_RUN = 16  # include/vtts_limiter.h: VTTS_LIMITER_RUN
+LIMITER_PHASE_TAPS = 52  # include/vtts_limiter.h: VTTS_LIMITER_PHASE_TAPS
+LIMITER_MIN_RATE, LIMITER_MAX_RATE = 8000, 96000  # include/vtts_limiter.h: VTTS_LIMITER_MIN_RATE / _MAX_RATE
+LIMITER_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/limiter.hip: the rows whose lengths one launch carries
+
 
 class MelCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float)]
@@ -77,6 +83,10 @@ class PitchCfg(C.Structure):
 
 class LoudnessCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32)]
+
+
+class LimiterCfg(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("lookahead_ms", C.c_float)]
 
 
 class AudioCfg(C.Structure):
@@ -252,6 +262,19 @@ STOI_SIGS = {
 }
 
 
+# include/vtts_limiter.h, likewise
+LIMITER_SIGS = {
+    "vtts_limiter_create": (C.c_int, [C.POINTER(LimiterCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_limiter_destroy": (None, [vp]),
+    "vtts_limiter_lookahead": (C.c_int, [vp, C.POINTER(C.c_int32)]),
+    "vtts_limiter_taps": (C.c_int, [vp, fp]),
+    "vtts_limiter_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_limiter_true_peak": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, vp, sz, vp]),
+    "vtts_limiter_pregain": (C.c_int, [vp, vp, C.c_int, C.c_float, C.c_float, vp, vp]),
+    "vtts_limiter_apply": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, C.c_float, vp, C.c_int, i64, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -265,6 +288,7 @@ DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
 PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
+LIMITER_EXPORTS = tuple(LIMITER_SIGS)  # include/vtts_limiter.h
 
 
 def default_lib_path() -> Path:
@@ -318,7 +342,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **LIMITER_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -8,7 +8,8 @@ target level written as float32 or PCM16 (include/vtts_loudness.h, viettts_amd/c
     python -m viettts_amd.loudness --wav F.wav [--target -23 --output out.wav]
 
 Everything stays on the device: ``normalize`` reads the meter's results where the kernel left them.  The ceiling acts on the SAMPLE peak;
-there is no true-peak measurement, loudness range, multichannel weighting or limiter, and the streamed synthesis paths are not hooked
+true-peak metering and the look-ahead limiter are ``viettts_amd.limiter.TruePeakLimiter`` (its ``normalize`` runs this meter and holds the ceiling
+in dBTP instead); there is no loudness range or multichannel weighting, and the streamed synthesis paths are not hooked
 (integrated loudness needs the whole utterance).  The reference has no loudness stage; nothing here is re-exported under ``vietTTS/``.
 No CPU fallback: the kernels are the only implementation.
 """

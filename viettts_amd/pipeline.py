@@ -84,12 +84,14 @@ def _copy_stream(device: torch.device):
 def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, acoustic_model, generator, silence_duration: float = -1.0,
                          dropout_seed: Optional[int] = 0, rank: int = 0, world: int = 1, gen_batch: int = 0,
                          timing: Optional[dict] = None, out_dtype: str = "f32", out_rate: Optional[int] = None,
-                         loudness: Optional[float] = None) -> Dict[int, np.ndarray]:
+                         loudness: Optional[float] = None, limit: bool = False) -> Dict[int, np.ndarray]:
     """Waveforms (float32, 16 kHz samples) of THIS rank's sentences, keyed by sentence index.  ``out_dtype="pcm16"`` returns int16
     arrays equal to ``wavio.float_to_pcm16`` of the default's, and ``out_rate`` samples at that rate: each pass is then converted
     (``viettts_amd.audio.Resampler``) and packed on the device, and only the packed samples are read back.  ``loudness`` (a target in LUFS;
     off by default) brings every sentence to that BS.1770 integrated loudness on the device, behind the generator and in front of the rate
-    and format conversion (``viettts_amd.loudness.LoudnessMeter.normalize`` at its default ceiling and largest gain).  ``timing`` (a dict) receives
+    and format conversion (``viettts_amd.loudness.LoudnessMeter.normalize`` at its default ceiling and largest gain).  With ``limit=True`` that
+    gain stage is ``viettts_amd.limiter.TruePeakLimiter.normalize`` at -1 dBTP instead: the gain to the target in full, and a look-ahead limiter on
+    the true peak in place of the sample-peak cap (``limit`` without ``loudness`` is an error).  ``timing`` (a dict) receives
     wall seconds per stage.  The stages run one after the other on the caller's stream; a pass's waveforms leave for pinned host memory
     on a copy stream while the next pass computes.  Masks are seeded by the GLOBAL sentence index and every stage computes a row
     independently of its batch, so the samples depend neither on the shard nor on the batch (tests/test_gpu_nat.py: bit-identical to each
@@ -108,6 +110,8 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
 
     if out_dtype not in ("f32", "pcm16"):
         raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
+    if limit and loudness is None:
+        raise ValueError("limit=True needs a loudness target")
     convert = out_dtype != "f32" or (out_rate is not None and int(out_rate) != t2m.FLAGS.sample_rate)
     mine = shard_utterances([len(t) for t in token_lists], world)[rank]
     if not mine:
@@ -180,7 +184,11 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
                 batch = torch.nn.functional.pad(batch, (0, 0, 0, Ts - batch.shape[1]))
             batch = batch.contiguous()
             w = generator.forward_ragged(batch, fr) if ragged else generator(batch)
-            if loudness is not None:  # per-sentence gain on the device: no host round trip
+            if loudness is not None and limit:  # the gain to the target, and the limiter under -1 dBTP, on the device
+                from .limiter import default_limiter
+
+                w, _ = default_limiter(dev, t2m.FLAGS.sample_rate).normalize(w, lengths=[generator.hop * f for f in fr], target=float(loudness))
+            elif loudness is not None:  # per-sentence gain on the device: no host round trip
                 from .loudness import default_meter
 
                 w, _ = default_meter(dev, t2m.FLAGS.sample_rate).normalize(w, lengths=[generator.hop * f for f in fr], target=float(loudness))

@@ -2,7 +2,7 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23] [--stoi]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi]
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
@@ -94,6 +94,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output-rate", type=int, default=None, help="convert the result to this rate on the GPU (default: the model's rate)")
     ap.add_argument("--f0", action="store_true", help="also print F0 RMSE (cents), voicing error and gross error of the result against the input (viettts_amd.pitch)")
     ap.add_argument("--loudness", type=float, default=None, help="write the result at this BS.1770 integrated loudness in LUFS (viettts_amd.loudness); the figures printed are of the result before the gain")
+    ap.add_argument("--limit", action="store_true", help="with --loudness: the full gain to the target and a look-ahead limiter under -1 dBTP (viettts_amd.limiter) in place of the sample-peak cap")
     ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of the result against the input at 10 kHz (viettts_amd.stoi); NaN below 30 analysis frames")
     return ap
 
@@ -102,6 +103,8 @@ def main(argv=None) -> None:
     from .hifigan.mel2wave import _generator
 
     a = build_parser().parse_args(argv)
+    if a.limit and a.loudness is None:
+        raise SystemExit("--limit needs --loudness")
     gen = _generator(a.dtype)  # FileNotFoundError without config / checkpoint, before the input is touched
     sr, pcm = wavio.read_wav(a.input)
     model_rate = NAT_FLAGS.sample_rate
@@ -113,7 +116,13 @@ def main(argv=None) -> None:
     wav = resynthesize(y, gen)
     n = 256 * (y.shape[1] // 256)
     written = wav
-    if a.loudness is not None:
+    if a.loudness is not None and a.limit:
+        from .limiter import default_limiter
+
+        written, res = default_limiter(gen.device, model_rate).normalize(wav, lengths=[n], target=a.loudness)
+        print(f"loudness: gain {20.0 * np.log10(float(res.gains[0])):+.2f} dB to {a.loudness:.1f} LUFS, limited by at most "
+              f"{-20.0 * np.log10(float(res.min_gain[0])):.2f} dB under -1.0 dBTP")
+    elif a.loudness is not None:
         from .loudness import default_meter
 
         written, gains = default_meter(gen.device, model_rate).normalize(wav, lengths=[n], target=a.loudness)

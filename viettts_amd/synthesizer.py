@@ -56,6 +56,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--stream", action="store_true", help="(extension) write the audio chunk by chunk while the decoder is still running")
     p.add_argument("--chunk-frames", default=32, type=int, help="(extension) mel frames per streamed chunk")
     p.add_argument("--loudness", default=None, type=float, help="(extension) bring the clip to this BS.1770 integrated loudness in LUFS, on the GPU")
+    p.add_argument("--limit", action="store_true", help="(extension) with --loudness: the full gain to the target and a look-ahead limiter under -1 dBTP "
+                   "(viettts_amd.limiter) in place of the sample-peak cap")
     return p
 
 
@@ -100,6 +102,8 @@ def _stream(args) -> int:
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.limit and args.loudness is None:
+        parser.error("--limit needs --loudness")
     if args.stream:  # argument errors before anything touches a device
         if args.resample:
             parser.error("--stream with --resample: a streamed resampler would need a filter state across chunks")
@@ -130,7 +134,14 @@ def main(argv=None) -> int:
         print("Normalized text input:", text)
         mel = text2mel(text, args.lexicon_file, args.silence_duration)
     wave = mel2wave(mel)
-    if args.loudness is not None:
+    if args.loudness is not None and args.limit:
+        from .limiter import default_limiter
+
+        out, res = default_limiter("cuda", FLAGS.sample_rate).normalize(np.asarray(wave, dtype=np.float32).reshape(1, -1), target=args.loudness)
+        print(f"loudness: gain {20.0 * np.log10(float(res.gains[0])):+.2f} dB to {args.loudness:.1f} LUFS, limited by at most "
+              f"{-20.0 * np.log10(float(res.min_gain[0])):.2f} dB under -1.0 dBTP")
+        wave = out[0].cpu().numpy()
+    elif args.loudness is not None:
         from .loudness import default_meter
 
         meter = default_meter("cuda", FLAGS.sample_rate)
