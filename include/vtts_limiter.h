@@ -43,7 +43,7 @@
  * tests/_limiter_oracle.py restates the contract in float64 and, for the error scale, in float32.
  *
  * Out of scope: loudness range (LRA), release shaping other than the symmetric window, multiband or soft-knee compression, re-metering or
- * iterating until the limited row lands exactly on the target, stereo, streamed audio, gradients.
+ * iterating until the limited row lands exactly on the target, stereo, gradients.
  *
  * Same conventions as vtts_loudness.h (vtts_status and vtts_last_error() of vtts_hifigan.h): plain pointers and sizes, 0 or a negative
  * vtts_status, device memory owned by the caller, asynchronous on the given stream.  The handle owns nothing on the device: the 208 taps

@@ -67,6 +67,8 @@ LIMITER_RUN = 16  # include/vtts_limiter.h: VTTS_LIMITER_RUN
 LIMITER_PHASE_TAPS = 52  # include/vtts_limiter.h: VTTS_LIMITER_PHASE_TAPS
 LIMITER_MIN_RATE, LIMITER_MAX_RATE = 8000, 96000  # include/vtts_limiter.h: VTTS_LIMITER_MIN_RATE / _MAX_RATE
 LIMITER_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/limiter.hip: the rows whose lengths one launch carries
+LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
+LIMSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_limstream.h: VTTS_LIMSTREAM_ROWS_PER_LAUNCH
 
 
 class MelCfg(C.Structure):
@@ -275,6 +277,19 @@ LIMITER_SIGS = {
 }
 
 
+# include/vtts_limstream.h, likewise
+i32p = C.POINTER(C.c_int32)
+LIMSTREAM_SIGS = {
+    "vtts_limstream_create": (C.c_int, [C.POINTER(LimiterCfg), C.c_int, C.c_int, C.c_int32, C.c_float, C.POINTER(vp)]),
+    "vtts_limstream_destroy": (None, [vp]),
+    "vtts_limstream_lookahead": (C.c_int, [vp, i32p]),
+    "vtts_limstream_state_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "vtts_limstream_reset": (C.c_int, [vp, C.c_int, C.c_float]),
+    "vtts_limstream_emit": (C.c_int, [vp, i64, i64, C.c_int32, C.c_int, C.POINTER(i64)]),
+    "vtts_limstream_push": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, i32p, i64, i32p, i32p, vp, C.c_int, i32p, vp, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -289,6 +304,7 @@ PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
 LIMITER_EXPORTS = tuple(LIMITER_SIGS)  # include/vtts_limiter.h
+LIMSTREAM_EXPORTS = tuple(LIMSTREAM_SIGS)  # include/vtts_limstream.h
 
 
 def default_lib_path() -> Path:
@@ -342,7 +358,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **LIMITER_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

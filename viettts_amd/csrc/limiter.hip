@@ -29,20 +29,26 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_limiter.h"
 #include "audio_design.h"
+#include "limiter_common.h"
 #include "vtts_internal.h"
 
 using vtts::failf;
 namespace ad = vtts_audio_design;
+using vtts_limiter_dev::from_float;
+using vtts_limiter_dev::KP;
+using vtts_limiter_dev::LEAD;
+using vtts_limiter_dev::LimTaps;
+using vtts_limiter_dev::OS;
+using vtts_limiter_dev::padded;
+using vtts_limiter_dev::req_of;
+using vtts_limiter_dev::to_float;
 
 namespace {
 
 constexpr int TILE = VTTS_LIMITER_TILE;
 constexpr int RUN = VTTS_LIMITER_RUN;
-constexpr int KP = VTTS_LIMITER_PHASE_TAPS;
-constexpr int OS = VTTS_LIMITER_OVERSAMPLE;
 constexpr int THREADS = 256;
 constexpr int ROWS_PER_LAUNCH = 128;
-constexpr int LEAD = 27;              // x[n - LEAD] meets a phase's first tap
 constexpr int SPAN = TILE + KP + 4;   // staged samples of a tile: x[t0 - LEAD .. t0 + TILE + 28]
 constexpr int MAX_W = 960;
 static_assert(THREADS * RUN == TILE, "one lane per run of the mean");
@@ -51,10 +57,6 @@ static_assert(TILE % (4 * THREADS) == 0, "whole passes of 4 samples a lane");
 // floats of one of lim_apply_k's two LDS buffers: req over TILE + 4 W, or held over TILE + 2 W at word j + j / 16
 constexpr int apply_buf_floats(int W) { return (TILE + 4 * W + (TILE + 2 * W) / RUN + 4 + 3) / 4 * 4; }
 constexpr int MAX_APPLY_LDS = 2 * apply_buf_floats(MAX_W) * (int)sizeof(float);
-
-struct LimTaps {
-    float t[OS][KP];
-};
 
 struct LimLens {
     int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
@@ -98,28 +100,6 @@ struct ApplyArgs {
     int W;
     int nb;  // floats of one LDS buffer
 };
-
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
-
-template <typename TO>
-__device__ __forceinline__ TO from_float(float v);
-template <>
-__device__ __forceinline__ float from_float<float>(float v) {
-    return v;
-}
-// audio.hip's rule (viettts_amd/wavio.py float_to_pcm16): rint(clip(x, -1, 1) * 32767) in double, NaN -> 0
-template <>
-__device__ __forceinline__ short from_float<short>(float v) {
-    if (!(v == v)) return 0;
-    const float c = fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)c * 32767.0);
-}
-
-__device__ __forceinline__ float req_of(float p, float g, float c) {
-    const float gp = g * p;
-    return gp <= c ? 1.0f : c / gp;
-}
 
 template <typename TI>
 __global__ __launch_bounds__(THREADS) void lim_env_k(const EnvArgs a, const LimTaps tp, const LimLens rows) {
@@ -225,8 +205,6 @@ __global__ __launch_bounds__(THREADS) void lim_pregain_k(const float* integrated
     }
     gains[i] = g;
 }
-
-__device__ __forceinline__ int padded(int j) { return j + (j >> 4); }
 
 template <typename TI, typename TO>
 __global__ __launch_bounds__(THREADS) void lim_apply_k(const ApplyArgs a, const LimRows rows) {

@@ -12,7 +12,11 @@ waveforms from a 4x oversampled reconstruction, and a per-sample gain that keeps
 ``LoudnessMeter.normalize`` backs a whole row off for one plosive, this holds the plosive down and leaves the row at its gain.  The limited
 row is not metered again, so it ends a little under the target where the limiter worked.  The oversampling factor is 4 at every rate (a
 component at the Nyquist frequency reads up to 0.69 dB low).  No loudness range, no release shaping but the symmetric window, no multiband or
-soft knee, mono only, and the streamed paths are not hooked.  No CPU fallback: the kernels are the only implementation.
+soft knee, mono only.  No CPU fallback: the kernels are the only implementation.
+
+    with lim.open_stream(rows=4, max_chunk=8192, out_dtype="pcm16") as s:   # LimiterStream: the same bits, chunk by chunk, 2 W + 24 samples late
+        s.reset(0, gain=2.0)
+        pcm, counts = s.push(chunk, last=False, rows=[0])                   # include/vtts_limstream.h, viettts_amd/csrc/limiter_stream.hip
 """
 from __future__ import annotations
 
@@ -48,6 +52,7 @@ class TruePeakLimiter(NativeHandle):
 
     def __init__(self, sample_rate: int = 16000, device="cuda:0", lookahead_ms: float = 5.0, lib_path=None):
         super().__init__("vtts_limiter", device, lib_path, "limiter")
+        self._lib_path = lib_path
         self.sample_rate = int(sample_rate)
         self.lookahead_ms = float(lookahead_ms)
         self._create(C.byref(_lib.LimiterCfg(self.sample_rate, self.lookahead_ms)))  # refuses rates outside 8 .. 96 kHz, look-ahead outside (0, 10] ms
@@ -115,6 +120,106 @@ class TruePeakLimiter(NativeHandle):
         gains = torch.empty(N, dtype=torch.float32, device=self.device)
         self._on_stream("pregain", ptr(r.integrated), N, float(target), float(max_gain_db), ptr(gains))
         return self.limit(y, lengths, gains=gains, ceiling_dbtp=ceiling_dbtp, out_dtype=out_dtype, packed=packed)
+
+    def open_stream(self, rows: int, max_chunk: int, ceiling_dbtp: float = -1.0, out_dtype: str = "f32") -> "LimiterStream":
+        """A streamed session of this limiter's rate, look-ahead and device: ``rows`` independent row slots fed chunk by chunk
+        (:class:`LimiterStream`), each chunk of at most ``max_chunk`` samples."""
+        return LimiterStream(self.sample_rate, rows, max_chunk, self.device, self.lookahead_ms, ceiling_dbtp, out_dtype, lib_path=self._lib_path)
+
+
+def stream_emit(received: int, emitted: int, count: int, last: bool, W: int) -> int:
+    """The streamed limiter's emit rule (include/vtts_limstream.h): the emitted count after a push of ``count`` samples onto ``received``
+    of which ``emitted`` have left.  Whole runs of 16 whose look-ahead (2 W + 24 samples) has arrived; everything on ``last``."""
+    r = int(received) + int(count)
+    if last:
+        return r
+    return max(int(emitted), max(0, r - 2 * int(W) - 24) // _lib.LIMITER_RUN * _lib.LIMITER_RUN)
+
+
+class LimiterStream(NativeHandle):
+    """``TruePeakLimiter.limit`` fed chunk by chunk (include/vtts_limstream.h, viettts_amd/csrc/limiter_stream.hip): ``rows`` slots, each
+    with its own cursor and pre-gain.  For every row the concatenation of what its pushes return equals ``limit`` on the whole row with
+    ``gains[b] = gain``, bit for bit, and :meth:`results` after its last push equals ``limit``'s.  One launch per push for every row of it
+    (and one small merge of the results); asynchronous on torch's current stream.  A context manager."""
+
+    def __init__(self, sample_rate: int, rows: int, max_chunk: int, device="cuda:0", lookahead_ms: float = 5.0, ceiling_dbtp: float = -1.0,
+                 out_dtype: str = "f32", lib_path=None):
+        if out_dtype not in ("f32", "pcm16"):
+            raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
+        super().__init__("vtts_limstream", device, lib_path, "limiter stream")
+        self.sample_rate, self.rows, self.max_chunk, self.out_dtype = int(sample_rate), int(rows), int(max_chunk), out_dtype
+        self.ceiling_dbtp = float(ceiling_dbtp)
+        self._create(C.byref(_lib.LimiterCfg(self.sample_rate, float(lookahead_ms))), tail=(self.rows, self.max_chunk, self.ceiling_dbtp))
+        w = C.c_int32(0)
+        self._call("lookahead", C.byref(w))
+        self.lookahead = int(w.value)
+        self.latency = 2 * self.lookahead + 24  # samples a row's output trails its input by (plus up to 15: whole runs of 16 leave)
+        need = C.c_size_t(0)
+        self._call("state_bytes", C.byref(need))
+        self._state = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)  # (never cleared: nothing is read before a row's sample 0)
+        self._results = torch.zeros((self.rows, 3), dtype=torch.float32, device=self.device)
+        self._dummy = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        super().close()
+        self._state = self._results = self._dummy = None
+
+    def reset(self, row: int, gain: float = 1.0) -> None:
+        """Start a new row in slot ``row`` with the pre-gain ``gain`` (linear).  Host bookkeeping only."""
+        self._call("reset", int(row), float(gain))
+
+    def push(self, chunks, counts=None, last=False, rows=None):
+        """Feed ``chunks``: ``[n, C]`` (row i's first ``counts[i]`` samples, all C without ``counts``) or a packed 1-D tensor with ``counts``;
+        float32 or int16 on the device.  ``rows``: the slots, ``range(n)`` by default; ``last``: a bool or one per row.  Returns ``(packed,
+        counts)``: the emitted samples of every row back to back (float32 or int16) and how many each row emitted."""
+        if not isinstance(chunks, torch.Tensor):
+            chunks = torch.as_tensor(np.asarray(chunks))
+        if chunks.dtype not in (torch.float32, torch.int16):
+            raise ValueError("chunks must be float32 or int16")
+        chunks = chunks.to(self.device).contiguous()
+        if chunks.dim() == 2:
+            n, stride = int(chunks.shape[0]), int(chunks.shape[1])
+            counts = [stride] * n if counts is None else [int(c) for c in counts]
+            if len(counts) != n or (counts and max(counts) > stride):
+                raise ValueError("counts must hold one count per row, none above the chunk's width")
+            if stride == 0:  # (the C side reads a zero stride as packed, which an all-empty push is as well)
+                chunks = chunks.reshape(-1)
+        elif chunks.dim() == 1 and counts is not None:
+            counts = [int(c) for c in counts]
+            n, stride = len(counts), 0
+            if sum(counts) != chunks.numel():
+                raise ValueError("a packed push holds exactly sum(counts) samples")
+        else:
+            raise ValueError("chunks must be [n, C], or 1-D with counts")
+        rows = list(range(n)) if rows is None else [int(r) for r in rows]
+        lasts = [bool(last)] * n if isinstance(last, (bool, int, np.bool_)) else [bool(v) for v in last]
+        if len(rows) != n or len(lasts) != n:
+            raise ValueError("rows and last must hold one entry per row of the push")
+        if n < 1:
+            raise ValueError("a push names at least one row")
+        i32 = C.c_int32 * n
+        got = i32()
+        pcm = self.out_dtype == "pcm16"
+        room = sum(counts) + n * (self.latency + 15)
+        out = torch.empty(max(room, 1), dtype=torch.int16 if pcm else torch.float32, device=self.device)
+        src = chunks if chunks.numel() else self._dummy
+        self._on_stream("push", ptr(self._state), ptr(src), _lib.VTTS_AUDIO_PCM16 if chunks.dtype == torch.int16 else _lib.VTTS_AUDIO_F32, n, i32(*rows),
+                        stride, i32(*counts), i32(*[int(v) for v in lasts]), ptr(out), _lib.VTTS_AUDIO_PCM16 if pcm else _lib.VTTS_AUDIO_F32, got,
+                        ptr(self._results))
+        emitted = [int(v) for v in got]
+        return out[:sum(emitted)], emitted
+
+    def results(self) -> LimiterResult:
+        """Per slot, on the device: the running ``true_peak`` and ``min_gain`` over the samples emitted so far (``limit``'s after a row's last
+        push) and the pre-gain; ``envelope`` is None."""
+        r = self._results
+        return LimiterResult(r[:, 0], r[:, 1], r[:, 2], None)
 
 
 _LIMITERS: dict = {}

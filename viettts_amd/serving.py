@@ -116,10 +116,16 @@ class SpeechPool:
     """A speech server's inner loop on one GPU: ``submit`` requests at any time, call :meth:`step` (or iterate :meth:`drain`) and hand every
     ``(id, samples, last)`` to its listener.  ``slots`` requests are decoded at once, the rest wait FIFO; a request may have ``Lmax`` tokens and
     ``Fmax`` frames.  Chunks are ``chunk_frames`` kept frames, the first ``first_chunk_frames`` if given (``streaming.stream_plan``); samples are
-    int16 (``out_dtype="pcm16"``) or float32 host arrays, ``hop * T`` per request in all.  Work is enqueued on torch's current stream."""
+    int16 (``out_dtype="pcm16"``) or float32 host arrays, ``hop * T`` per request in all.  Work is enqueued on torch's current stream.
+
+    ``limit=True``: every request passes the streamed true-peak limiter (``viettts_amd.limiter.LimiterStream`` with one row per slot: a gain of
+    ``gain_db``, then a ceiling of ``ceiling_dbtp``), one push per round for all of the round's rows.  A request's samples are then
+    ``synthesize_stream``'s of it alone with the same three arguments; they leave ``LimiterStream.latency`` samples late, a row's chunks of one
+    round arrive as one part, and a part may be empty.  The limiter is designed for the models' rate (``FLAGS.sample_rate``)."""
 
     def __init__(self, duration_model, acoustic_model, generator, slots: int, Lmax: int, Fmax: int, chunk_frames: int = 32,
-                 first_chunk_frames: Optional[int] = None, out_dtype: str = "pcm16"):
+                 first_chunk_frames: Optional[int] = None, out_dtype: str = "pcm16", limit: bool = False, gain_db: float = 0.0,
+                 ceiling_dbtp: float = -1.0):
         _check_dtype(out_dtype)
         self.dm, self.am, self.gen, self.out_dtype = duration_model, acoustic_model, generator, out_dtype
         self.planner = RoundPlanner(slots, chunk_frames, first_chunk_frames)
@@ -128,6 +134,15 @@ class SpeechPool:
         self._req: Dict[int, tuple] = {}  # id -> (tokens, durations in frames, n_frames, seed) until admitted
         self._empty: List[int] = []  # requests with nothing to say (T < 1): answered by the next step
         self._pending = None  # the previous round's chunks on their way to the host
+        self.limiter = None
+        if limit:
+            from .limiter import default_limiter
+            from .nat.config import FLAGS
+
+            # a row's chunks of one round are one push: at most a window and the generator's halo (RoundPlanner.due)
+            self.limiter = default_limiter(generator.device, FLAGS.sample_rate).open_stream(
+                slots, generator.hop * (self.planner.max_window + HALO_FRAMES), ceiling_dbtp, out_dtype)
+            self._gain = float(np.float32(10.0 ** (float(gain_db) / 20.0)))
 
     def submit(self, tokens: Sequence[int], silence_duration: float = -1.0, dropout_seed: Optional[int] = 0) -> int:
         """Queue one sentence (token ids); the duration model runs now, the frame rules are text2mel's (``frame_plan``).  Returns the request's id."""
@@ -176,6 +191,8 @@ class SpeechPool:
             for rid, slot in pl.admissions():
                 toks, frames, n, seed = self._req.pop(rid)
                 pool.admit(slot, toks, frames, n, dropout_seed=seed)
+                if self.limiter is not None:
+                    self.limiter.reset(slot, self._gain)
             pool.decode(pl.chunk_frames)
             pl.advance(pl.chunk_frames)
             rnd = pl.due()
@@ -192,12 +209,23 @@ class SpeechPool:
                 # the kept samples of every chunk back to back, the halos cut as streaming._vocode cuts them
                 kept = [wav[q, hop * s.chunk.keep_from : hop * (s.chunk.keep_from + s.chunk.t1 - s.chunk.t0)] for q, (_, _, s, _) in enumerate(rnd.chunks)]
                 w = torch.cat(kept)
-                if self.out_dtype == "pcm16":
+                parts = [(rid, hop * (s.chunk.t1 - s.chunk.t0), last) for rid, _, s, last in rnd.chunks]
+                if self.limiter is not None:  # one push: a row's chunks of this round lie back to back in w and count as one
+                    rows, merged = [], []
+                    for (rid, count, last), (_, slot, _, _) in zip(parts, rnd.chunks):
+                        if rows and rows[-1] == slot:
+                            merged[-1] = (rid, merged[-1][1] + count, last)
+                        else:
+                            rows.append(slot)
+                            merged.append((rid, count, last))
+                    w, emitted = self.limiter.push(w, counts=[c for _, c, _ in merged], last=[z for _, _, z in merged], rows=rows)
+                    parts = [(rid, e, last) for (rid, _, last), e in zip(merged, emitted)]
+                elif self.out_dtype == "pcm16":
                     from .audio import to_pcm16
 
                     w = to_pcm16(w.contiguous())
                 host, landed = _copy_out(w, cur, s_copy)
-                nxt = (host, landed, [(rid, hop * (s.chunk.t1 - s.chunk.t0), last) for rid, _, s, last in rnd.chunks])
+                nxt = (host, landed, parts)
             for _, slot in rnd.retired:
                 pool.retire(slot)
         if self._pending is not None:
@@ -219,3 +247,6 @@ class SpeechPool:
         if self.pool is not None:
             self.pool.close()
             self.pool = None
+        if self.limiter is not None:
+            self.limiter.close()
+            self.limiter = None

@@ -80,15 +80,50 @@ def _vocode(generator, mel, chunk: Chunk, out_dtype: str):
     return w
 
 
+def _first(*tensors):
+    """Element 0 of each device tensor as a float: one read-back."""
+    import torch
+
+    return tuple(float(v) for v in torch.stack([t[0] for t in tensors]).tolist())
+
+
+class _Limited:
+    """The streamed true-peak limiter behind one sentence's vocoder chunks (``viettts_amd.limiter.LimiterStream``, one row): a fixed gain of
+    ``gain_db`` and a ceiling of ``ceiling_dbtp`` that holds while the sentence is still being decoded.  The limiter is the models' rate's
+    (``FLAGS.sample_rate``: the look-ahead in samples and the oversampling filter), as the un-streamed ``limit`` hooks'."""
+
+    def __init__(self, device, max_chunk: int, gain_db: float, ceiling_dbtp: float, out_dtype: str):
+        from .limiter import default_limiter
+        from .nat.config import FLAGS
+
+        self.stream = default_limiter(device, FLAGS.sample_rate).open_stream(1, max_chunk, ceiling_dbtp, out_dtype)
+        self.stream.reset(0, float(np.float32(10.0 ** (float(gain_db) / 20.0))))
+
+    def push(self, w, last: bool):
+        """The float32 chunk ``w`` on the device -> the samples that leave now, in the session's out_dtype."""
+        return self.stream.push(w, counts=[int(w.numel())], last=last)[0]
+
+    def summary(self) -> dict:
+        r = self.stream.results()
+        tp, mg, g = _first(r.true_peak, r.min_gain, r.gains)
+        return {"true_peak": tp, "min_gain": mg, "gain": g}
+
+    def close(self) -> None:
+        self.stream.close()
+
+
 def _check_dtype(out_dtype: str) -> None:
     if out_dtype not in ("f32", "pcm16"):
         raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
 
 
-def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32") -> Iterator[np.ndarray]:
+def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32", limit: bool = False,
+               gain_db: float = 0.0, ceiling_dbtp: float = -1.0) -> Iterator[np.ndarray]:
     """Vocoder-only streaming of a finished mel (``[T, num_mels]`` float32, host array or tensor): the chunks of :func:`stream_plan`, one generator
     call each, every chunk's read-back under the next chunk's compute.  Yields host arrays (float32, or int16 equal to ``wavio.float_to_pcm16``
-    of the float chunks); their concatenation has ``hop * T`` samples."""
+    of the float chunks); their concatenation has ``hop * T`` samples.  With ``limit=True`` every chunk passes the streamed true-peak limiter
+    (a gain of ``gain_db``, then a ceiling of ``ceiling_dbtp``) on the device: the samples are ``TruePeakLimiter.limit``'s of the whole
+    waveform bit for bit and leave ``LimiterStream.latency`` samples late, so the first chunk is shorter and the last one longer."""
     import torch
 
     from .pipeline import _copy_stream
@@ -104,19 +139,28 @@ def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optio
         return
     cur, s_copy = torch.cuda.current_stream(generator.device), _copy_stream(generator.device)
     pending = None
-    for step in stream_plan(T, T, chunk_frames, first_chunk_frames):
-        nxt = _copy_out(_vocode(generator, mel, step.chunk, out_dtype), cur, s_copy)
-        if pending is not None:
-            pending[1].synchronize()
-            yield pending[0].numpy()
-        pending = nxt
-    pending[1].synchronize()
-    yield pending[0].numpy()
+    plan = stream_plan(T, T, chunk_frames, first_chunk_frames)
+    lim = _Limited(generator.device, generator.hop * max(s.chunk.t1 - s.chunk.t0 for s in plan), gain_db, ceiling_dbtp, out_dtype) if limit else None
+    try:
+        for k, step in enumerate(plan):
+            w = _vocode(generator, mel, step.chunk, "f32" if limit else out_dtype)
+            if limit:
+                w = lim.push(w.contiguous(), k + 1 == len(plan))
+            nxt = _copy_out(w, cur, s_copy)
+            if pending is not None:
+                pending[1].synchronize()
+                yield pending[0].numpy()
+            pending = nxt
+        pending[1].synchronize()
+        yield pending[0].numpy()
+    finally:
+        if lim is not None:
+            lim.close()
 
 
 def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, generator, silence_duration: float = -1.0, dropout_seed: Optional[int] = 0,
                       dropout_rng=None, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32",
-                      info: Optional[dict] = None) -> Iterator[np.ndarray]:
+                      info: Optional[dict] = None, limit: bool = False, gain_db: float = 0.0, ceiling_dbtp: float = -1.0) -> Iterator[np.ndarray]:
     """A generator over the waveform of ONE sentence (token ids), chunk by chunk, in order: host arrays, float32 or (``out_dtype="pcm16"``) int16 equal
     to ``wavio.float_to_pcm16`` of the float chunks; ``256 * T`` samples in all, T = the frames text2mel keeps.  The frame rules are text2mel's
     (``frame_plan``: vietTTS/nat/text2mel.py:78-79, :90-102); dropout as ``predict_mel`` (``dropout_rng``: the reference's stream; else
@@ -125,7 +169,10 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
     Per step of :func:`stream_plan`: decoder up to ``decode_upto``, postnet up to ``mel_upto``, generator on ``mel[lo:hi]``, the kept samples (packed
     to PCM16 on the device if asked) to pinned memory on a copy stream; the NEXT step's decoder frames are enqueued before the host waits for this
     step's copy.  ``info`` (a dict) receives ``frames`` (T), ``n_frames`` and ``samples`` before the first chunk is yielded, and
-    ``frames_decoded_at_first_chunk``.  Work is enqueued on torch's current stream."""
+    ``frames_decoded_at_first_chunk``.  Work is enqueued on torch's current stream.
+
+    ``limit=True``: the vocoder's float32 chunk stays on the device and passes the streamed true-peak limiter (a gain of ``gain_db``, a ceiling of
+    ``ceiling_dbtp``: :func:`stream_mel`) before the copy; ``info["limiter"]`` receives ``true_peak``, ``min_gain`` and ``gain`` with the last chunk."""
     import torch
 
     from .nat import text2mel as t2m
@@ -145,20 +192,30 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
     kw = {"dropout_rng": dropout_rng} if dropout_rng is not None else {"dropout_seeds": None if dropout_seed is None else [dropout_seed]}
     dev = generator.device
     cur, s_copy = torch.cuda.current_stream(dev), _copy_stream(dev)
-    with acoustic_model.open_stream([toks], [frames[0]], [n], max(windows), **kw) as st:
-        st.decode(plan[0].decode_upto)
-        final = 0
-        for k, step in enumerate(plan):
-            if step.mel_upto > final:
-                st.finish(final, step.mel_upto)
-                final = step.mel_upto
-            host, landed = _copy_out(_vocode(generator, st.mel[0], step.chunk, out_dtype), cur, s_copy)
-            if info is not None and k == 0:
-                info["frames_decoded_at_first_chunk"] = st.frames_decoded
-            if k + 1 < len(plan):
-                st.decode(plan[k + 1].decode_upto)  # under this chunk's vocoder and copy
-            landed.synchronize()
-            yield host.numpy()
+    lim = _Limited(dev, generator.hop * max(s.chunk.t1 - s.chunk.t0 for s in plan), gain_db, ceiling_dbtp, out_dtype) if limit else None
+    try:
+        with acoustic_model.open_stream([toks], [frames[0]], [n], max(windows), **kw) as st:
+            st.decode(plan[0].decode_upto)
+            final = 0
+            for k, step in enumerate(plan):
+                if step.mel_upto > final:
+                    st.finish(final, step.mel_upto)
+                    final = step.mel_upto
+                w = _vocode(generator, st.mel[0], step.chunk, "f32" if limit else out_dtype)
+                if limit:
+                    w = lim.push(w.contiguous(), k + 1 == len(plan))
+                host, landed = _copy_out(w, cur, s_copy)
+                if info is not None and k == 0:
+                    info["frames_decoded_at_first_chunk"] = st.frames_decoded
+                if k + 1 < len(plan):
+                    st.decode(plan[k + 1].decode_upto)  # under this chunk's vocoder and copy
+                landed.synchronize()
+                if limit and info is not None and k + 1 == len(plan):
+                    info["limiter"] = lim.summary()
+                yield host.numpy()
+    finally:
+        if lim is not None:
+            lim.close()
 
 
 def stream_text(text: str, lexicon_fn=None, silence_duration: float = -1.0, **kw) -> Iterator[np.ndarray]:

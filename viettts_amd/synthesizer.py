@@ -58,6 +58,9 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--loudness", default=None, type=float, help="(extension) bring the clip to this BS.1770 integrated loudness in LUFS, on the GPU")
     p.add_argument("--limit", action="store_true", help="(extension) with --loudness: the full gain to the target and a look-ahead limiter under -1 dBTP "
                    "(viettts_amd.limiter) in place of the sample-peak cap")
+    p.add_argument("--ceiling-dbtp", default=None, type=float, help="(extension) with --stream: hold the true peak under this ceiling in dBTP, chunk by chunk "
+                   "(viettts_amd.limiter.LimiterStream)")
+    p.add_argument("--gain-db", default=None, type=float, help="(extension) with --stream --ceiling-dbtp: a fixed gain in dB ahead of the limiter")
     return p
 
 
@@ -71,6 +74,7 @@ def _stream(args) -> int:
     raw = str(args.output) == "-"
     say = (lambda *a: print(*a, file=sys.stderr)) if raw else print
     info = {}
+    lim = {} if args.ceiling_dbtp is None else {"limit": True, "gain_db": args.gain_db or 0.0, "ceiling_dbtp": args.ceiling_dbtp}
     if args.mel_file is not None:
         from .hifigan.mel2wave import _generator
 
@@ -78,11 +82,11 @@ def _stream(args) -> int:
         mel = mel[0] if mel.ndim == 3 else mel
         gen = _generator()
         info["samples"] = gen.hop * mel.shape[0]
-        chunks = stream_mel(gen, mel, args.chunk_frames, out_dtype="pcm16")
+        chunks = stream_mel(gen, mel, args.chunk_frames, out_dtype="pcm16", **lim)
     else:
         text = nat_normalize_text(args.text)
         say("Normalized text input:", text)
-        chunks = stream_text(text, args.lexicon_file, args.silence_duration, chunk_frames=args.chunk_frames, out_dtype="pcm16", info=info)
+        chunks = stream_text(text, args.lexicon_file, args.silence_duration, chunk_frames=args.chunk_frames, out_dtype="pcm16", info=info, **lim)
     first = next(chunks, None)  # (the text path knows its sample count once the duration model has run: before the first decoder frame)
     say("writing output to file", args.output)
     f = sys.stdout.buffer if raw else open(str(args.output), "wb")
@@ -104,6 +108,13 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     if args.limit and args.loudness is None:
         parser.error("--limit needs --loudness")
+    if not args.stream and (args.ceiling_dbtp is not None or args.gain_db is not None):
+        parser.error("--ceiling-dbtp and --gain-db belong to --stream; for a whole clip use --loudness T --limit")
+    if args.gain_db is not None and args.ceiling_dbtp is None:
+        parser.error("--gain-db needs --ceiling-dbtp")
+    if args.ceiling_dbtp is not None and args.sample_rate != FLAGS.sample_rate:
+        parser.error(f"--ceiling-dbtp with --sample-rate {args.sample_rate}: the streamed samples are the models' {FLAGS.sample_rate} Hz, and the limiter's "
+                     "look-ahead and oversampling filter are designed for that rate; a relabelled file would carry another true peak")
     if args.stream:  # argument errors before anything touches a device
         if args.resample:
             parser.error("--stream with --resample: a streamed resampler would need a filter state across chunks")
