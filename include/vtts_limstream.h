@@ -32,8 +32,8 @@
  * row), and one small kernel merges the tiles' maxima and minima into the results: two launches for up to 128 rows, whatever the counts;
  * more rows mean more launches of the same two kernels.  Nothing synchronises with the host.
  *
- * Out of scope: streamed loudness normalisation or any gain that depends on the utterance's own level, a streamed resampler, and
- * everything vtts_limiter.h leaves out.
+ * Out of scope: streamed loudness normalisation or any gain that depends on the utterance's own level, and everything vtts_limiter.h
+ * leaves out.  A streamed resampler is vtts_rsstream.h's: it takes this session's fp32 output chunk by chunk.
  *
  * Same conventions as vtts_limiter.h: plain pointers and sizes, 0 or a negative vtts_status (vtts_last_error() of vtts_hifigan.h), device
  * memory owned by the caller, asynchronous on the given stream.  The handle owns nothing on the device.

@@ -69,6 +69,8 @@ LIMITER_MIN_RATE, LIMITER_MAX_RATE = 8000, 96000  # include/vtts_limiter.h: VTTS
 LIMITER_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/limiter.hip: the rows whose lengths one launch carries
 LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
 LIMSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_limstream.h: VTTS_LIMSTREAM_ROWS_PER_LAUNCH
+RSSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_rsstream.h: VTTS_RSSTREAM_MAX_CHUNK
+RSSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_rsstream.h: VTTS_RSSTREAM_ROWS_PER_LAUNCH
 
 
 class MelCfg(C.Structure):
@@ -290,6 +292,21 @@ LIMSTREAM_SIGS = {
 }
 
 
+# include/vtts_rsstream.h, likewise
+RSSTREAM_SIGS = {
+    "vtts_rsstream_create": (C.c_int, [C.POINTER(AudioCfg), C.c_int, C.c_int, C.c_int32, C.POINTER(vp)]),
+    "vtts_rsstream_destroy": (None, [vp]),
+    "vtts_rsstream_ratio": (C.c_int, [vp, i32p, i32p, i32p]),
+    "vtts_rsstream_state_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "vtts_rsstream_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "vtts_rsstream_bind_packed": (C.c_int, [vp, vp, sz]),
+    "vtts_rsstream_reset": (C.c_int, [vp, C.c_int]),
+    "vtts_rsstream_cursor": (C.c_int, [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int)]),
+    "vtts_rsstream_emit": (C.c_int, [vp, i64, i64, C.c_int32, C.c_int, C.POINTER(i64)]),
+    "vtts_rsstream_push": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, i32p, i64, i32p, i32p, vp, C.c_int, i32p, vp]),
+}
+
+
 def _exports(*prefixes: str) -> tuple:
     return tuple(name for name in SIGS if name.startswith(prefixes))
 
@@ -305,6 +322,7 @@ LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
 LIMITER_EXPORTS = tuple(LIMITER_SIGS)  # include/vtts_limiter.h
 LIMSTREAM_EXPORTS = tuple(LIMSTREAM_SIGS)  # include/vtts_limstream.h
+RSSTREAM_EXPORTS = tuple(RSSTREAM_SIGS)  # include/vtts_rsstream.h
 
 
 def default_lib_path() -> Path:
@@ -358,7 +376,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

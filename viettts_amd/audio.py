@@ -4,6 +4,8 @@ conversion with a Kaiser-windowed sinc, and PCM16 in and out, one fused kernel.
     Resampler(48000, 16000, device)(wav)                      # [N, S] float32 or int16 -> [N, ceil(S / 3)] float32
     Resampler(16000, 44100, device)(wav, lengths, out_dtype="pcm16", packed=True)   # ragged rows, packed int16, ready for a WAV file
     to_pcm16(wav)                                             # wavio.float_to_pcm16 on the device, bit for bit
+    with Resampler(16000, 48000, device).open_stream(rows=4, max_chunk=8192, out_dtype="pcm16") as s:   # ResamplerStream: the same bits,
+        pcm, counts = s.push(chunk, last=False, rows=[0])     # chunk by chunk (include/vtts_rsstream.h, viettts_amd/csrc/resample_stream.hip)
 
 The reference has no such stage: it writes 16 kHz samples with ``sf.write`` and relabels them when asked for another rate.
 No CPU fallback: the input lives on (or is copied to) the GPU.
@@ -57,6 +59,7 @@ class Resampler(NativeHandle):
 
     def __init__(self, in_rate: int, out_rate: int, device="cuda:0", lib_path=None):
         super().__init__("vtts_audio", device, lib_path, "resampler")
+        self._lib_path = lib_path
         self.in_rate, self.out_rate = int(in_rate), int(out_rate)
         self._create(C.byref(_lib.AudioCfg(self.in_rate, self.out_rate)))
         L, M, half = C.c_int32(0), C.c_int32(0), C.c_int32(0)
@@ -103,6 +106,108 @@ class Resampler(NativeHandle):
         if not packed and max(outs) == 0:
             out = out[:, :0]
         return out[0] if one_row and not packed else out
+
+    def open_stream(self, rows: int, max_chunk: int, out_dtype: str = "f32") -> "ResamplerStream":
+        """A streamed session of this resampler's rates and device: ``rows`` independent row slots fed chunk by chunk
+        (:class:`ResamplerStream`), each chunk of at most ``max_chunk`` samples.  The session binds this resampler's tap table."""
+        return ResamplerStream(self, rows, max_chunk, out_dtype)
+
+
+def resample_emit(received: int, emitted: int, count: int, last: bool, L: int, M: int, half: int) -> int:
+    """The streamed resampler's emit rule (include/vtts_rsstream.h): the emitted count after a push of ``count`` samples onto ``received``
+    of which ``emitted`` have left.  The outputs whose newest input ``(m M + half) // L`` has arrived; ``ceil(R' L / M)`` on ``last``;
+    ``R'`` when the rates are equal (``L == M == 1``)."""
+    r = int(received) + int(count)
+    L, M, half = int(L), int(M), int(half)
+    if L == M:
+        return r
+    if last:
+        return -((-r * L) // M)
+    return max(int(emitted), 0, -((half - r * L) // M))
+
+
+class ResamplerStream(NativeHandle):
+    """``Resampler`` fed chunk by chunk (include/vtts_rsstream.h, viettts_amd/csrc/resample_stream.hip): ``rows`` slots, each with its own
+    cursor.  For every row the concatenation of what its pushes return equals the resampler on the whole row, bit for bit, ``latency``
+    input samples late.  One launch per push for every row of it; asynchronous on torch's current stream.  A context manager."""
+
+    def __init__(self, resampler: Resampler, rows: int, max_chunk: int, out_dtype: str = "f32"):
+        if out_dtype not in _DTYPES:
+            raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
+        super().__init__("vtts_rsstream", resampler.device, resampler._lib_path, "resampler stream")
+        self.in_rate, self.out_rate, self.rows, self.max_chunk, self.out_dtype = resampler.in_rate, resampler.out_rate, int(rows), int(max_chunk), out_dtype
+        self._create(C.byref(_lib.AudioCfg(self.in_rate, self.out_rate)), tail=(self.rows, self.max_chunk))
+        self.L, self.M, self.half = resampler.L, resampler.M, resampler.half
+        self.identity = self.in_rate == self.out_rate
+        self.latency = 0 if self.identity else -(-self.half // self.L)  # input samples a row's output trails its input by
+        if not self.identity:
+            if resampler._blob is None:  # the tap table goes to the device once
+                resampler._pack()
+            self.adopt_packed(resampler.packed_blob())
+        need = C.c_size_t(0)
+        self._call("state_bytes", C.byref(need))
+        self._state = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)  # (never cleared: nothing is read before a row's sample 0)
+        self._dummy = torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        super().close()
+        self._state = self._dummy = None
+
+    def reset(self, row: int) -> None:
+        """Start a new row in slot ``row``.  Host bookkeeping only."""
+        self._call("reset", int(row))
+
+    def cursor(self, row: int):
+        """``(received, emitted, closed)`` of slot ``row``, as the host holds them."""
+        r, f, c = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        self._call("cursor", int(row), C.byref(r), C.byref(f), C.byref(c))
+        return int(r.value), int(f.value), bool(c.value)
+
+    def push(self, chunks, counts=None, last=False, rows=None):
+        """Feed ``chunks``: ``[n, C]`` (row i's first ``counts[i]`` samples, all C without ``counts``) or a packed 1-D tensor with ``counts``;
+        float32 or int16 on the device.  ``rows``: the slots, ``range(n)`` by default; ``last``: a bool or one per row.  Returns ``(packed,
+        counts)``: the emitted samples of every row back to back (float32 or int16) and how many each row emitted."""
+        if not isinstance(chunks, torch.Tensor):
+            chunks = torch.as_tensor(np.asarray(chunks))
+        if chunks.dtype not in (torch.float32, torch.int16):
+            raise ValueError("chunks must be float32 or int16")
+        chunks = chunks.to(self.device).contiguous()
+        if chunks.dim() == 2:
+            n, stride = int(chunks.shape[0]), int(chunks.shape[1])
+            counts = [stride] * n if counts is None else [int(c) for c in counts]
+            if len(counts) != n or (counts and max(counts) > stride):
+                raise ValueError("counts must hold one count per row, none above the chunk's width")
+            if stride == 0:  # (the C side reads a zero stride as packed, which an all-empty push is as well)
+                chunks = chunks.reshape(-1)
+        elif chunks.dim() == 1 and counts is not None:
+            counts = [int(c) for c in counts]
+            n, stride = len(counts), 0
+            if sum(counts) != chunks.numel():
+                raise ValueError("a packed push holds exactly sum(counts) samples")
+        else:
+            raise ValueError("chunks must be [n, C], or 1-D with counts")
+        rows = list(range(n)) if rows is None else [int(r) for r in rows]
+        lasts = [bool(last)] * n if isinstance(last, (bool, int, np.bool_)) else [bool(v) for v in last]
+        if len(rows) != n or len(lasts) != n:
+            raise ValueError("rows and last must hold one entry per row of the push")
+        if n < 1:
+            raise ValueError("a push names at least one row")
+        i32 = C.c_int32 * n
+        got = i32()
+        tdt, code = _DTYPES[self.out_dtype]
+        room = sum(counts) if self.identity else sum((c * self.L + self.half) // self.M + 2 for c in counts)
+        out = torch.empty(max(room, 1), dtype=tdt, device=self.device)
+        src = chunks if chunks.numel() else self._dummy
+        self._on_stream("push", ptr(self._state), ptr(src), _lib.VTTS_AUDIO_PCM16 if chunks.dtype == torch.int16 else _lib.VTTS_AUDIO_F32, n, i32(*rows),
+                        stride, i32(*counts), i32(*[int(v) for v in lasts]), ptr(out), code, got)
+        emitted = [int(v) for v in got]
+        return out[:sum(emitted)], emitted
 
 
 _RESAMPLERS: dict = {}

@@ -28,6 +28,7 @@
 
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
+#include "audio_common.h"
 #include "audio_design.h"
 #include "vtts_internal.h"
 
@@ -35,6 +36,11 @@ using vtts::check_blob;
 using vtts::failf;
 using vtts::upload_blob;
 namespace ad = vtts_audio_design;
+using vtts_audio_dev::floor8;
+using vtts_audio_dev::from_float;
+using vtts_audio_dev::Phases;
+using vtts_audio_dev::span_outputs;
+using vtts_audio_dev::to_float;
 
 namespace {
 
@@ -58,27 +64,6 @@ struct AudioArgs {
     int vec_ok;          // input rows are 16-byte aligned: interior chunks take one 16-byte load
     int identity;        // in_rate == out_rate
 };
-
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
-
-// floor(a / 8) * 8, a may be negative
-__device__ __forceinline__ long long floor8(long long a) { return a & ~7LL; }
-
-template <typename TO>
-__device__ __forceinline__ TO from_float(float v);
-template <>
-__device__ __forceinline__ float from_float<float>(float v) {
-    return v;
-}
-// viettts_amd/wavio.py float_to_pcm16: rint(clip(x, -1, 1) * 32767) in double.  The product of a 24-bit and a 15-bit significand is exact
-// in double, so the only rounding is rint's (to nearest, ties to even).
-template <>
-__device__ __forceinline__ short from_float<short>(float v) {
-    if (!(v == v)) return 0;
-    const float c = fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)c * 32767.0);
-}
 
 template <typename TI, typename TO>
 __global__ __launch_bounds__(THREADS) void audio_resample_k(const AudioArgs a, const AudioRows rows) {
@@ -135,28 +120,8 @@ __global__ __launch_bounds__(THREADS) void audio_resample_k(const AudioArgs a, c
 
     // ---- 2./3. one fmaf chain per output, ascending n
     const int sbase = (int)(q0 - nb) - (a.kp4 - 1);  // >= 0: span index of x[q0 - (kp4 - 1)]
-    const int nq = a.kp4 >> 2;
-    const int nslots = (cnt + a.L - 1) / a.L * a.L;  // whole runs of L outputs: < OPB + L
-    for (int slot = tid; slot < nslots; slot += THREADS) {
-        const int run = slot / a.L, sl = slot - run * a.L;
-        const int i = run * a.L + sl * a.minv % a.L;  // sl * minv < 2048^2
-        if (i >= cnt) continue;
-        float acc = 0.0f;
-        if (i < live) {
-            const int p = p0 + sl < a.L ? p0 + sl : p0 + sl - a.L;  // = (p0 + i M) mod L
-            const int dq = (p0 + i * a.M) / a.L;                     // p0 + i M < L + OPB * M <= 2049 * 2048
-            const float* s = span + sbase + dq;
-            const float4* g = reinterpret_cast<const float4*>(a.table) + p;
-            for (int c = 0; c < nq; ++c) {
-                const float4 w = g[(size_t)c * a.L];
-                acc = fmaf(s[4 * c + 0], w.x, acc);
-                acc = fmaf(s[4 * c + 1], w.y, acc);
-                acc = fmaf(s[4 * c + 2], w.z, acc);
-                acc = fmaf(s[4 * c + 3], w.w, acc);
-            }
-        }
-        out[i] = from_float<TO>(acc);
-    }
+    const Phases ph = {a.table, a.L, a.M, a.kp4, a.minv};
+    span_outputs<TO>(ph, span, sbase, p0, cnt, live, out, tid, THREADS);
 }
 
 template <typename TI, typename TO>

@@ -121,11 +121,15 @@ class SpeechPool:
     ``limit=True``: every request passes the streamed true-peak limiter (``viettts_amd.limiter.LimiterStream`` with one row per slot: a gain of
     ``gain_db``, then a ceiling of ``ceiling_dbtp``), one push per round for all of the round's rows.  A request's samples are then
     ``synthesize_stream``'s of it alone with the same three arguments; they leave ``LimiterStream.latency`` samples late, a row's chunks of one
-    round arrive as one part, and a part may be empty.  The limiter is designed for the models' rate (``FLAGS.sample_rate``)."""
+    round arrive as one part, and a part may be empty.  The limiter is designed for the models' rate (``FLAGS.sample_rate``).
+
+    ``out_rate`` (other than the models' rate): every request's float32 samples, limited or not, then pass the streamed resampler
+    (``viettts_amd.audio.ResamplerStream`` with one row per slot), one push per round likewise: ``synthesize_stream``'s samples of the request
+    alone with the same ``out_rate``, ``out_samples(hop * T)`` in all."""
 
     def __init__(self, duration_model, acoustic_model, generator, slots: int, Lmax: int, Fmax: int, chunk_frames: int = 32,
                  first_chunk_frames: Optional[int] = None, out_dtype: str = "pcm16", limit: bool = False, gain_db: float = 0.0,
-                 ceiling_dbtp: float = -1.0):
+                 ceiling_dbtp: float = -1.0, out_rate: Optional[int] = None):
         _check_dtype(out_dtype)
         self.dm, self.am, self.gen, self.out_dtype = duration_model, acoustic_model, generator, out_dtype
         self.planner = RoundPlanner(slots, chunk_frames, first_chunk_frames)
@@ -134,15 +138,24 @@ class SpeechPool:
         self._req: Dict[int, tuple] = {}  # id -> (tokens, durations in frames, n_frames, seed) until admitted
         self._empty: List[int] = []  # requests with nothing to say (T < 1): answered by the next step
         self._pending = None  # the previous round's chunks on their way to the host
-        self.limiter = None
+        self.limiter = self.resampler = None
+        from .streaming import _converts
+
+        convert = _converts(out_rate)
+        # a row's chunks of one round are one push: at most a window and the generator's halo (RoundPlanner.due)
+        max_chunk = generator.hop * (self.planner.max_window + HALO_FRAMES)
         if limit:
             from .limiter import default_limiter
             from .nat.config import FLAGS
 
-            # a row's chunks of one round are one push: at most a window and the generator's halo (RoundPlanner.due)
-            self.limiter = default_limiter(generator.device, FLAGS.sample_rate).open_stream(
-                slots, generator.hop * (self.planner.max_window + HALO_FRAMES), ceiling_dbtp, out_dtype)
+            self.limiter = default_limiter(generator.device, FLAGS.sample_rate).open_stream(slots, max_chunk, ceiling_dbtp, "f32" if convert else out_dtype)
             self._gain = float(np.float32(10.0 ** (float(gain_db) / 20.0)))
+            max_chunk += self.limiter.latency + 15  # a row's last push also flushes the limiter's delay
+        if convert:
+            from .audio import resampler
+            from .nat.config import FLAGS
+
+            self.resampler = resampler(FLAGS.sample_rate, int(out_rate), generator.device).open_stream(slots, max_chunk, out_dtype)
 
     def submit(self, tokens: Sequence[int], silence_duration: float = -1.0, dropout_seed: Optional[int] = 0) -> int:
         """Queue one sentence (token ids); the duration model runs now, the frame rules are text2mel's (``frame_plan``).  Returns the request's id."""
@@ -193,6 +206,8 @@ class SpeechPool:
                 pool.admit(slot, toks, frames, n, dropout_seed=seed)
                 if self.limiter is not None:
                     self.limiter.reset(slot, self._gain)
+                if self.resampler is not None:
+                    self.resampler.reset(slot)
             pool.decode(pl.chunk_frames)
             pl.advance(pl.chunk_frames)
             rnd = pl.due()
@@ -210,7 +225,8 @@ class SpeechPool:
                 kept = [wav[q, hop * s.chunk.keep_from : hop * (s.chunk.keep_from + s.chunk.t1 - s.chunk.t0)] for q, (_, _, s, _) in enumerate(rnd.chunks)]
                 w = torch.cat(kept)
                 parts = [(rid, hop * (s.chunk.t1 - s.chunk.t0), last) for rid, _, s, last in rnd.chunks]
-                if self.limiter is not None:  # one push: a row's chunks of this round lie back to back in w and count as one
+                tails = [t for t in (self.limiter, self.resampler) if t is not None]
+                if tails:  # one push each: a row's chunks of this round lie back to back in w and count as one
                     rows, merged = [], []
                     for (rid, count, last), (_, slot, _, _) in zip(parts, rnd.chunks):
                         if rows and rows[-1] == slot:
@@ -218,8 +234,10 @@ class SpeechPool:
                         else:
                             rows.append(slot)
                             merged.append((rid, count, last))
-                    w, emitted = self.limiter.push(w, counts=[c for _, c, _ in merged], last=[z for _, _, z in merged], rows=rows)
-                    parts = [(rid, e, last) for (rid, _, last), e in zip(merged, emitted)]
+                    parts = merged
+                    for tail in tails:
+                        w, emitted = tail.push(w, counts=[c for _, c, _ in parts], last=[z for _, _, z in parts], rows=rows)
+                        parts = [(rid, e, last) for (rid, _, last), e in zip(parts, emitted)]
                 elif self.out_dtype == "pcm16":
                     from .audio import to_pcm16
 
@@ -250,3 +268,6 @@ class SpeechPool:
         if self.limiter is not None:
             self.limiter.close()
             self.limiter = None
+        if self.resampler is not None:
+            self.resampler.close()
+            self.resampler = None

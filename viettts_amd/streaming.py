@@ -112,18 +112,64 @@ class _Limited:
         self.stream.close()
 
 
+class _Resampled:
+    """The streamed resampler behind one sentence's chunks (``viettts_amd.audio.ResamplerStream``, one row): the models' rate
+    (``FLAGS.sample_rate``) to ``out_rate``, ``Resampler`` on the whole waveform bit for bit, ``latency`` input samples late."""
+
+    def __init__(self, device, max_chunk: int, out_rate: int, out_dtype: str):
+        from .audio import resampler
+        from .nat.config import FLAGS
+
+        self.resampler = resampler(FLAGS.sample_rate, out_rate, device)
+        self.stream = self.resampler.open_stream(1, max_chunk, out_dtype)
+
+    def push(self, w, last: bool):
+        """The float32 chunk ``w`` on the device -> the samples that leave now, in the session's out_dtype."""
+        return self.stream.push(w, counts=[int(w.numel())], last=last)[0]
+
+    def close(self) -> None:
+        self.stream.close()
+
+
+def _converts(out_rate: Optional[int]) -> bool:
+    """Does ``out_rate`` ask for a conversion?  None and the models' own rate do not: those calls are the calls without the argument."""
+    if out_rate is None:
+        return False
+    from .nat.config import FLAGS
+
+    if int(out_rate) < 1:
+        raise ValueError(f"out_rate must be positive, got {out_rate!r}")
+    return int(out_rate) != FLAGS.sample_rate
+
+
+def _tail(device, max_chunk: int, out_dtype: str, limit: bool, gain_db: float, ceiling_dbtp: float, out_rate: Optional[int]):
+    """The un-streamed pipeline's order behind the vocoder's float32 chunks: (limiter, float32 out) -> (resampler, ``out_dtype``).  Returns
+    ``(limiter or None, resampler or None)``; with neither the vocoder's chunk leaves as it did."""
+    rs = _converts(out_rate)
+    lim = _Limited(device, max_chunk, gain_db, ceiling_dbtp, "f32" if rs else out_dtype) if limit else None
+    try:  # a limiter's last push also flushes its delay
+        res = _Resampled(device, max_chunk + (lim.stream.latency + 15 if lim else 0), int(out_rate), out_dtype) if rs else None
+    except Exception:
+        if lim is not None:
+            lim.close()
+        raise
+    return lim, res
+
+
 def _check_dtype(out_dtype: str) -> None:
     if out_dtype not in ("f32", "pcm16"):
         raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
 
 
 def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32", limit: bool = False,
-               gain_db: float = 0.0, ceiling_dbtp: float = -1.0) -> Iterator[np.ndarray]:
+               gain_db: float = 0.0, ceiling_dbtp: float = -1.0, out_rate: Optional[int] = None) -> Iterator[np.ndarray]:
     """Vocoder-only streaming of a finished mel (``[T, num_mels]`` float32, host array or tensor): the chunks of :func:`stream_plan`, one generator
     call each, every chunk's read-back under the next chunk's compute.  Yields host arrays (float32, or int16 equal to ``wavio.float_to_pcm16``
     of the float chunks); their concatenation has ``hop * T`` samples.  With ``limit=True`` every chunk passes the streamed true-peak limiter
     (a gain of ``gain_db``, then a ceiling of ``ceiling_dbtp``) on the device: the samples are ``TruePeakLimiter.limit``'s of the whole
-    waveform bit for bit and leave ``LimiterStream.latency`` samples late, so the first chunk is shorter and the last one longer."""
+    waveform bit for bit and leave ``LimiterStream.latency`` samples late, so the first chunk is shorter and the last one longer.  With
+    ``out_rate`` (other than the models' rate) every chunk then passes the streamed resampler (``viettts_amd.audio.ResamplerStream``): the
+    samples are ``Resampler(models' rate, out_rate)``'s of the whole (limited) float32 waveform bit for bit, ``out_samples(hop * T)`` in all."""
     import torch
 
     from .pipeline import _copy_stream
@@ -140,12 +186,14 @@ def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optio
     cur, s_copy = torch.cuda.current_stream(generator.device), _copy_stream(generator.device)
     pending = None
     plan = stream_plan(T, T, chunk_frames, first_chunk_frames)
-    lim = _Limited(generator.device, generator.hop * max(s.chunk.t1 - s.chunk.t0 for s in plan), gain_db, ceiling_dbtp, out_dtype) if limit else None
+    lim, res = _tail(generator.device, generator.hop * max(s.chunk.t1 - s.chunk.t0 for s in plan), out_dtype, limit, gain_db, ceiling_dbtp, out_rate)
     try:
         for k, step in enumerate(plan):
-            w = _vocode(generator, mel, step.chunk, "f32" if limit else out_dtype)
-            if limit:
+            w = _vocode(generator, mel, step.chunk, "f32" if lim or res else out_dtype)
+            if lim is not None:
                 w = lim.push(w.contiguous(), k + 1 == len(plan))
+            if res is not None:
+                w = res.push(w.contiguous(), k + 1 == len(plan))
             nxt = _copy_out(w, cur, s_copy)
             if pending is not None:
                 pending[1].synchronize()
@@ -154,13 +202,15 @@ def stream_mel(generator, mel, chunk_frames: int = 32, first_chunk_frames: Optio
         pending[1].synchronize()
         yield pending[0].numpy()
     finally:
-        if lim is not None:
-            lim.close()
+        for t in (lim, res):
+            if t is not None:
+                t.close()
 
 
 def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, generator, silence_duration: float = -1.0, dropout_seed: Optional[int] = 0,
                       dropout_rng=None, chunk_frames: int = 32, first_chunk_frames: Optional[int] = None, out_dtype: str = "f32",
-                      info: Optional[dict] = None, limit: bool = False, gain_db: float = 0.0, ceiling_dbtp: float = -1.0) -> Iterator[np.ndarray]:
+                      info: Optional[dict] = None, limit: bool = False, gain_db: float = 0.0, ceiling_dbtp: float = -1.0,
+                      out_rate: Optional[int] = None) -> Iterator[np.ndarray]:
     """A generator over the waveform of ONE sentence (token ids), chunk by chunk, in order: host arrays, float32 or (``out_dtype="pcm16"``) int16 equal
     to ``wavio.float_to_pcm16`` of the float chunks; ``256 * T`` samples in all, T = the frames text2mel keeps.  The frame rules are text2mel's
     (``frame_plan``: vietTTS/nat/text2mel.py:78-79, :90-102); dropout as ``predict_mel`` (``dropout_rng``: the reference's stream; else
@@ -172,7 +222,10 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
     ``frames_decoded_at_first_chunk``.  Work is enqueued on torch's current stream.
 
     ``limit=True``: the vocoder's float32 chunk stays on the device and passes the streamed true-peak limiter (a gain of ``gain_db``, a ceiling of
-    ``ceiling_dbtp``: :func:`stream_mel`) before the copy; ``info["limiter"]`` receives ``true_peak``, ``min_gain`` and ``gain`` with the last chunk."""
+    ``ceiling_dbtp``: :func:`stream_mel`) before the copy; ``info["limiter"]`` receives ``true_peak``, ``min_gain`` and ``gain`` with the last chunk.
+
+    ``out_rate`` (other than the models' rate): the float32 chunk, limited or not, passes the streamed resampler before the copy
+    (:func:`stream_mel`); ``info["samples"]`` is then ``out_samples(hop * T)``.  ``info["sample_rate"]`` is the rate of what is yielded."""
     import torch
 
     from .nat import text2mel as t2m
@@ -183,8 +236,14 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
     secs = duration_model([toks])
     frames, nfr, trail = t2m.frame_plan([toks], secs, silence_duration)
     n, T = nfr[0], nfr[0] - trail[0]
+    samples, rate = generator.hop * max(T, 0), t2m.FLAGS.sample_rate
+    if _converts(out_rate):
+        from math import gcd
+
+        g = gcd(rate, int(out_rate))
+        samples, rate = -(-samples * (int(out_rate) // g) // (rate // g)), int(out_rate)  # include/vtts_audio.h: ceil(S L / M)
     if info is not None:
-        info.update(frames=max(T, 0), n_frames=n, samples=generator.hop * max(T, 0))
+        info.update(frames=max(T, 0), n_frames=n, samples=samples, sample_rate=rate)
     if n < 1 or T < 1:
         return
     plan = stream_plan(T, n, chunk_frames, first_chunk_frames)
@@ -192,7 +251,7 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
     kw = {"dropout_rng": dropout_rng} if dropout_rng is not None else {"dropout_seeds": None if dropout_seed is None else [dropout_seed]}
     dev = generator.device
     cur, s_copy = torch.cuda.current_stream(dev), _copy_stream(dev)
-    lim = _Limited(dev, generator.hop * max(s.chunk.t1 - s.chunk.t0 for s in plan), gain_db, ceiling_dbtp, out_dtype) if limit else None
+    lim, res = _tail(dev, generator.hop * max(s.chunk.t1 - s.chunk.t0 for s in plan), out_dtype, limit, gain_db, ceiling_dbtp, out_rate)
     try:
         with acoustic_model.open_stream([toks], [frames[0]], [n], max(windows), **kw) as st:
             st.decode(plan[0].decode_upto)
@@ -201,9 +260,11 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
                 if step.mel_upto > final:
                     st.finish(final, step.mel_upto)
                     final = step.mel_upto
-                w = _vocode(generator, st.mel[0], step.chunk, "f32" if limit else out_dtype)
-                if limit:
+                w = _vocode(generator, st.mel[0], step.chunk, "f32" if lim or res else out_dtype)
+                if lim is not None:
                     w = lim.push(w.contiguous(), k + 1 == len(plan))
+                if res is not None:
+                    w = res.push(w.contiguous(), k + 1 == len(plan))
                 host, landed = _copy_out(w, cur, s_copy)
                 if info is not None and k == 0:
                     info["frames_decoded_at_first_chunk"] = st.frames_decoded
@@ -214,13 +275,14 @@ def synthesize_stream(tokens: Sequence[int], duration_model, acoustic_model, gen
                     info["limiter"] = lim.summary()
                 yield host.numpy()
     finally:
-        if lim is not None:
-            lim.close()
+        for t in (lim, res):
+            if t is not None:
+                t.close()
 
 
-def stream_text(text: str, lexicon_fn=None, silence_duration: float = -1.0, **kw) -> Iterator[np.ndarray]:
+def stream_text(text: str, lexicon_fn=None, silence_duration: float = -1.0, out_rate: Optional[int] = None, **kw) -> Iterator[np.ndarray]:
     """:func:`synthesize_stream` from text, through the models ``viettts_amd.nat.text2mel`` and ``viettts_amd.hifigan.mel2wave`` cache (the
-    checkpoints under the CWD, as the reference reads them); the dropout stream is ``predict_mel``'s."""
+    checkpoints under the CWD, as the reference reads them); the dropout stream is ``predict_mel``'s.  ``out_rate``: as there."""
     from .hifigan.mel2wave import _generator
     from .nat import text2mel as t2m
 
@@ -228,4 +290,4 @@ def stream_text(text: str, lexicon_fn=None, silence_duration: float = -1.0, **kw
     am = t2m.acoustic_model()
     if "dropout_rng" not in kw and getattr(am, "checkpoint_rng", None) is not None:
         kw["dropout_rng"] = am.checkpoint_rng
-    return synthesize_stream(tokens, t2m.duration_model(), am, _generator(), silence_duration, **kw)
+    return synthesize_stream(tokens, t2m.duration_model(), am, _generator(), silence_duration, out_rate=out_rate, **kw)

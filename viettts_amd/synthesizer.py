@@ -10,7 +10,8 @@ mel->waveform path can be driven on its own (the text path runs the NAT duration
 (``viettts_amd.audio.Resampler``) where the reference, and this CLI without the flag, only label the 16 kHz samples with R, and ``--stream``
 writes the output chunk by chunk while the acoustic decoder is still running (``viettts_amd.streaming``): the WAV header first — the sample count
 is known before the first decoder frame — then PCM16 per chunk of ``--chunk-frames`` mel frames, flushed; ``--output -`` writes the raw PCM16 to
-stdout (the two printed lines go to stderr then).
+stdout (the two printed lines go to stderr then); ``--stream --output-rate R`` converts the streamed samples to R chunk by chunk
+(``viettts_amd.audio.ResamplerStream``), the header carrying R and the converted count.
 
     python -m viettts_amd.synthesizer --text "..." --output clip.wav --lexicon-file assets/infore/lexicon.txt
 """
@@ -61,6 +62,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--ceiling-dbtp", default=None, type=float, help="(extension) with --stream: hold the true peak under this ceiling in dBTP, chunk by chunk "
                    "(viettts_amd.limiter.LimiterStream)")
     p.add_argument("--gain-db", default=None, type=float, help="(extension) with --stream --ceiling-dbtp: a fixed gain in dB ahead of the limiter")
+    p.add_argument("--output-rate", default=None, type=int, help="(extension) with --stream: convert the samples to this rate on the GPU, chunk by chunk "
+                   "(viettts_amd.audio.ResamplerStream); the header carries it")
     return p
 
 
@@ -75,6 +78,9 @@ def _stream(args) -> int:
     say = (lambda *a: print(*a, file=sys.stderr)) if raw else print
     info = {}
     lim = {} if args.ceiling_dbtp is None else {"limit": True, "gain_db": args.gain_db or 0.0, "ceiling_dbtp": args.ceiling_dbtp}
+    rate = args.sample_rate
+    if args.output_rate is not None:  # (main() has checked that --sample-rate is the models' then)
+        lim["out_rate"] = rate = args.output_rate
     if args.mel_file is not None:
         from .hifigan.mel2wave import _generator
 
@@ -82,6 +88,11 @@ def _stream(args) -> int:
         mel = mel[0] if mel.ndim == 3 else mel
         gen = _generator()
         info["samples"] = gen.hop * mel.shape[0]
+        if args.output_rate is not None:
+            from math import gcd
+
+            g = gcd(FLAGS.sample_rate, rate)
+            info["samples"] = -(-info["samples"] * (rate // g) // (FLAGS.sample_rate // g))  # include/vtts_audio.h: ceil(S L / M)
         chunks = stream_mel(gen, mel, args.chunk_frames, out_dtype="pcm16", **lim)
     else:
         text = nat_normalize_text(args.text)
@@ -92,7 +103,7 @@ def _stream(args) -> int:
     f = sys.stdout.buffer if raw else open(str(args.output), "wb")
     try:
         if not raw:
-            f.write(wav_header_pcm16(info["samples"], args.sample_rate))
+            f.write(wav_header_pcm16(info["samples"], rate))
         while first is not None:
             f.write(first.astype("<i2", copy=False).tobytes())
             f.flush()
@@ -115,9 +126,17 @@ def main(argv=None) -> int:
     if args.ceiling_dbtp is not None and args.sample_rate != FLAGS.sample_rate:
         parser.error(f"--ceiling-dbtp with --sample-rate {args.sample_rate}: the streamed samples are the models' {FLAGS.sample_rate} Hz, and the limiter's "
                      "look-ahead and oversampling filter are designed for that rate; a relabelled file would carry another true peak")
+    if args.output_rate is not None:
+        if not args.stream:
+            parser.error("--output-rate belongs to --stream; for a whole clip use --sample-rate R --resample")
+        if args.output_rate < 1:
+            parser.error("--output-rate must be positive")
+        if args.sample_rate != FLAGS.sample_rate:
+            parser.error(f"--output-rate with --sample-rate {args.sample_rate}: the streamed samples are the models' {FLAGS.sample_rate} Hz and --output-rate "
+                         "converts them; leave --sample-rate alone")
     if args.stream:  # argument errors before anything touches a device
         if args.resample:
-            parser.error("--stream with --resample: a streamed resampler would need a filter state across chunks")
+            parser.error("--stream with --resample: --resample converts a whole clip; a stream converts chunk by chunk with --output-rate R")
         if args.low_latency:
             parser.error("--stream with --low-latency: a streamed decoder runs the per-frame launches, not the resident kernel")
         if args.loudness is not None:
