@@ -8,12 +8,16 @@ The bar, for every input and over EVERY element of the output:
 fused multiply-add chain in ascending n) on that input; it is never taken from the kernel under test.  The second term is two fp32
 ulps at the largest output.  PCM16 output has conditions of its own (below).
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
 
 import _audio_oracle as oracle
+import _row_split as RS
 from viettts_amd import _lib, wavio
+from viettts_amd._handle import ptr
 
 pytestmark = pytest.mark.gpu
 OPB = _lib.AUDIO_OUT_PER_BLOCK
@@ -158,6 +162,71 @@ def test_ragged_packed_and_pcm_input_are_the_same_bits(rs, dev, rates):
         assert np.array_equal(strided[0], xf[0]) and np.array_equal(_host(r(pcm, out_dtype="pcm16")), pcm)  # the same format on both sides: copies
     else:
         assert np.array_equal(_host(r(pcm, lengths=lengths, out_dtype="pcm16")), p_str)
+
+
+def _run_prefilled(r, x, lengths, out_dtype="f32", packed=False):
+    """forward() through the C ABI into an output pre-filled with NaN (f32) or 12345 (PCM16): what no launch writes shows.  Packed outputs
+    carry eight spare elements, which must keep the fill."""
+    xt = torch.from_numpy(np.array(x)).to(r.device)  # (a copy: the shared rows are read-only)
+    N, S = xt.shape
+    outs = r.out_lengths(lengths)
+    tdt, code, fill = (torch.int16, _lib.VTTS_AUDIO_PCM16, 12345) if out_dtype == "pcm16" else (torch.float32, _lib.VTTS_AUDIO_F32, float("nan"))
+    out = torch.full((sum(outs) + 8,) if packed else (N, max(outs)), fill, dtype=tdt, device=r.device)
+    if r._blob is None:
+        r._pack()
+    in_code = _lib.VTTS_AUDIO_PCM16 if xt.dtype == torch.int16 else _lib.VTTS_AUDIO_F32
+    r._on_stream("forward", ptr(xt), in_code, N, S, (C.c_int32 * N)(*lengths), ptr(out), code, 0 if packed else max(outs))
+    got = _host(out)
+    if packed:
+        assert np.all(got[-8:] == 12345) if out_dtype == "pcm16" else np.isnan(got[-8:]).all()
+        got = got[:-8]
+    return got
+
+
+def test_rows_behind_the_launch_split_against_the_oracle(rs):
+    """AUDIO_ROWS_PER_LAUNCH + 3 rows at 16 -> 24 kHz (tests/_row_split.py): the rows behind the split differ from the first rows in content
+    and length and hold the longest row and an empty one.  Strided f32: every row against the fp64 oracle at the module's bar (once per
+    distinct row), zeros past its count, and the rows at both ends of the split bit for bit the row alone.  Packed f32 is the strided rows
+    back to back; PCM16 out, strided and packed, is float_to_pcm16 of them and within one step of the oracle's PCM, at most 1 % off it."""
+    rates = (16000, 24000)
+    bt = RS.audio_batch(_lib.AUDIO_ROWS_PER_LAUNCH)
+    assert bt.N == _lib.AUDIO_ROWS_PER_LAUNCH + 3
+    r = rs(*rates)
+    counts = r.out_lengths(bt.lengths)
+
+    def ref(row):
+        if row.length == 0:
+            return np.zeros(0), 0.0
+        x = row.content[: row.length]
+        want = oracle.resample(x, *rates)
+        return want, float(np.abs(oracle.resample(x, *rates, dtype=np.float32).astype(np.float64) - want).max())
+
+    refs = RS.per_kind(bt, ref)
+    strided = _run_prefilled(r, bt.rows, bt.lengths)
+    assert strided.shape == (bt.N, r.out_samples(max(bt.lengths[bt.P :]))) and not np.isnan(strided).any()
+    worst = {False: 0.0, True: 0.0}
+    for b, (n, (want, e32)) in enumerate(zip(counts, refs)):
+        assert want.shape == (n,) and np.all(strided[b, n:] == 0), b
+        if n:
+            err, bar = float(np.abs(strided[b, :n].astype(np.float64) - want).max()), _bar(e32, want)
+            worst[b >= bt.P] = max(worst[b >= bt.P], err / bar)
+            assert err <= bar, (b, err, bar)
+    for b in list(range(bt.k)) + list(bt.behind()):
+        if counts[b]:
+            assert np.array_equal(_host(r(bt.rows[b, : bt.lengths[b]].copy())), strided[b, : counts[b]]), b
+    print(f"\naudio rows across the split: worst error / bar {worst[False]:.3f} before, {worst[True]:.3f} behind the split")
+    flat = np.concatenate([strided[b, :n] for b, n in enumerate(counts)])
+    assert np.array_equal(_run_prefilled(r, bt.rows, bt.lengths, packed=True).view(np.uint32), flat.view(np.uint32))
+    p_str = _run_prefilled(r, bt.rows, bt.lengths, "pcm16")
+    assert p_str.dtype == np.int16 and np.array_equal(p_str, wavio.float_to_pcm16(strided))
+    assert np.array_equal(_run_prefilled(r, bt.rows, bt.lengths, "pcm16", packed=True), wavio.float_to_pcm16(flat))
+    off = np.abs(wavio.float_to_pcm16(flat).astype(np.int32) - wavio.float_to_pcm16(np.concatenate([w for w, _ in refs])).astype(np.int32))
+    print(f"PCM16 out: {100.0 * np.count_nonzero(off) / off.size:.3f} % of {off.size} samples differ from the oracle's PCM, max {off.max()} step")
+    assert off.max() <= 1 and np.count_nonzero(off) <= 0.01 * off.size
+    # the same batch at equal rates: copies of every row's own samples, through the same host loop
+    same = _run_prefilled(rs(16000, 16000), bt.rows, bt.lengths)
+    for b, n in enumerate(bt.lengths):
+        assert np.array_equal(same[b, :n].view(np.uint32), bt.rows[b, :n].view(np.uint32)) and np.all(same[b, n:] == 0), b
 
 
 def test_an_adopted_blob_gives_the_same_bits(rs, dev):

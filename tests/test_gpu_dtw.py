@@ -4,12 +4,16 @@ compared with ==: the contract fixes every fp32 operation and its order, so ther
 
 Sizes come from the header's constants: for every tile / strip / code-word size S the lengths 1, 2, S - 1, S, S + 1, 2 S - 1, 2 S, 2 S + 1.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
 
 import _dtw_oracle as O
-from viettts_amd import align
+import _row_split as RS
+from viettts_amd import _lib, align
+from viettts_amd._handle import ptr
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -131,6 +135,39 @@ def test_sliced_batch_equals_the_unsliced_one(dtws):
     for x, y in zip(whole, _host(two.dtw(a, b, las, lbs))):
         assert np.array_equal(x, y)
     _assert_equal(whole, 2, O.dtw_f32(a[2, :33], b[2, :17]), 33, "row 2")
+
+
+def _run_prefilled(d, a, b, las, lbs):
+    """forward() through the C ABI, the whole batch in ONE call, into outputs pre-filled with NaN / -7: what no launch writes shows."""
+    at, bt_ = (torch.from_numpy(np.array(x)).to(d.device) for x in (a, b))  # (copies: the shared rows are read-only)
+    N, Ta, Tb = at.shape[0], at.shape[1], bt_.shape[1]
+    total = torch.full((N,), float("nan"), dtype=torch.float32, device=d.device)
+    path_len = torch.full((N,), -7, dtype=torch.int32, device=d.device)
+    span = torch.full((N, Ta, 2), -7, dtype=torch.int32, device=d.device)
+    ws = d._workspace(d.workspace_bytes(N, Ta, Tb)).fill_(0xFF)
+    d._on_stream("forward", ptr(at), ptr(bt_), N, Ta, Tb, (C.c_int32 * N)(*las), (C.c_int32 * N)(*lbs), ptr(total), ptr(path_len), ptr(span), ptr(ws), ws.numel())
+    torch.cuda.synchronize()
+    return total.cpu().numpy(), path_len.cpu().numpy(), span.cpu().numpy()
+
+
+@pytest.mark.parametrize("band", [0, RS.DTW_NARROW_BAND])
+def test_pairs_behind_the_launch_split_against_the_oracle(dtws, band):
+    """DTW_PAIRS_PER_LAUNCH + 3 pairs (tests/_row_split.py) in one forward(): the pairs behind the split differ from the first ones in a, in b
+    and in both lengths, and hold the longest a and b, a 1 x n and an n x 1 pair.  total, path_len and the whole span of every pair == dtw_f32
+    (once per distinct pair); each pair behind the split is that pair run alone."""
+    bt = RS.dtw_batch(_lib.DTW_PAIRS_PER_LAUNCH)
+    a, b, las, lbs = RS.dtw_pairs(bt)
+    assert bt.N == _lib.DTW_PAIRS_PER_LAUNCH + 3 and a.shape[2] == 8
+    d = dtws(8, band)
+    want = RS.per_kind(bt, lambda r: O.dtw_f32(r.content[: r.length // 64], r.content[a.shape[1] : a.shape[1] + r.length % 64], band))
+    got = _run_prefilled(d, a, b, las, lbs)
+    for n in range(bt.N):
+        assert np.isfinite(want[n][0])
+        _assert_equal(got, n, want[n], las[n], (n, las[n], lbs[n], band))
+    for n in bt.behind():
+        alone = _host(d.dtw(np.array(a[n, : las[n]]), np.array(b[n, : lbs[n]])))
+        assert alone[0][0] == got[0][n] and alone[1][0] == got[1][n] and np.array_equal(alone[2][0], got[2][n, : las[n]]), n
+    print(f"\ndtw pairs behind the split, band {band}: {bt.k} pairs ==, worst error / bar 0 (the contract is ==)")
 
 
 def test_planted_warp_recovers_token_frame_counts(dtws):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _limiter_oracle as O
+import _row_split as RS
 from viettts_amd import _lib, wavio
 from viettts_amd._handle import ptr
 
@@ -210,21 +211,38 @@ def test_a_row_gives_the_same_bits_however_it_arrives(dev, batch):
     assert np.array_equal(y0.view(np.uint32), y1.view(np.uint32)) and np.array_equal(mg0, mg1) and np.all(gu0 == 1.0) and np.all(gu1 == 1.0)
 
 
-def test_rows_across_the_launch_split_are_the_rows_before_it(dev):
-    """The lengths of 128 rows travel with one launch: row 128 + b of a 131-row batch is row b."""
+def test_rows_across_the_launch_split_are_the_rows_before_it(dev, reference):
+    """The lengths of 128 rows travel with one launch.  Rows 128 + b of the batch of tests/_row_split.py differ from rows b in content, length
+    and gain and hold the longest row and a one-sample row: EVERY row, the fillers included, is compared with the float64 oracle of that row
+    as test_ragged_batch_agrees_with_the_float64_oracle does (samples, min gain, true peak, envelope, gain used).  Three more rows behind
+    them are rows 0 .. 2 again: a row of the second launch is bit for bit the same row of the first."""
+    f64, bound = reference
     split = _lib.LIMITER_ROWS_PER_LAUNCH
-    rows = [O.speech(500 + b, 300 + 37 * b, FS) for b in range(3)]
-    fill = [O.speech(600, 64, FS)] * (split - 3)
-    wav, lens = _ragged(rows + fill + rows)
-    gains = [4.0, 3.0, 5.0] + [4.0] * (split - 3) + [4.0, 3.0, 5.0]
+    bt = RS.limiter_batch(split)
+    refs = RS.per_kind(bt, lambda r: O.limit(r.content[: r.length], FS, r.scalar)) + [None] * 3
+    refs[-3:] = refs[:3]
+    wav, lens = _ragged([bt.rows[b, :n] for b, n in enumerate(bt.lengths)] + [bt.rows[b, : bt.lengths[b]] for b in range(3)])
+    gains = list(bt.scalars) + list(bt.scalars[:3])
     m = _lim(dev)
     y, tp, mg, gu, env = _apply(m, wav, lens, gains, envelope=True)
-    assert len(lens) == split + 3
+    assert len(lens) == split + 6 and max(lens) == lens[split + 1] and min(lens) == lens[split + 2] == 1
+    worst = {False: 0.0, True: 0.0}
+    for b, (n, r) in enumerate(zip(lens, refs)):
+        assert np.all(y[b, n:] == 0) and gu[b] == np.float32(gains[b]), b
+        err = float(np.abs(y[b, :n] - r.y).max())
+        worst[b >= split] = max(worst[b >= split], err / bound)
+        assert err <= bound, (b, err)
+        assert abs(float(mg[b]) - r.min_gain) <= bound / float(r.c), b
+        tol = 53 * 2.0 ** -24 * 3 * r.true_peak
+        assert abs(float(tp[b]) - r.true_peak) <= tol and np.abs(env[b, :n] - r.p).max() <= tol and np.all(env[b, n:] == 0), b
+        assert float(np.abs(y[b, :n]).max()) <= float(r.c) * (1 + EPS) ** 2, b
+    print(f"\nlimiter rows across the split: worst error / bound {worst[False]:.3f} before, {worst[True]:.3f} behind the split (bound {bound:.2e})")
     for b in range(3):
         n = lens[b]
-        assert np.array_equal(y[split + b].view(np.uint32), y[b].view(np.uint32)) and not np.isnan(y[b]).any() and np.abs(y[b, :n]).max() > 0.5
-        assert tp[split + b] == tp[b] and mg[split + b] == mg[b] < 1.0 and gu[split + b] == gu[b]
-        assert np.array_equal(env[split + b], env[b])
+        assert np.array_equal(y[split + 3 + b].view(np.uint32), y[b].view(np.uint32)) and not np.isnan(y[b]).any() and np.abs(y[b, :n]).max() > 0.5
+        assert tp[split + 3 + b] == tp[b] and mg[split + 3 + b] == mg[b] < 1.0 and gu[split + 3 + b] == gu[b]
+        assert np.array_equal(env[split + 3 + b], env[b])
+        assert lens[split + b] != n and gains[split + b] != gains[b] and not np.array_equal(y[split + b, :8].view(np.uint32), y[b, :8].view(np.uint32))
     packed, _, _, _, _ = _apply(m, wav, lens, gains, packed=True)
     assert np.array_equal(packed.view(np.uint32), np.concatenate([y[b, :n] for b, n in enumerate(lens)]).view(np.uint32))
     tpm, envm = _meter(m, wav, lens)

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import _limiter_oracle as O
+import _row_split as RS
 from viettts_amd import _lib, wavio
 from viettts_amd._handle import ptr
 from viettts_amd._lib import VttsError
@@ -251,23 +252,44 @@ def test_rows_at_different_cursors_in_one_session(dev):
 
 
 def test_rows_across_the_launch_split_are_the_rows_before_it(dev):
-    """131 slots pushed at once: the cursors of 128 rows travel with one launch, so slot 128 + b is in the second one and equals slot b."""
+    """134 slots pushed at once: the cursors of 128 rows travel with one launch.  Slots 128 + b of the batch of tests/_row_split.py differ from
+    slots b in content, length and gain and hold the longest row and a one-sample row: EVERY slot, the fillers included, is ``limit`` on
+    that whole row bit for bit, results too, and within the float64 oracle's bound.  Three more slots behind them are rows 0 .. 2 again."""
+    _, _, d = O.gpu_reference()
+    bound = 4 * d
     split = _lib.LIMSTREAM_ROWS_PER_LAUNCH
     lim = _lim(dev)
-    heads = [O.speech(500 + b, 300 + 37 * b, FS) for b in range(3)]
-    xs = heads + [O.speech(600, 64, FS)] * (split - 3) + heads
-    gains = [4.0, 3.0, 5.0] + [4.0] * (split - 3) + [4.0, 3.0, 5.0]
-    with _open(lim, split + 3, 100) as s:
+    bt = RS.limiter_batch(split)
+    xs = [np.array(bt.rows[b, :n]) for b, n in enumerate(bt.lengths)]  # (copies: the shared rows are read-only)
+    xs += xs[:3]
+    gains = [float(g) for g in bt.scalars] + [float(g) for g in bt.scalars[:3]]
+    kind = list(bt.kind) + list(bt.kind[:3])
+    refs = RS.per_kind(bt, lambda row: O.limit(row.content[: row.length], FS, row.scalar))
+    refs += refs[:3]
+    assert len(xs) == split + 6 and max(len(x) for x in xs) == len(xs[split + 1]) and len(xs[split + 2]) == 1
+    with _open(lim, split + 6, 100) as s:
         for b, g in enumerate(gains):
             s.reset(b, g)
         got = _feed(s, xs, 100, True)
         r = s.results()
+        worst = {False: 0.0, True: 0.0}
+        for b, ref in enumerate(refs):
+            y, tp, mg, gu = _whole(lim, xs[b], gains[b], key=("split", int(kind[b])))
+            assert torch.equal(got[b], y), b
+            assert torch.equal(r.true_peak[b], tp) and torch.equal(r.min_gain[b], mg) and torch.equal(r.gains[b], gu) and float(gu) == gains[b], b
+            err = float(np.abs(got[b].cpu().numpy() - ref.y).max())
+            worst[b >= split] = max(worst[b >= split], err / bound)
+            assert err <= bound, (b, err)
+            assert abs(float(r.min_gain[b]) - ref.min_gain) <= bound / float(ref.c), b
+            assert abs(float(r.true_peak[b]) - ref.true_peak) <= 53 * 2.0 ** -24 * 3 * ref.true_peak, b
+        print(f"\nlimiter stream rows across the split: worst error / bound {worst[False]:.3f} before, {worst[True]:.3f} behind the split (bound {bound:.2e})")
         for b in range(3):
-            y, tp, mg, _ = _whole(lim, xs[b], gains[b])
-            assert torch.equal(got[b], y) and torch.equal(got[split + b], y) and float(mg) < 1.0
-            assert torch.equal(r.true_peak[split + b], tp) and torch.equal(r.min_gain[split + b], mg) and torch.equal(r.min_gain[b], mg)
-        y, _, _, _ = _whole(lim, xs[3], 4.0)
-        assert all(torch.equal(got[b], y) for b in (3, 64, split - 1))
+            y, tp, mg, _ = _whole(lim, xs[b], gains[b], key=("split", int(kind[b])))
+            assert torch.equal(got[b], y) and torch.equal(got[split + 3 + b], y) and float(mg) < 1.0
+            assert torch.equal(r.true_peak[split + 3 + b], tp) and torch.equal(r.min_gain[split + 3 + b], mg) and torch.equal(r.min_gain[b], mg)
+            assert len(xs[split + b]) != len(xs[b]) and gains[split + b] != gains[b] and not np.array_equal(xs[split + b][:1], xs[b][:1])
+        y, _, _, _ = _whole(lim, xs[3], gains[3], key=("split", int(kind[3])))
+        assert all(torch.equal(got[b], y) for b in range(3, split) if kind[b] == kind[3]) and kind[3] == kind[7] == kind[split - 1]
 
 
 @pytest.mark.parametrize("rate,ms,S,size", [(16000, 2.0, 2 * TILE + 1, 1000), (22050, 5.0, TILE + 333, 777), (96000, 10.0, 6017, 2048)])

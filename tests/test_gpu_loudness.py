@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _loudness_oracle as O
+import _row_split as RS
 from viettts_amd import _lib, wavio
 from viettts_amd._handle import ptr
 
@@ -157,6 +158,75 @@ def test_normalize_is_one_multiply_and_to_pcm16s_rule(dev, bound, name):
         packed, g = _normalize(m, rows, lengths, dt, True, **kw)
         assert packed.shape == (sum(lengths),) and np.array_equal(g.view(np.uint32), gains.view(np.uint32))
         assert np.array_equal(packed, np.concatenate([strided[b, :n] for b, n in enumerate(lengths)]))
+
+
+@pytest.fixture(scope="module")
+def split():
+    """The batch that crosses the rows-per-launch split (tests/_row_split.py) and the float64 oracle of every row, once per distinct row."""
+    bt = RS.loudness_batch(_lib.LOUDNESS_ROWS_PER_LAUNCH)
+    assert bt.N == _lib.LOUDNESS_ROWS_PER_LAUNCH + 3 and bt.lengths[bt.P - 1] > 0 and 0 < bt.lengths[bt.P] < 4 * 1600
+    return bt, RS.per_kind(bt, lambda r: O.measure(r.content[: r.length]))
+
+
+def test_measure_rows_behind_the_launch_split_against_the_oracle(dev, bound, split):
+    """The rows behind the split differ from the first rows in content, level and length and hold the longest row (three blocks, two
+    segments: nseg and nhop are the second launch's), the row too short for a block and an empty one.  All five results and the momentary
+    series of EVERY row against the float64 oracle, as the ragged test above does; outputs and workspace pre-filled."""
+    bt, refs = split
+    f, n, mom = _run(_meter(16000, dev), bt.rows, bt.lengths)
+    assert mom.shape[1] == O.num_blocks(max(bt.lengths[bt.P :]), 16000) + 2 == 3 + 2
+    worst = {False: 0.0, True: 0.0}
+    for b, (length, ref) in enumerate(zip(bt.lengths, refs)):
+        assert ref.gate_room >= 0.05, (b, length, ref.gate_room)
+        got = _got(f, n, mom, b, 16000, length)
+        assert (got.n_blocks, got.n_gated) == (ref.n_blocks, ref.n_gated), (b, length)
+        assert got.sample_peak.view(np.uint32) == ref.sample_peak.view(np.uint32), (b, length)
+        d = O.distance(got, ref)
+        worst[b >= bt.P] = max(worst[b >= bt.P], d / bound)
+        assert d <= bound, (b, length, d, got.integrated, ref.integrated)
+    print(f"\nloudness rows across the split: worst distance / bound {worst[False]:.3f} before, {worst[True]:.3f} behind the split (bound {bound:.2e} LU)")
+
+
+def _normalize_prefilled(m, y, lengths, out_dtype, packed):
+    """normalize() through the C ABI into samples pre-filled with NaN (f32) or 12345 (PCM16) and NaN gains; a packed output carries eight
+    spare elements, which must keep the fill."""
+    yt = torch.from_numpy(np.array(y)).to(m.device)
+    N, S = yt.shape
+    r = m(yt, lengths)
+    tdt, odt, fill = (torch.int16, _lib.VTTS_AUDIO_PCM16, 12345) if out_dtype == "pcm16" else (torch.float32, _lib.VTTS_AUDIO_F32, float("nan"))
+    out = torch.full((sum(lengths) + 8,) if packed else (N, S), fill, dtype=tdt, device=m.device)
+    gains = torch.full((N,), float("nan"), dtype=torch.float32, device=m.device)
+    m._on_stream("normalize", ptr(yt), _lib.VTTS_AUDIO_F32, N, S, (C.c_int32 * N)(*lengths), ptr(r.integrated), ptr(r.sample_peak), -23.0, -1.0, 30.0,
+                 ptr(out), odt, 0 if packed else S, ptr(gains))
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    if packed:
+        assert np.all(out[-8:] == 12345) if out_dtype == "pcm16" else np.isnan(out[-8:]).all()
+        out = out[:-8]
+    return out, gains.cpu().numpy()
+
+
+def test_normalize_rows_behind_the_launch_split(dev, bound, split):
+    """The same batch into strided f32, packed f32 and packed PCM16.  Row P - 1 is not empty and row P is the row too short for a block (gain
+    exactly 1), so the packed offset of row P is the running sum over the whole first launch; the rows behind the split have gains of their
+    own.  Every row: the oracle's gain within the bound, one float32 multiply, to_pcm16's rule, zeros past its samples."""
+    bt, refs = split
+    m = _meter(16000, dev)
+    x = bt.rows
+    f32, gains = _normalize_prefilled(m, x, bt.lengths, "f32", False)
+    ratio = 10.0 ** (2.0 * bound / 20.0)
+    assert gains[bt.P] == 1.0 and len({float(gains[b]) for b in list(range(bt.k)) + list(bt.behind())}) == 2 * bt.k - 1  # (the empty row's gain is 1 as well)
+    for b, (n, ref) in enumerate(zip(bt.lengths, refs)):
+        want = float(O.gain(ref))
+        assert want / ratio <= float(gains[b]) <= want * ratio, (b, n, gains[b], want)
+        prod = x[b, :n] * gains[b]
+        assert np.array_equal(f32[b, :n].view(np.uint32), prod.view(np.uint32)), (b, n)
+        assert not f32[b, n:].any(), b
+    flat = np.concatenate([f32[b, :n] for b, n in enumerate(bt.lengths)])
+    packed, g = _normalize_prefilled(m, x, bt.lengths, "f32", True)
+    assert np.array_equal(g.view(np.uint32), gains.view(np.uint32)) and np.array_equal(packed.view(np.uint32), flat.view(np.uint32))
+    pcm, g = _normalize_prefilled(m, x, bt.lengths, "pcm16", True)
+    assert pcm.dtype == np.int16 and np.array_equal(g.view(np.uint32), gains.view(np.uint32)) and np.array_equal(pcm, wavio.float_to_pcm16(flat))
 
 
 def test_each_cap_binds_and_a_gain_of_one_is_to_pcm16(dev, bound):

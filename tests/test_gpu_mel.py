@@ -10,6 +10,7 @@ restatement (tests/_mel_oracle.py) for inputs made here; it is never taken from 
 ulps at the largest output: logf's one ulp and the final rounding.  All inputs carry a noise floor: log of a band near the 1e-5 floor
 amplifies any absolute error, and no fp32 transform meets fp64 there.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -17,7 +18,9 @@ import pytest
 import torch
 
 import _mel_oracle as oracle
+import _row_split as RS
 from viettts_amd import _lib
+from viettts_amd._handle import ptr
 
 pytestmark = pytest.mark.gpu
 FLOOR32 = np.float32(math.log(1e-5))
@@ -102,6 +105,61 @@ def test_ragged_rows_equal_the_rows_alone(mf, golden):
     err = float(np.abs(got.astype(np.float64) - want)[valid].max())
     print(f"\nragged: max|gpu - fp64| = {err:.3e}, err_ref32 = {e32:.3e}, ratio {err / e32:.2f}")
     assert err <= _bar(e32, want)
+
+
+@pytest.mark.parametrize("pcm", [False, True], ids=["f32", "pcm16"])
+def test_rows_behind_the_launch_split_against_the_oracle(mf, golden, pcm):
+    """MEL_ROWS_PER_LAUNCH + 3 rows (tests/_row_split.py): the rows behind the split differ from the first rows in content and length and
+    hold the longest and the shortest row.  Every row against log_mel_ragged (once per distinct row) at the module's bar, taken over the
+    batch as test_ragged_rows_equal_the_rows_alone and test_tile_edges take it: err_ref32 and max |fp64| are the batch's.  Every row behind
+    the split and the first ones bit for bit the row alone, FLOOR32 past every row's frames; the output is NaN-filled."""
+    bt = RS.frames_batch(_lib.MEL_ROWS_PER_LAUNCH, pcm)
+    assert bt.N == _lib.MEL_ROWS_PER_LAUNCH + 3
+
+    def ref(r):
+        x = r.content.astype(np.float32) / np.float32(32768.0) if pcm else r.content
+        want = oracle.log_mel_ragged(x[None].astype(np.float64), [r.length], golden["melfb"])[0]
+        e32 = np.abs(oracle.log_mel_ragged(x[None], [r.length], golden["melfb"], dtype=np.float32)[0].astype(np.float64) - want).max()
+        return want, float(e32)
+
+    refs = RS.per_kind(bt, ref)
+    got = _run(mf, np.array(bt.rows), bt.lengths)  # (a copy: the shared rows are read-only)
+    assert got.shape == (bt.N, oracle.num_frames(max(bt.lengths[bt.P :])), 80) and not np.isnan(got).any()
+    bar = _bar(max(e32 for _, e32 in refs), np.concatenate([want for want, _ in refs]))
+    worst = {False: 0.0, True: 0.0}
+    for b, (n, (want, _)) in enumerate(zip(bt.lengths, refs)):
+        Tb = oracle.num_frames(n)
+        assert want.shape[0] == Tb
+        err = float(np.abs(got[b, :Tb].astype(np.float64) - want).max())
+        worst[b >= bt.P] = max(worst[b >= bt.P], err / bar)
+        assert err <= bar, (b, err, bar)
+        assert np.all(got[b, Tb:] == FLOOR32), b
+    for b in list(range(bt.k)) + list(bt.behind()):
+        n = bt.lengths[b]
+        assert np.array_equal(_run(mf, np.array(bt.rows[b : b + 1, :n]))[0], got[b, : oracle.num_frames(n)]), b
+    print(f"\nmel rows across the split ({'pcm16' if pcm else 'f32'}): worst error / bar {worst[False]:.3f} before, {worst[True]:.3f} behind the split")
+
+
+@pytest.mark.parametrize("pcm", [False, True], ids=["f32", "pcm16"])
+def test_unaligned_batch_takes_the_scalar_loads_to_the_same_bits(mf, pcm):
+    """Three ragged rows as a view into a flat buffer that starts one element in, at an odd row stride: neither the base nor any row is on
+    16 bytes, so the staging takes the scalar loads.  Bit for bit the same rows in an aligned buffer at an aligned stride."""
+    bt = RS.frames_batch(_lib.MEL_ROWS_PER_LAUNCH, pcm)
+    pick = [0, bt.P, bt.P + 1]  # with a fourth row, the f32 row 3 would sit on 16 bytes again
+    y, lengths = bt.rows[pick], [bt.lengths[b] for b in pick]  # (fancy indexing: a copy)
+    want = _run(mf, y, lengths)
+    assert not np.isnan(want).any()
+    N, S = y.shape
+    odd = S + 1
+    assert S % 8 == 0 and odd % 2 == 1
+    flat = torch.full((1 + N * odd,), 0x7FFF if pcm else float("nan"), dtype=torch.int16 if pcm else torch.float32, device=mf.device)
+    view = flat[1:].view(N, odd)
+    view[:, :S] = torch.from_numpy(np.array(y)).to(mf.device)
+    assert view.data_ptr() % 16 != 0 and all((view.data_ptr() + b * odd * view.element_size()) % 16 != 0 for b in range(N))
+    out = torch.full(want.shape, float("nan"), dtype=torch.float32, device=mf.device)
+    mf._on_stream("forward", ptr(view), _lib.VTTS_MEL_PCM16 if pcm else _lib.VTTS_MEL_F32, N, odd, (C.c_int32 * N)(*lengths), ptr(out), want.shape[1], None)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), want.view(np.uint32))
 
 
 def test_an_adopted_blob_gives_the_same_bits(mf, golden):

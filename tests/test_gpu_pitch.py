@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import _pitch_oracle as O
+import _row_split as RS
 from viettts_amd import _lib
 from viettts_amd._handle import ptr
 
@@ -96,6 +97,47 @@ def test_ragged_batch_rows_equal_the_rows_alone(dev, pcm):
         assert alone.shape == (3, 1, Tb)
         assert np.array_equal(alone[:, 0].view(np.uint32), got[:, b, :Tb].view(np.uint32)), b  # bit for bit: the row is reflected at its own end
         assert np.all(got[0, b, Tb:] == 0) and np.all(got[1, b, Tb:] == 1) and np.all(got[2, b, Tb:] == 0), b
+
+
+@pytest.mark.parametrize("pcm", [False, True], ids=["f32", "pcm16"])
+def test_rows_behind_the_launch_split_against_the_oracle(dev, pcm):
+    """PITCH_ROWS_PER_LAUNCH + 3 rows (tests/_row_split.py): the rows behind the split differ from the first rows in content and length and
+    hold the longest and the shortest row, so a second launch without ``r0`` on its input, its lengths or an output computes something else
+    than yin_f32 says.  NaN-filled outputs with two spare frames; the fill rule past every row's frames."""
+    bt = RS.frames_batch(_lib.PITCH_ROWS_PER_LAUNCH, pcm)
+    assert bt.N == _lib.PITCH_ROWS_PER_LAUNCH + 3 and bt.rows.dtype == (np.int16 if pcm else np.float32)
+    want = RS.per_kind(bt, lambda r: _want(O.yin_f32(r.content[None], O.DEFAULT, [r.length])))
+    got = _run(_tracker(O.DEFAULT, dev), bt.rows, bt.lengths, t_extra=2)
+    assert got.shape[2] == O.num_frames(max(bt.lengths[bt.P :])) + 2
+    for b, n in enumerate(bt.lengths):
+        Tb = O.num_frames(n)
+        assert np.array_equal(got[:, b, :Tb].view(np.uint32), want[b][:, 0, :Tb].view(np.uint32)), b
+        assert np.all(got[0, b, Tb:] == 0) and np.all(got[1, b, Tb:] == 1) and np.all(got[2, b, Tb:] == 0), b
+    print(f"\npitch rows behind the split: {bt.k} rows ==, worst error / bar 0 (the contract is ==)")
+
+
+@pytest.mark.parametrize("pcm", [False, True], ids=["f32", "pcm16"])
+def test_unaligned_batch_takes_the_scalar_loads_to_the_same_bits(dev, pcm):
+    """Three ragged rows as a view into a flat buffer that starts one element in, at an odd row stride: neither the base nor any row is on
+    16 bytes, so the staging takes the scalar loads.  Bit for bit the same rows in an aligned buffer at an aligned stride."""
+    bt = RS.frames_batch(_lib.PITCH_ROWS_PER_LAUNCH, pcm)
+    pick = [0, bt.P, bt.P + 1]  # with a fourth row, the f32 row 3 would sit on 16 bytes again
+    y, lengths = bt.rows[pick], [bt.lengths[b] for b in pick]
+    trk = _tracker(O.DEFAULT, dev)
+    want = _run(trk, y, lengths, t_extra=1)
+    _same(want, _want(O.yin_f32(y, O.DEFAULT, lengths), t_extra=1))
+    N, S = y.shape
+    odd = S + 1
+    assert S % 8 == 0 and odd % 2 == 1
+    flat = torch.full((1 + N * odd,), 0x7FFF if pcm else float("nan"), dtype=torch.int16 if pcm else torch.float32, device=trk.device)
+    view = flat[1:].view(N, odd)
+    view[:, :S] = torch.from_numpy(np.array(y)).to(trk.device)
+    assert view.data_ptr() % 16 != 0 and all((view.data_ptr() + b * odd * view.element_size()) % 16 != 0 for b in range(N))
+    T = want.shape[2]
+    out = torch.full((3, N, T), float("nan"), dtype=torch.float32, device=trk.device)
+    trk._on_stream("forward", ptr(view), _lib.VTTS_MEL_PCM16 if pcm else _lib.VTTS_MEL_F32, N, odd, (C.c_int32 * N)(*lengths), ptr(out[0]), ptr(out[1]), ptr(out[2]), T, None)
+    torch.cuda.synchronize()
+    _same(out.cpu().numpy(), want)
 
 
 def test_content_voiced_noise_and_silence(dev):

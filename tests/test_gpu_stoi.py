@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _row_split as RS
 import _stoi_oracle as O
 from viettts_amd import _lib
 from viettts_amd._handle import ptr
@@ -202,6 +203,36 @@ def test_a_row_alone_equals_the_row_in_a_ragged_batch_bit_for_bit(meter):
         assert np.array_equal(a.ser.view(np.uint32)[:, 0, :M], g.ser.view(np.uint32)[:, b, :M])
         assert np.array_equal(a.mags.view(np.uint32)[0, :, :, :T], g.mags.view(np.uint32)[b, :, :, :T])
         assert np.array_equal(a.kept[0, :K], g.kept[b, :K]) and np.array_equal(a.energy.view(np.uint64)[0, :K], g.energy.view(np.uint64)[b, :K])
+
+
+def test_rows_behind_the_launch_split_against_the_oracle(meter, bounds):
+    """STOI_ROWS_PER_LAUNCH + 3 rows (tests/_row_split.py): the rows behind the split differ from the first rows in both signals and in
+    length, and hold the longest row (kmax, mmax and the strides of the four workspace slices are the second launch's), a row one sample
+    short of a segment and an empty one.  Both figures, the three counts, the keep list, the energies, both series and the band magnitudes of
+    EVERY row against the float64 oracle (once per distinct row), all requested in the one call; each row behind the split is the row alone."""
+    bt = RS.stoi_batch(_lib.STOI_ROWS_PER_LAUNCH)
+    assert bt.N == _lib.STOI_ROWS_PER_LAUNCH + 3
+    xs, ys = np.ascontiguousarray(bt.rows[:, :, 0]), np.ascontiguousarray(bt.rows[:, :, 1])
+    refs = RS.per_kind(bt, lambda r: O.measure(r.content[: r.length, 0], r.content[: r.length, 1]))
+    assert [refs[b].n_segments > 0 for b in bt.behind()] == [False, True, False] and refs[bt.P + 1].n_frames == max(r.n_frames for r in refs)
+    g = _run(meter, xs, ys, bt.lengths)
+    before, behind = {}, {}
+    for b, ref in enumerate(refs):
+        _compare(g, b, ref, bounds, behind if b >= bt.P else before)
+    _report("rows before the split", before, bounds)
+    _report("rows behind the split", behind, bounds)
+    print("worst error / bound behind the split: " + "  ".join(f"{k} {v / getattr(bounds, k):.3f}" for k, v in behind.items()))
+    for b in bt.behind():
+        n = bt.lengths[b]
+        if n == 0:
+            continue  # (a call needs a sample; the empty row is compared with the oracle above)
+        a = _run(meter, xs[b : b + 1, :n], ys[b : b + 1, :n], None)
+        K, Kk = int(a.n[0, 0]), int(a.n[1, 0])
+        T, M = max(0, Kk - 1), int(a.n[2, 0])
+        assert np.array_equal(a.f.view(np.uint32)[:, 0], g.f.view(np.uint32)[:, b]) and np.array_equal(a.n[:, 0], g.n[:, b]), b
+        assert np.array_equal(a.ser.view(np.uint32)[:, 0, :M], g.ser.view(np.uint32)[:, b, :M]), b
+        assert np.array_equal(a.mags.view(np.uint32)[0, :, :, :T], g.mags.view(np.uint32)[b, :, :, :T]), b
+        assert np.array_equal(a.kept[0, :K], g.kept[b, :K]) and np.array_equal(a.energy.view(np.uint64)[0, :K], g.energy.view(np.uint64)[b, :K]), b
 
 
 def test_float32_input_equals_pcm16_input_bit_for_bit(meter, bounds):

@@ -67,6 +67,12 @@ LIMITER_RUN = 16  # include/vtts_limiter.h: VTTS_LIMITER_RUN
 LIMITER_PHASE_TAPS = 52  # include/vtts_limiter.h: VTTS_LIMITER_PHASE_TAPS
 LIMITER_MIN_RATE, LIMITER_MAX_RATE = 8000, 96000  # include/vtts_limiter.h: VTTS_LIMITER_MIN_RATE / _MAX_RATE
 LIMITER_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/limiter.hip: the rows whose lengths one launch carries
+AUDIO_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/audio.hip, likewise: ROWS_PER_LAUNCH
+MEL_ROWS_PER_LAUNCH = 256  # viettts_amd/csrc/mel.hip
+PITCH_ROWS_PER_LAUNCH = 256  # viettts_amd/csrc/pitch.hip
+STOI_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stoi.hip
+LOUDNESS_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/loudness.hip
+DTW_PAIRS_PER_LAUNCH = 128  # viettts_amd/csrc/dtw.hip: PAIRS_PER_LAUNCH
 LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
 LIMSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_limstream.h: VTTS_LIMSTREAM_ROWS_PER_LAUNCH
 RSSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_rsstream.h: VTTS_RSSTREAM_MAX_CHUNK
