@@ -55,8 +55,8 @@ sets its running sums aside every 8 steps where a layer has more than 512 input 
 order; up to 512 channels the instantiation, and so every bit and the speed, is the parent's).  The restatement of the folded order predicted 1.8e-6 (0.49 of
 the bar); the GPU gives 2.13e-6 (0.53), and W's autoregressive figures fell from 0.63 / 0.75 to 0.26 / 0.33 with it.
 
-Left unmeasured: streaming windows, long-form chunking and speed at other widths; the grouped hand-over (forward_groups) and forward_from_encoder at other
-widths; the partitionable mask layout at other prenet widths.
+Left unmeasured: long-form chunking and speed at other widths.  (The streaming session, the slot pool, forward_groups, forward_from_encoder and the
+partitionable mask layout run at every set in tests/test_gpu_nat_sessions.py, bit for bit against the plain calls this module pins to the oracles.)
 """
 import numpy as np
 import pytest

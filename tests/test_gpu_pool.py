@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from _nat_sessions import decode_to as _decode_to, finish_all as _finish_all, mel0 as _mel0  # the drivers all widths share
 from viettts_amd._lib import VttsError
 
 pytestmark = pytest.mark.gpu
@@ -24,16 +25,6 @@ def _case(seed, L):
 # 77, 39, 6 and 110 frames, and a fifth sentence for a slot's second occupant; a dropout seed per row
 CASES = {"a": _case(47, 25), "b": _case(48, 12), "c": _case(49, 3), "d": _case(48, 32), "e": _case(50, 9)}
 SEEDS = {"a": 11, "b": 12, "c": 13, "d": 14, "e": 15}
-
-
-def _mel0(model, ws, B, Lmax, Fmax):
-    """The decoder's mel before the postnet, ``[B, Fmax, mel_dim]``: the sixth buffer of the workspace layout both the un-pooled call and the pool
-    use (viettts_amd/csrc/nat.hip: NatAcousticWs — encoder ping-pong x 2, encoder output, both layers' per-token gates, then mel0; 256-byte blocks)."""
-    al = lambda n: (n + 255) // 256 * 256
-    cfg = model.cfg
-    bld, g = B * Lmax * cfg.encoder_dim * 4, 4 * cfg.decoder_dim
-    off = 2 * al(bld) + al(2 * bld) + 2 * al(B * Lmax * g * 4)
-    return ws[off : off + B * Fmax * cfg.mel_dim * 4].view(torch.float32).view(B, Fmax, cfg.mel_dim)
 
 
 @pytest.fixture(scope="module")
@@ -69,23 +60,8 @@ def _admit(pool, slot, key):
     pool.admit(slot, tok, dur, n, dropout_seed=SEEDS[key])
 
 
-def _decode_to(pool, tick):
-    """Up to ``tick`` in calls of 32, 7 and 1 ticks, the largest that fits first."""
-    while pool.tick < tick:
-        pool.decode(next(k for k in (32, 7, 1) if pool.tick + k <= tick))
-
-
 def _pool_mel0(acoustic, pool):
     return _mel0(acoustic, pool._ws, pool.slots, pool.Lmax, pool.Fmax)
-
-
-def _finish_all(pool, width):
-    """Every busy row's remaining frames in windows of ``width``, all rows of a round in one call."""
-    while True:
-        wins = [(s, pool.finished[s], min(pool.finished[s] + width, pool.n_frames[s])) for s in range(pool.slots) if pool.busy[s] and pool.finished[s] < pool.n_frames[s]]
-        if not wins:
-            return
-        pool.finish(wins)
 
 
 def _assert_rows(acoustic, pool, refs, rows, sfx=""):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from _nat_sessions import stream_in_windows
 from viettts_amd._lib import VttsError
 from viettts_amd.streaming import stream_plan, synthesize_stream
 
@@ -61,17 +62,8 @@ def refs(acoustic):
 
 
 def _stream_in_windows(am, cases, seeds, chunk, ref):
-    """Windows of ``chunk`` frames, the decoder 10 frames ahead of each: after every window the mel's frames below its end are final."""
-    Fmax = max(c[2] for c in cases)
-    with am.open_stream(*_batch(cases), max_window=chunk, dropout_seeds=seeds) as st:
-        assert st.mel.shape == ref.shape and not am.resident_used
-        for f0 in range(0, Fmax, chunk):
-            f1 = min(Fmax, f0 + chunk)
-            st.decode(f1 + 10)
-            assert st.frames_decoded == min(f1 + 10, Fmax)
-            st.finish(f0, f1)
-            assert torch.equal(st.mel[:, :f1], ref[:, :f1]), (chunk, f0, f1)
-        assert torch.equal(st.mel, ref), chunk
+    """The window driver all widths share (tests/_nat_sessions.py) on this module's sentences."""
+    stream_in_windows(am, _batch(cases), seeds, chunk, ref)
 
 
 @pytest.mark.parametrize("chunk", [1, 7, 32, 50])
