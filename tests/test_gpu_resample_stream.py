@@ -233,6 +233,24 @@ def test_rows_across_the_launch_split(dev):
         assert _same(torch.cat([a[i], b[i]]), want[i]), i
 
 
+def test_pcm16_on_both_sides_off_the_identity_ratio(dev):
+    """rs_stream_k<short, short>, the dtype pair the tests above reach only where the rates are equal (a copy): rows of 17, 4097 and
+    2 * 4096 + 5 PCM16 samples at 3/2 (more than one tile, no multiple of it), at once and in random sizes with an empty last flush, strided
+    and packed.  The whole row's PCM16 is float_to_pcm16 of its fp32 output, so the yardstick's own format is checked as well."""
+    from viettts_amd import wavio
+
+    rs = _rs(dev, 16000, 24000)
+    xs = [_row(900 + i, S, True) for i, S in enumerate((17, 4097, 2 * 4096 + 5))]
+    want = [_whole(rs, x, "pcm16") for x in xs]
+    for x, w in zip(xs, want):
+        assert w.dtype == torch.int16 and np.array_equal(w.cpu().numpy(), wavio.float_to_pcm16(_whole(rs, x, "f32").cpu().numpy()))
+    for sizes, packed, flush in (([2 * 4096 + 5], False, False), (RANDOM, True, True)):
+        with _open(rs, len(xs), 2 * 4096 + 5, "pcm16") as s:
+            got = _feed(s, xs, sizes, packed, flush=flush)
+        for x, g, w in zip(xs, got, want):
+            assert g.dtype == torch.int16 and g.shape == w.shape == (rs.out_samples(len(x)),) and _same(g, w), (sizes[0], packed, len(x))
+
+
 # ------------------------------------------------------------ 5. NaN and Inf ------------------------------------------------------------
 @pytest.mark.parametrize("rates", SO.RATES[:-1], ids=IDS[:-1])
 def test_nan_and_inf_reach_the_outputs_they_reach_unstreamed(dev, rates):

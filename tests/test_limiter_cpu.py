@@ -207,7 +207,12 @@ def test_limiter_hip_is_built_without_packed_f32():
     assert "limiter.hip" in build.SOURCES and "-fno-slp-vectorize" in build.FILE_FLAGS["limiter.hip"]
     assert any(str(h).endswith("vtts_limiter.h") for h in build.HEADERS) and "audio_design.h" in build.HEADERS
     src = (build.CSRC / "limiter.hip").read_text()
-    assert "asm" not in src and '#include "audio_design.h"' in src and "kaiser" not in src.lower()  # the design is reused, not restated
+    common = (build.CSRC / "limiter_common.h").read_text()
+    # the design is reused, not restated: both create()s reach it through limiter_common.h's configure()
+    assert "asm" not in src and '#include "limiter_common.h"' in src and '#include "audio_design.h"' in common and "limiter_common.h" in build.HEADERS
+    for text in (src, common, (build.CSRC / "limiter_stream.hip").read_text()):
+        assert "kaiser" not in text.lower()
+    assert "ad::design(" in common and "ad::design(" not in src and "ad::design(" not in (build.CSRC / "limiter_stream.hip").read_text()
 
 
 @pytest.mark.parametrize("rate", [8000, 16000, 22050, 48000])

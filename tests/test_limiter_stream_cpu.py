@@ -193,11 +193,37 @@ def test_limiter_stream_hip_is_built_like_the_other_device_files():
     from viettts_amd.csrc import build
 
     assert "limiter_stream.hip" in build.SOURCES and "-fno-slp-vectorize" in build.FILE_FLAGS["limiter_stream.hip"]
-    assert {"limiter_common.h", "limstream_host.h"} <= set(build.HEADERS) and any(str(h).endswith("vtts_limstream.h") for h in build.HEADERS)
+    assert {"limiter_common.h", "limstream_host.h", "stream_rows_host.h", "sample_convert.h"} <= set(build.HEADERS)
+    assert any(str(h).endswith("vtts_limstream.h") for h in build.HEADERS)
     src = (build.CSRC / "limiter_stream.hip").read_text()
-    assert "asm" not in src and '#include "limstream_host.h"' in src
-    host = (build.CSRC / "limstream_host.h").read_text()
-    assert "#include <hip" not in host and "hipStream" not in host and "hipError" not in host  # plain C++: tools/check_limstream_host.cpp builds it alone
+    assert "asm" not in src and '#include "limstream_host.h"' in src and '#include "limiter_common.h"' in src and '#include "stream_rows_host.h"' in src
+    # plain C++: tools/check_limstream_host.cpp and tools/check_stream_rows_host.cpp build them alone
+    for name in ("limstream_host.h", "stream_rows_host.h"):
+        host = (build.CSRC / name).read_text()
+        assert "#include <hip" not in host and "hipStream" not in host and "hipError" not in host, name
+    assert "__device__" not in host and "__HIPCC__" not in host  # (the cursors live on the host alone)
+    assert (O.REPO / "tools" / "check_stream_rows_host.cpp").exists()
+    assert '#include "stream_rows_host.h"' in (build.CSRC / "resample_stream.hip").read_text()  # one copy of the cursors' rules for both streams
+
+
+def test_the_limiters_arithmetic_and_the_sample_conversions_are_stated_once():
+    from viettts_amd.csrc import build
+
+    whole, stream, common = ((build.CSRC / n).read_text() for n in ("limiter.hip", "limiter_stream.hip", "limiter_common.h"))
+    assert '#include "limiter_common.h"' in whole  # "the un-streamed bits" by one copy of the chains, the sliding minimum and the run sums
+    assert "fmaf(" not in whole and "fmaf(" not in stream and "fmaf(" in common
+    for name in ("true_peak4(", "smooth_gains(", "gain_buf_floats("):
+        assert len(re.findall(r"^[^/\n]*\b(?:void|float\*|int) " + re.escape(name), common, re.M)) == 1 and name in whole and name in stream, name
+        assert not re.search(r"\b(?:void|float\*|int) " + re.escape(name), whole + stream), name
+    assert "double s = 0.0" in common and "double s" not in whole and "double s" not in stream  # the fp64 run sums
+    defs = [p.name for p in sorted(build.CSRC.iterdir()) if p.suffix in (".hip", ".h") and "to_float(short" in p.read_text()]
+    assert defs == ["sample_convert.h"]
+    defs = [p.name for p in sorted(build.CSRC.iterdir()) if p.suffix in (".hip", ".h") and re.search(r"short from_float<short>\(", p.read_text())]
+    assert defs == ["sample_convert.h"]
+    defs = [p.name for p in sorted(build.CSRC.iterdir()) if p.suffix in (".hip", ".h") and re.search(r"\bint check_rows\(", p.read_text())]
+    assert defs == ["vtts_internal.h"]  # the limiter's and the loudness meter's, the margin (TILE or SEGMENT) a parameter
+    for name in ("limiter.hip", "loudness.hip"):
+        assert "check_rows(" in (build.CSRC / name).read_text(), name
 
 
 def test_create_refuses_what_the_header_rules_out(lib):

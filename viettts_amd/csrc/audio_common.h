@@ -1,33 +1,19 @@
-// Device helpers the resampler's kernels share (audio.hip, resample_stream.hip): the sample conversions and the outputs of one staged
-// span, i.e. the slot -> output -> phase arithmetic and the one fp32 fmaf chain per output (include/vtts_audio.h).
+// Device helpers the resampler's kernels share (audio.hip, resample_stream.hip): the outputs of one staged span, i.e. the slot -> output
+// -> phase arithmetic and the one fp32 fmaf chain per output (include/vtts_audio.h).  The sample conversions are sample_convert.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/vtts_audio.h"
+#include "sample_convert.h"
 
 namespace vtts_audio_dev {
 
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
+using vtts_sample::from_float;
+using vtts_sample::to_float;
 
 // floor(a / 8) * 8, a may be negative
 __device__ __forceinline__ long long floor8(long long a) { return a & ~7LL; }
-
-template <typename TO>
-__device__ __forceinline__ TO from_float(float v);
-template <>
-__device__ __forceinline__ float from_float<float>(float v) {
-    return v;
-}
-// viettts_amd/wavio.py float_to_pcm16: rint(clip(x, -1, 1) * 32767) in double.  The product of a 24-bit and a 15-bit significand is exact
-// in double, so the only rounding is rint's (to nearest, ties to even).
-template <>
-__device__ __forceinline__ short from_float<short>(float v) {
-    if (!(v == v)) return 0;
-    const float c = fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)c * 32767.0);
-}
 
 // The table's shape and the ratio, as the kernels carry them.
 struct Phases {

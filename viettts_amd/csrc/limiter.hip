@@ -3,18 +3,15 @@
 //
 //   lim_env_k, one workgroup (256 lanes) per VTTS_LIMITER_TILE = 4096 samples of one row:
 //     1. stage the tile and its FIR halo (27 samples before, 24 after; zeros outside the row) in LDS, PCM16 scaled by 2^-15.
-//     2. each lane takes 4 consecutive samples at a time: 56 staged values in registers feed the 16 fmaf chains of their 4 x 4 oversampled
-//        points (audio.hip's chain for L = 4, M = 1: 52 taps a phase, ascending n, the zero padding first), 14 16-byte LDS reads for 832 FMAs.
-//        The 208 taps are a kernel argument and reach the FMAs as scalar operands.
+//     2. each lane takes 4 consecutive samples at a time through limiter_common.h's true_peak4: their 4 x 4 oversampled points.  The 208
+//        taps are a kernel argument.
 //     3. p[n] = max(|x[n]|, |u[4 n .. 4 n + 3]|) goes to the workspace (unless only the peak is wanted) and, if asked for, to the caller's
 //        envelope; the tile's maximum goes to its slot.
 //   lim_reduce_k, one wave per row: the row's true peak from its tiles' slots in tile order (and, behind the limiter, its smallest gain).
 //   lim_apply_k, same tiling.  A row with fl(g true_peak) <= c takes the plain multiply.  Otherwise:
 //     1. req over the tile and 2 W samples either side (indices clamped to the row) into LDS.
-//     2. sliding minimum over 2 W + 1 by doubling: min over windows of 2, 4, .. 2^q <= 2 W + 1 samples between two LDS buffers, and the two
-//        overlapping windows of 2^q that cover 2 W + 1.  A minimum is exact, so the scheme does not show in the bits.
-//     3. the mean in the contract's fixed order: a lane owns VTTS_LIMITER_RUN = 16 consecutive samples, sums the first one's window in fp64
-//        and slides it along the other 15.  held is kept at word j + j / 16 so that 64 lanes walking 16 words apart meet 64 banks.
+//     2./3. limiter_common.h's smooth_gains: the sliding minimum over 2 W + 1, then its mean in the contract's fixed order, between two
+//        LDS buffers.
 //     4. a = min(req, mean), y = (g x) a, the store, and the tile's smallest a to its slot: coalesced again.
 //   lim_pregain_k: one thread per row.
 //
@@ -28,35 +25,18 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_limiter.h"
-#include "audio_design.h"
 #include "limiter_common.h"
 #include "vtts_internal.h"
 
 using vtts::failf;
-namespace ad = vtts_audio_design;
-using vtts_limiter_dev::from_float;
-using vtts_limiter_dev::KP;
-using vtts_limiter_dev::LEAD;
-using vtts_limiter_dev::LimTaps;
-using vtts_limiter_dev::OS;
-using vtts_limiter_dev::padded;
-using vtts_limiter_dev::req_of;
-using vtts_limiter_dev::to_float;
+using vtts::check_rows;
+using namespace vtts_limiter_dev;  // (the tiling constants among them)
 
 namespace {
 
-constexpr int TILE = VTTS_LIMITER_TILE;
-constexpr int RUN = VTTS_LIMITER_RUN;
-constexpr int THREADS = 256;
 constexpr int ROWS_PER_LAUNCH = 128;
 constexpr int SPAN = TILE + KP + 4;   // staged samples of a tile: x[t0 - LEAD .. t0 + TILE + 28]
-constexpr int MAX_W = 960;
-static_assert(THREADS * RUN == TILE, "one lane per run of the mean");
-static_assert(TILE % (4 * THREADS) == 0, "whole passes of 4 samples a lane");
-
-// floats of one of lim_apply_k's two LDS buffers: req over TILE + 4 W, or held over TILE + 2 W at word j + j / 16
-constexpr int apply_buf_floats(int W) { return (TILE + 4 * W + (TILE + 2 * W) / RUN + 4 + 3) / 4 * 4; }
-constexpr int MAX_APPLY_LDS = 2 * apply_buf_floats(MAX_W) * (int)sizeof(float);
+constexpr int MAX_APPLY_LDS = 2 * gain_buf_floats(MAX_W) * (int)sizeof(float);  // lim_apply_k's two gain buffers
 
 struct LimLens {
     int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
@@ -135,26 +115,11 @@ __global__ __launch_bounds__(THREADS) void lim_env_k(const EnvArgs a, const LimT
     for (int it = 0; it < TILE / (4 * THREADS); ++it) {
         const int i = 4 * (tid + THREADS * it);
         if (i >= live) break;
-        float xv[KP + 4];
-#pragma unroll
-        for (int c = 0; c < (KP + 4) / 4; ++c) {
-            const float4 v = span4[(i >> 2) + c];
-            xv[4 * c + 0] = v.x, xv[4 * c + 1] = v.y, xv[4 * c + 2] = v.z, xv[4 * c + 3] = v.w;
-        }
         float pk[4];
+        true_peak4(span4, i, tp, pk);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            float p = fabsf(xv[s + LEAD]);
-#pragma unroll
-            for (int r = 0; r < OS; ++r) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int k = 0; k < KP; ++k) acc = fmaf(xv[s + k], tp.t[r][k], acc);
-                p = fmaxf(p, fabsf(acc));
-            }
-            pk[s] = p;
-            if (i + s < live) mx = fmaxf(mx, p);
-        }
+        for (int s = 0; s < 4; ++s)
+            if (i + s < live) mx = fmaxf(mx, pk[s]);
         if (ew) *reinterpret_cast<float4*>(ew + i) = make_float4(pk[0], pk[1], pk[2], pk[3]);  // (past the row inside its last tile: never read)
         if (eo) {
 #pragma unroll
@@ -164,11 +129,10 @@ __global__ __launch_bounds__(THREADS) void lim_env_k(const EnvArgs a, const LimT
     }
     if (eo)
         for (int i = live + tid; i < cnt; i += THREADS) eo[i] = 0.0f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = wave_extreme<false>(mx);
     if ((tid & 63) == 0) wmax[tid >> 6] = mx;
     __syncthreads();
-    if (tid == 0) a.tmax[(long long)b * a.nt + blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (tid == 0) a.tmax[(long long)b * a.nt + blockIdx.x] = extreme4<false>(wmax);
 }
 
 // MIN = false: result = max over the row's tile slots, from 0.  MIN = true: min, from 1.
@@ -182,11 +146,7 @@ __global__ __launch_bounds__(64) void lim_reduce_k(const ReduceArgs a, const Lim
         const float s = a.slots[(long long)b * a.nt + t];
         v = MIN ? fminf(v, s) : fmaxf(v, s);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float w = __shfl_xor(v, o);
-        v = MIN ? fminf(v, w) : fmaxf(v, w);
-    }
+    v = wave_extreme<MIN>(v);
     if (lane == 0) {
         a.result[b] = v;
         if (a.gains_used) a.gains_used[b] = a.gains ? a.gains[b] : 1.0f;
@@ -233,11 +193,10 @@ __global__ __launch_bounds__(THREADS) void lim_apply_k(const ApplyArgs a, const 
         return;
     }
 
-    const int W = a.W, Lw = 2 * W + 1, nR = TILE + 4 * W, nH = TILE + 2 * W;
+    const int W = a.W, nR = TILE + 4 * W;
     const float* e = a.env + (long long)b * a.e_stride;
     const long long last = len - 1;
     float* cur = reinterpret_cast<float*>(lds4);
-    float* nxt = cur + a.nb;
 
     // ---- 1. req[t0 - 2 W + k], k < TILE + 4 W
 #pragma clang loop vectorize(disable)  // (the loop vectoriser would pair the multiplies into v_pk_mul_f32: build.py)
@@ -247,65 +206,28 @@ __global__ __launch_bounds__(THREADS) void lim_apply_k(const ApplyArgs a, const 
     }
     __syncthreads();
 
-    // ---- 2. cur[k] = min req over `win` samples from k, win = 1, 2, 4, .. while 2 win <= Lw
-    int win = 1, ncur = nR;
-    while (2 * win <= Lw) {
-        ncur -= win;
-        for (int k = tid; k < ncur; k += THREADS) nxt[k] = fminf(cur[k], cur[k + win]);
-        __syncthreads();
-        float* t = cur;
-        cur = nxt;
-        nxt = t;
-        win *= 2;
-    }
-    // held[t0 - W + j] at nxt[padded(j)], j < TILE + 2 W: the window of the CLAMPED sample
-    for (int j = tid; j < nH; j += THREADS) {
-        const long long m = min(max(t0 - W + j, 0LL), last);
-        const int jc = (int)(m - (t0 - W));  // 0 .. nH - 1; its window is req[jc .. jc + 2 W] of the staged span
-        nxt[padded(j)] = fminf(cur[jc], cur[jc + Lw - win]);
-    }
-    __syncthreads();
-
-    // ---- 3. the mean of held[n - W .. n + W]: fp64, the first sample of a run from scratch, the others by sliding
-    {
-        const float* H = nxt;
-        const int i0 = RUN * tid;
-        if (i0 < live) {
-            double s = 0.0;
-            for (int k = 0; k < Lw; ++k) s += (double)H[padded(i0 + k)];
-            const double dl = (double)Lw;
-            cur[i0] = (float)(s / dl);
-            for (int t = 1; t < RUN; ++t) {
-                const int n = i0 + t;
-                s = (s + (double)H[padded(n + 2 * W)]) - (double)H[padded(n - 1)];
-                cur[n] = (float)(s / dl);
-            }
-        }
-    }
-    __syncthreads();
+    // ---- 2./3. the mean of the sliding minimum, for the tile's samples
+    const float* mean = smooth_gains(cur, cur + a.nb, nR, W, t0, last, TILE + 2 * W, live, tid);
 
     // ---- 4. a, y, the store
     float amin = 1.0f;
 #pragma clang loop vectorize(disable)  // (the loop vectoriser would pair the multiplies into v_pk_mul_f32: build.py)
     for (int i = tid; i < cnt; i += THREADS) {
         if (i < live) {
-            const float av = fminf(req_of(e[t0 + i], g, c), cur[i]);
+            const float av = fminf(req_of(e[t0 + i], g, c), mean[i]);
             amin = fminf(amin, av);
             out[i] = from_float<TO>((to_float(x[i]) * g) * av);
         } else {
             out[i] = TO(0);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amin = fminf(amin, __shfl_xor(amin, o));
+    amin = wave_extreme<true>(amin);
     if ((tid & 63) == 0) wmin[tid >> 6] = amin;
     __syncthreads();
-    if (tid == 0) a.tmin[(long long)b * a.nt + blockIdx.x] = fminf(fminf(wmin[0], wmin[1]), fminf(wmin[2], wmin[3]));
+    if (tid == 0) a.tmin[(long long)b * a.nt + blockIdx.x] = extreme4<true>(wmin);
 }
 
 // ------------------------------------------------------------ host side ------------------------------------------------------------
-constexpr int64_t MAX_S = 0x7fffffff - TILE;
-
 struct Layout {
     int64_t nt = 0;        // tiles of the longest row: the per-row pitch of the slots, and e_stride = nt * TILE
     size_t env = 0, tmax = 0, tmin = 0, bytes = 0;
@@ -320,21 +242,6 @@ Layout layout(int N, int64_t S) {
     l.bytes = (l.tmin + slots + 15) / 16 * 16;
     if (l.bytes == 0) l.bytes = 16;
     return l;
-}
-
-int check_rows(const char* what, const void* wav, int dtype, int N, int64_t S_stride, const int32_t* lengths, int64_t* longest) {
-    if (!wav) return failf(VTTS_ERR_INVALID, "null argument");
-    if (dtype != VTTS_AUDIO_F32 && dtype != VTTS_AUDIO_PCM16) return failf(VTTS_ERR_INVALID, "%s: dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", what, dtype);
-    if (N <= 0) return failf(VTTS_ERR_INVALID, "%s: N must be positive (got %d)", what, N);
-    if (S_stride < 0 || S_stride > MAX_S) return failf(VTTS_ERR_SHAPE, "%s: S_stride must be in 0 .. 2^31 - 1 - %d (got %lld)", what, TILE, (long long)S_stride);
-    int64_t m = 0;
-    for (int b = 0; b < N; ++b) {
-        const int64_t len = lengths ? lengths[b] : S_stride;
-        if (len < 0 || len > S_stride) return failf(VTTS_ERR_SHAPE, "%s: lengths[%d] = %lld is outside 0 .. S_stride = %lld", what, b, (long long)len, (long long)S_stride);
-        if (len > m) m = len;
-    }
-    *longest = m;
-    return VTTS_OK;
 }
 
 int check_workspace(const void* workspace, size_t workspace_bytes, const Layout& l) {
@@ -408,22 +315,12 @@ hipError_t launch_apply(const ApplyArgs& a, const LimRows& rows, dim3 grid, hipS
 
 VTTS_API int vtts_limiter_create(const vtts_limiter_cfg* cfg, int device, vtts_limiter** out) {
     if (!cfg || !out) return failf(VTTS_ERR_INVALID, "null argument");
-    if (cfg->sample_rate < VTTS_LIMITER_MIN_RATE || cfg->sample_rate > VTTS_LIMITER_MAX_RATE)
-        return failf(VTTS_ERR_INVALID, "sample_rate must be in %d .. %d (got %d)", VTTS_LIMITER_MIN_RATE, VTTS_LIMITER_MAX_RATE, cfg->sample_rate);
-    if (!(cfg->lookahead_ms > 0.0f) || !(cfg->lookahead_ms <= (float)VTTS_LIMITER_MAX_LOOKAHEAD_MS))
-        return failf(VTTS_ERR_INVALID, "lookahead_ms must be above 0 and at most %g (got %g)", VTTS_LIMITER_MAX_LOOKAHEAD_MS, (double)cfg->lookahead_ms);
     auto* h = new (std::nothrow) vtts_limiter();
     if (!h) return failf(VTTS_ERR_NOMEM, "host allocation failed");
-    ad::Design d;
-    char why[160];
-    if (ad::design(cfg->sample_rate, OS * cfg->sample_rate, d, why) != 0 || d.L != OS || d.M != 1 || d.kp4 != KP) {
+    if (int rc = configure(cfg, h->taps, h->W)) {
         delete h;
-        return failf(VTTS_ERR_INVALID, "%s", why[0] ? why : "the 4x design does not have the shape the kernel expects");
+        return rc;
     }
-    for (int p = 0; p < OS; ++p)
-        for (int i = 0; i < KP; ++i) h->taps.t[p][i] = ad::table_at(d, p, i);
-    const int W = (int)std::floor((double)cfg->sample_rate * (double)cfg->lookahead_ms / 1000.0 + 0.5);
-    h->W = W < 1 ? 1 : W;
     h->rate = cfg->sample_rate;
     h->device = device;
     *out = h;
@@ -457,7 +354,7 @@ VTTS_API int vtts_limiter_true_peak(vtts_limiter* h, const void* wav_dev, int dt
                                     float* true_peak_dev, float* envelope_dev, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !true_peak_dev) return failf(VTTS_ERR_INVALID, "null argument");
     int64_t longest = 0;
-    if (int rc = check_rows("true_peak", wav_dev, dtype, N, S_stride, lengths, &longest)) return rc;
+    if (int rc = check_rows("true_peak", wav_dev, dtype, N, S_stride, lengths, TILE, &longest)) return rc;
     const Layout l = layout(N, longest);
     if (int rc = check_workspace(workspace, workspace_bytes, l)) return rc;
     return run_envelope(h, wav_dev, dtype, N, S_stride, lengths, longest, l, static_cast<char*>(workspace), false, envelope_dev, true_peak_dev, nullptr,
@@ -484,7 +381,7 @@ VTTS_API int vtts_limiter_apply(vtts_limiter* h, const void* wav_dev, int dtype,
     if (out_dtype != VTTS_AUDIO_F32 && out_dtype != VTTS_AUDIO_PCM16)
         return failf(VTTS_ERR_INVALID, "apply: out_dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", out_dtype);
     int64_t longest = 0;
-    if (int rc = check_rows("apply", wav_dev, dtype, N, S_stride, lengths, &longest)) return rc;
+    if (int rc = check_rows("apply", wav_dev, dtype, N, S_stride, lengths, TILE, &longest)) return rc;
     if (!std::isfinite(ceiling_dbtp)) return failf(VTTS_ERR_INVALID, "apply: ceiling_dbtp must be finite (got %g)", ceiling_dbtp);
     if (O_stride < 0 || (O_stride > 0 && O_stride < longest))
         return failf(VTTS_ERR_SHAPE, "O_stride = %lld is below the longest row's %lld samples", (long long)O_stride, (long long)longest);
@@ -523,7 +420,7 @@ VTTS_API int vtts_limiter_apply(vtts_limiter* h, const void* wav_dev, int dtype,
         a.o_stride = O_stride;
         a.c = (float)std::pow(10.0, (double)ceiling_dbtp / 20.0);
         a.W = h->W;
-        a.nb = apply_buf_floats(h->W);
+        a.nb = gain_buf_floats(h->W);
         if (tiles > 0) {
             const dim3 grid(tiles, (unsigned)nr);
             hipError_t e;

@@ -23,35 +23,20 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_limstream.h"
-#include "audio_design.h"
 #include "limiter_common.h"
 #include "limstream_host.h"
+#include "stream_rows_host.h"
 #include "vtts_internal.h"
 
 using vtts::failf;
-namespace ad = vtts_audio_design;
 namespace lh = vtts_limstream_host;
-using vtts_limiter_dev::from_float;
-using vtts_limiter_dev::KP;
-using vtts_limiter_dev::LEAD;
-using vtts_limiter_dev::LimTaps;
-using vtts_limiter_dev::OS;
-using vtts_limiter_dev::padded;
-using vtts_limiter_dev::req_of;
-using vtts_limiter_dev::to_float;
+using namespace vtts_limiter_dev;  // (the tiling constants among them)
 
 namespace {
 
-constexpr int TILE = VTTS_LIMITER_TILE;
-constexpr int RUN = VTTS_LIMITER_RUN;
-constexpr int THREADS = 256;
 constexpr int ROWS_PER_LAUNCH = VTTS_LIMSTREAM_ROWS_PER_LAUNCH;
-constexpr int MAX_W = 960;
-static_assert(THREADS * RUN == TILE, "one lane per run of the mean");
 static_assert(LEAD == lh::LEAD && KP == lh::LEAD + lh::TRAIL + 1, "a phase reads x[n - 27 .. n + 24]");
 
-// floats of one of the two gain buffers: limiter.hip's (req over TILE + 4 W, or held over TILE + 2 W at word j + j / 16)
-constexpr int gain_buf_floats(int W) { return (TILE + 4 * W + (TILE + 2 * W) / RUN + 4 + 3) / 4 * 4; }
 // staged samples: x[t0 - 2 W - 27 .. t0 + TILE + 2 W + 24], and what the last group of four reads past it
 constexpr int span_floats(int W) { return TILE + 4 * W + KP + 4; }
 constexpr int lds_bytes(int W) { return (span_floats(W) + 2 * gain_buf_floats(W) + TILE) * (int)sizeof(float); }
@@ -125,7 +110,7 @@ __global__ __launch_bounds__(THREADS) void lim_stream_k(const LsArgs a, const Li
     float* nxt = cur + a.nb;
     float* rq = nxt + a.nb;
     const int liveR = (live + RUN - 1) / RUN * RUN;  // whole runs: past the row's end (its last push only) they repeat its last sample
-    const int Lw = 2 * W + 1, nR = liveR + 4 * W, nH = liveR + 2 * W;
+    const int nR = liveR + 4 * W;
     const int nP = (live + 4 * W + 3) / 4 * 4;  // p[t0 - 2 W + k], k < nP
     const float g = row.g, c = a.c;
     const long long top = last ? Rn - 1 : 0x7fffffffffffLL;  // the row's last sample, once it is known
@@ -143,26 +128,12 @@ __global__ __launch_bounds__(THREADS) void lim_stream_k(const LsArgs a, const Li
     // ---- 2. p into nxt, four samples a lane and pass: lim_env_k's chains
     float mx = 0.0f;
     for (int i = 4 * tid; i < nP; i += 4 * THREADS) {
-        float xv[KP + 4];
-#pragma unroll
-        for (int q = 0; q < (KP + 4) / 4; ++q) {
-            const float4 v = lds4[(i >> 2) + q];
-            xv[4 * q + 0] = v.x, xv[4 * q + 1] = v.y, xv[4 * q + 2] = v.z, xv[4 * q + 3] = v.w;
-        }
         float pk[4];
+        true_peak4(lds4, i, tp, pk);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            float p = fabsf(xv[s + LEAD]);
-#pragma unroll
-            for (int r = 0; r < OS; ++r) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int k = 0; k < KP; ++k) acc = fmaf(xv[s + k], tp.t[r][k], acc);
-                p = fmaxf(p, fabsf(acc));
-            }
-            pk[s] = p;
             const int e = i + s - 2 * W;  // the tile's own samples are final by the emit rule
-            if (e >= 0 && e < live) mx = fmaxf(mx, p);
+            if (e >= 0 && e < live) mx = fmaxf(mx, pk[s]);
         }
         *reinterpret_cast<float4*>(nxt + i) = make_float4(pk[0], pk[1], pk[2], pk[3]);
     }
@@ -192,62 +163,22 @@ __global__ __launch_bounds__(THREADS) void lim_stream_k(const LsArgs a, const Li
 #pragma clang loop vectorize(disable)  // (the loop vectoriser would pair the multiplies into v_pk_mul_f32: build.py)
         for (int i = tid; i < live; i += THREADS) out[i] = from_float<TO>(xc[i] * g);
     } else {
-        // ---- 3b. cur[k] = min req over `win` samples from k, win = 1, 2, 4, .. while 2 win <= Lw
-        int win = 1, ncur = nR;
-        while (2 * win <= Lw) {
-            ncur -= win;
-            for (int k = tid; k < ncur; k += THREADS) nxt[k] = fminf(cur[k], cur[k + win]);
-            __syncthreads();
-            float* t = cur;
-            cur = nxt;
-            nxt = t;
-            win *= 2;
-        }
-        // held[t0 - W + j] at nxt[padded(j)], j < nH: the window of the CLAMPED sample
-        for (int j = tid; j < nH; j += THREADS) {
-            const long long m = min(max(t0 - W + j, 0LL), top);
-            const int jc = (int)(m - (t0 - W));
-            nxt[padded(j)] = fminf(cur[jc], cur[jc + Lw - win]);
-        }
-        __syncthreads();
-        // ---- 3c. the mean of held[n - W .. n + W]: fp64, the first sample of a run from scratch, the others by sliding
-        {
-            const float* H = nxt;
-            const int i0 = RUN * tid;
-            if (i0 < live) {
-                double s = 0.0;
-                for (int k = 0; k < Lw; ++k) s += (double)H[padded(i0 + k)];
-                const double dl = (double)Lw;
-                cur[i0] = (float)(s / dl);
-                for (int t = 1; t < RUN; ++t) {
-                    const int n = i0 + t;
-                    s = (s + (double)H[padded(n + 2 * W)]) - (double)H[padded(n - 1)];
-                    cur[n] = (float)(s / dl);
-                }
-            }
-        }
-        __syncthreads();
+        // ---- 3b./3c. the mean of the sliding minimum, for the tile's samples: lim_apply_k's
+        const float* mean = smooth_gains(cur, nxt, nR, W, t0, top, liveR + 2 * W, live, tid);
         // ---- 3d. a, y, the store
 #pragma clang loop vectorize(disable)  // (the loop vectoriser would pair the multiplies into v_pk_mul_f32: build.py)
         for (int i = tid; i < live; i += THREADS) {
-            const float av = fminf(rq[i], cur[i]);
+            const float av = fminf(rq[i], mean[i]);
             amin = fminf(amin, av);
             out[i] = from_float<TO>((xc[i] * g) * av);
         }
     }
 
     // ---- 4. the tile's max p and min a
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, o));
-        amin = fminf(amin, __shfl_xor(amin, o));
-    }
+    mx = wave_extreme<false>(mx), amin = wave_extreme<true>(amin);
     if ((tid & 63) == 0) wred[0][tid >> 6] = mx, wred[1][tid >> 6] = amin;
     __syncthreads();
-    if (tid == 0) {
-        slots[2 * blockIdx.x] = fmaxf(fmaxf(wred[0][0], wred[0][1]), fmaxf(wred[0][2], wred[0][3]));
-        slots[2 * blockIdx.x + 1] = fminf(fminf(wred[1][0], wred[1][1]), fminf(wred[1][2], wred[1][3]));
-    }
+    if (tid == 0) slots[2 * blockIdx.x] = extreme4<false>(wred[0]), slots[2 * blockIdx.x + 1] = extreme4<true>(wred[1]);
 }
 
 // One wave per row of the push: the tiles' slots into the slot's running results.  A row's first push (R = 0) starts them over.
@@ -263,11 +194,7 @@ __global__ __launch_bounds__(64) void lim_stream_merge_k(const LsArgs a, const L
         vmax = fmaxf(vmax, slots[2 * t]);
         vmin = fminf(vmin, slots[2 * t + 1]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        vmin = fminf(vmin, __shfl_xor(vmin, o));
-    }
+    vmax = wave_extreme<false>(vmax), vmin = wave_extreme<true>(vmin);
     if (lane == 0) {
         float* res = a.results + 3 * (size_t)row.slot;
         if (row.R > 0) {
@@ -279,8 +206,6 @@ __global__ __launch_bounds__(64) void lim_stream_merge_k(const LsArgs a, const L
         res[2] = row.g;
     }
 }
-
-constexpr int64_t MAX_S = 0x7fffffff - TILE;
 
 template <typename TI, typename TO>
 hipError_t launch_stream(const LsArgs& a, const LimTaps& taps, const LsRows& rows, dim3 grid, hipStream_t s, vtts::DynLdsOnce& once) {
@@ -294,52 +219,39 @@ hipError_t launch_stream(const LsArgs& a, const LimTaps& taps, const LsRows& row
 }  // namespace
 
 struct vtts_limstream {
-    int rate = 0, W = 0, rows = 0, max_chunk = 0;
+    int rate = 0, W = 0;
     float c = 0.0f;
     lh::Layout lay;
     LimTaps taps;
-    std::vector<int64_t> R, F;
+    vtts_stream_rows::Cursors cur;
     std::vector<float> g;
-    std::vector<unsigned char> closed, parity;
-    std::vector<unsigned> seen;  // the push that last named a slot
-    unsigned pushes = 0;
     vtts::DynLdsOnce lds[4];
 };
 
 VTTS_API int vtts_limstream_create(const vtts_limiter_cfg* cfg, int device, int rows, int32_t max_chunk, float ceiling_dbtp, vtts_limstream** out) {
     (void)device;  // (the handle owns nothing on a device: the calls run on the caller's current one)
     if (!cfg || !out) return failf(VTTS_ERR_INVALID, "null argument");
-    if (cfg->sample_rate < VTTS_LIMITER_MIN_RATE || cfg->sample_rate > VTTS_LIMITER_MAX_RATE)
-        return failf(VTTS_ERR_INVALID, "sample_rate must be in %d .. %d (got %d)", VTTS_LIMITER_MIN_RATE, VTTS_LIMITER_MAX_RATE, cfg->sample_rate);
-    if (!(cfg->lookahead_ms > 0.0f) || !(cfg->lookahead_ms <= (float)VTTS_LIMITER_MAX_LOOKAHEAD_MS))
-        return failf(VTTS_ERR_INVALID, "lookahead_ms must be above 0 and at most %g (got %g)", VTTS_LIMITER_MAX_LOOKAHEAD_MS, (double)cfg->lookahead_ms);
+    LimTaps taps;
+    int W = 0;
+    if (int rc = configure(cfg, taps, W)) return rc;
     if (rows < 1 || rows > (1 << 24)) return failf(VTTS_ERR_INVALID, "rows must be in 1 .. 2^24 (got %d)", rows);
     if (max_chunk < 1 || max_chunk > VTTS_LIMSTREAM_MAX_CHUNK)
         return failf(VTTS_ERR_INVALID, "max_chunk must be in 1 .. %d (got %d)", VTTS_LIMSTREAM_MAX_CHUNK, max_chunk);
     if (!std::isfinite(ceiling_dbtp)) return failf(VTTS_ERR_INVALID, "ceiling_dbtp must be finite (got %g)", ceiling_dbtp);
-    ad::Design d;
-    char why[160];
-    if (ad::design(cfg->sample_rate, OS * cfg->sample_rate, d, why) != 0 || d.L != OS || d.M != 1 || d.kp4 != KP)
-        return failf(VTTS_ERR_INVALID, "%s", why[0] ? why : "the 4x design does not have the shape the kernel expects");
     auto* h = new (std::nothrow) vtts_limstream();
     if (!h) return failf(VTTS_ERR_NOMEM, "host allocation failed");
-    for (int p = 0; p < OS; ++p)
-        for (int i = 0; i < KP; ++i) h->taps.t[p][i] = ad::table_at(d, p, i);
-    const int W = (int)std::floor((double)cfg->sample_rate * (double)cfg->lookahead_ms / 1000.0 + 0.5);
-    h->W = W < 1 ? 1 : W;
+    h->taps = taps;
+    h->W = W;
     h->rate = cfg->sample_rate;
-    h->rows = rows;
-    h->max_chunk = max_chunk;
     h->c = (float)std::pow(10.0, (double)ceiling_dbtp / 20.0);
     h->lay = lh::layout(h->W, rows, max_chunk);
+    bool ok = h->cur.init(rows, max_chunk);
     try {
-        h->R.assign(rows, 0);
-        h->F.assign(rows, 0);
         h->g.assign(rows, 1.0f);
-        h->closed.assign(rows, 0);
-        h->parity.assign(rows, 0);
-        h->seen.assign(rows, 0);
     } catch (const std::bad_alloc&) {
+        ok = false;
+    }
+    if (!ok) {
         delete h;
         return failf(VTTS_ERR_NOMEM, "host allocation failed");
     }
@@ -363,10 +275,9 @@ VTTS_API int vtts_limstream_state_bytes(const vtts_limstream* h, size_t* bytes) 
 
 VTTS_API int vtts_limstream_reset(vtts_limstream* h, int row, float gain) {
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
-    if (row < 0 || row >= h->rows) return failf(VTTS_ERR_INVALID, "reset: row %d is outside 0 .. %d", row, h->rows - 1);
+    if (!h->cur.has(row)) return failf(VTTS_ERR_INVALID, "reset: row %d is outside 0 .. %d", row, h->cur.rows - 1);
     if (!std::isfinite(gain)) return failf(VTTS_ERR_INVALID, "reset: the gain must be finite (got %g)", gain);
-    h->R[row] = h->F[row] = 0;
-    h->closed[row] = 0;
+    h->cur.reset(row);
     h->g[row] = gain;
     return VTTS_OK;
 }
@@ -387,27 +298,13 @@ VTTS_API int vtts_limstream_push(vtts_limstream* h, void* state_dev, const void*
     if (dtype != VTTS_AUDIO_F32 && dtype != VTTS_AUDIO_PCM16) return failf(VTTS_ERR_INVALID, "push: dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", dtype);
     if (out_dtype != VTTS_AUDIO_F32 && out_dtype != VTTS_AUDIO_PCM16)
         return failf(VTTS_ERR_INVALID, "push: out_dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", out_dtype);
-    if (n < 1 || n > h->rows) return failf(VTTS_ERR_INVALID, "push: n must be in 1 .. rows = %d (got %d)", h->rows, n);
+    vtts_stream_rows::Cursors& cu = h->cur;
+    if (n < 1 || n > cu.rows) return failf(VTTS_ERR_INVALID, "push: n must be in 1 .. rows = %d (got %d)", cu.rows, n);
     if (c_stride < 0) return failf(VTTS_ERR_INVALID, "push: c_stride must not be negative (got %lld)", (long long)c_stride);
     if (reinterpret_cast<uintptr_t>(state_dev) % 16) return failf(VTTS_ERR_INVALID, "push: the state must be 16-byte aligned");
-
-    // ---- every refusal before any bookkeeping changes
-    if (++h->pushes == 0) {  // (the counter wrapped: forget every earlier mark)
-        h->seen.assign(h->seen.size(), 0u);
-        h->pushes = 1;
-    }
-    const unsigned mark = h->pushes;
-    for (int i = 0; i < n; ++i) {
-        const int r = rows_host[i];
-        if (r < 0 || r >= h->rows) return failf(VTTS_ERR_INVALID, "push: rows[%d] = %d is outside 0 .. %d", i, r, h->rows - 1);
-        if (h->seen[r] == mark) return failf(VTTS_ERR_INVALID, "push: row %d is named twice", r);
-        h->seen[r] = mark;
-        if (h->closed[r]) return failf(VTTS_ERR_STATE, "push: row %d ended with its last push; reset() it first", r);
-        const int64_t cnt = counts_host[i];
-        if (cnt < 0 || cnt > h->max_chunk) return failf(VTTS_ERR_INVALID, "push: counts[%d] = %lld is outside 0 .. max_chunk = %d", i, (long long)cnt, h->max_chunk);
-        if (c_stride && cnt > c_stride) return failf(VTTS_ERR_INVALID, "push: counts[%d] = %lld is above c_stride = %lld", i, (long long)cnt, (long long)c_stride);
-        if (h->R[r] + cnt > MAX_S) return failf(VTTS_ERR_SHAPE, "push: row %d would pass 2^31 - 1 - %d samples", r, TILE);
-    }
+    // ---- every refusal before any bookkeeping changes; a row stays within MAX_S = 2^31 - 1 - TILE samples
+    char why[160];
+    if (int rc = cu.check_push(n, rows_host, counts_host, c_stride, TILE, why)) return failf(rc, "%s", why);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pin = dtype == VTTS_AUDIO_PCM16, pout = out_dtype == VTTS_AUDIO_PCM16;
@@ -430,13 +327,13 @@ VTTS_API int vtts_limstream_push(vtts_limstream* h, void* state_dev, const void*
         int in_off = 0, out_off = 0, tiles = 1;
         for (int b = 0; b < nr; ++b) {
             const int r = rows_host[r0 + b], cnt = counts_host[r0 + b], last = last_host && last_host[r0 + b] ? 1 : 0;
-            const int64_t Fn = lh::emit_rule(h->W, h->R[r], h->F[r], cnt, last);
-            const int emit = (int)(Fn - h->F[r]);
+            const int64_t Fn = lh::emit_rule(h->W, cu.R[r], cu.F[r], cnt, last);
+            const int emit = (int)(Fn - cu.F[r]);
             LsRow& q = rows.r[b];
             q.in_off = in_off;
             q.out_off = out_off;
-            q.R = (int)h->R[r];
-            q.cnt_flags = cnt << 2 | (int)h->parity[r] << 1 | last;
+            q.R = (int)cu.R[r];
+            q.cnt_flags = cnt << 2 | (int)cu.parity[r] << 1 | last;
             q.slot = r;
             q.g = h->g[r];
             in_off += cnt;
@@ -457,15 +354,7 @@ VTTS_API int vtts_limstream_push(vtts_limstream* h, void* state_dev, const void*
             e = hipGetLastError();
         }
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "limiter kernel launch failed: %s", hipGetErrorString(e));
-        for (int b = 0; b < nr; ++b) {  // the launch's rows have moved
-            const int r = rows_host[r0 + b], cnt = counts_host[r0 + b], last = last_host && last_host[r0 + b] ? 1 : 0;
-            h->F[r] += out_counts_host[r0 + b];
-            h->R[r] += cnt;
-            if (last)
-                h->closed[r] = 1;
-            else
-                h->parity[r] ^= 1;
-        }
+        cu.advance(nr, rows_host + r0, counts_host + r0, last_host ? last_host + r0 : nullptr, out_counts_host + r0);  // the launch's rows have moved
     }
     return VTTS_OK;
 }

@@ -30,9 +30,13 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_loudness.h"
 #include "loudness_design.h"
+#include "sample_convert.h"
 #include "vtts_internal.h"
 
+using vtts::check_rows;
 using vtts::failf;
+using vtts_sample::from_float;
+using vtts_sample::to_float;
 namespace ld = vtts_loudness_design;
 
 namespace {
@@ -88,23 +92,6 @@ struct ApplyArgs {
     long long s_stride;
     long long o_stride;  // 0 = packed
 };
-
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
-
-template <typename TO>
-__device__ __forceinline__ TO from_float(float v);
-template <>
-__device__ __forceinline__ float from_float<float>(float v) {
-    return v;
-}
-// audio.hip's rule (viettts_amd/wavio.py float_to_pcm16): rint(clip(x, -1, 1) * 32767) in double, NaN -> 0
-template <>
-__device__ __forceinline__ short from_float<short>(float v) {
-    if (!(v == v)) return 0;
-    const float c = fminf(fmaxf(v, -1.0f), 1.0f);
-    return (short)(int)rint((double)c * 32767.0);
-}
 
 // r = m s, m row-major 4 x 4
 __device__ __forceinline__ void matvec(const float* m, const float (&s)[4], float (&r)[4]) {
@@ -361,21 +348,6 @@ __global__ __launch_bounds__(THREADS) void loud_apply_k(const ApplyArgs a, const
     }
 }
 
-int check_rows(const char* what, const void* wav, int dtype, int N, int64_t S_stride, const int32_t* lengths, int64_t* longest) {
-    if (!wav) return failf(VTTS_ERR_INVALID, "null argument");
-    if (dtype != VTTS_AUDIO_F32 && dtype != VTTS_AUDIO_PCM16) return failf(VTTS_ERR_INVALID, "%s: dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", what, dtype);
-    if (N <= 0) return failf(VTTS_ERR_INVALID, "%s: N must be positive (got %d)", what, N);
-    if (S_stride < 0 || S_stride > 0x7fffffff - SEGMENT) return failf(VTTS_ERR_SHAPE, "%s: S_stride must be in 0 .. 2^31 - 1 - %d (got %lld)", what, SEGMENT, (long long)S_stride);
-    int64_t m = 0;
-    for (int b = 0; b < N; ++b) {
-        const int64_t len = lengths ? lengths[b] : S_stride;
-        if (len < 0 || len > S_stride) return failf(VTTS_ERR_SHAPE, "%s: lengths[%d] = %lld is outside 0 .. S_stride = %lld", what, b, (long long)len, (long long)S_stride);
-        if (len > m) m = len;
-    }
-    *longest = m;
-    return VTTS_OK;
-}
-
 }  // namespace
 
 struct vtts_loudness {
@@ -426,7 +398,7 @@ VTTS_API int vtts_loudness_measure(vtts_loudness* h, const void* wav_dev, int dt
     if (!h || !integrated_dev || !momentary_max_dev || !sample_peak_dev || !n_blocks_dev || !n_gated_dev || !workspace)
         return failf(VTTS_ERR_INVALID, "null argument");
     int64_t longest = 0;
-    if (int rc = check_rows("measure", wav_dev, dtype, N, S_stride, lengths, &longest)) return rc;
+    if (int rc = check_rows("measure", wav_dev, dtype, N, S_stride, lengths, SEGMENT, &longest)) return rc;
     if (momentary_dev && J_stride < ld::num_blocks(h->d, longest))
         return failf(VTTS_ERR_SHAPE, "J_stride = %lld is below the longest row's %lld blocks", (long long)J_stride, (long long)ld::num_blocks(h->d, longest));
     const ld::Layout l = ld::layout(h->d, N, longest);
@@ -492,7 +464,7 @@ VTTS_API int vtts_loudness_normalize(vtts_loudness* h, const void* wav_dev, int 
     if (out_dtype != VTTS_AUDIO_F32 && out_dtype != VTTS_AUDIO_PCM16)
         return failf(VTTS_ERR_INVALID, "normalize: out_dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", out_dtype);
     int64_t longest = 0;
-    if (int rc = check_rows("normalize", wav_dev, dtype, N, S_stride, lengths, &longest)) return rc;
+    if (int rc = check_rows("normalize", wav_dev, dtype, N, S_stride, lengths, SEGMENT, &longest)) return rc;
     if (!std::isfinite(target_lufs) || !std::isfinite(ceiling_dbfs) || !std::isfinite(max_gain_db))
         return failf(VTTS_ERR_INVALID, "normalize: target_lufs, ceiling_dbfs and max_gain_db must be finite (got %g, %g, %g)", target_lufs, ceiling_dbfs, max_gain_db);
     if (O_stride < 0 || (O_stride > 0 && O_stride < longest))

@@ -32,11 +32,13 @@
 
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_mel.h"
+#include "sample_convert.h"
 #include "vtts_internal.h"
 
 using vtts::check_blob;
 using vtts::failf;
 using vtts::upload_blob;
+using vtts_sample::to_float;
 
 namespace {
 
@@ -111,9 +113,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void mel_fused_k(const MelArgs a, const MelRows rows) {

@@ -33,6 +33,7 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_mel.h"
 #include "../../include/vtts_pitch.h"
+#include "sample_convert.h"
 #include "vtts_internal.h"
 
 // The contract's operations are single fp32 operations: nothing in this file may be fused into an FMA.  The pragma covers this file's own
@@ -41,6 +42,7 @@
 #pragma clang fp contract(off)
 
 using vtts::failf;
+using vtts_sample::to_float;
 
 namespace {
 
@@ -84,9 +86,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
 
 // one step of a chain: s + (a - y)^2, three rounded operations
 __device__ __forceinline__ float step(float s, float a, float y) {

@@ -24,6 +24,7 @@
 #include "audio_common.h"
 #include "audio_design.h"
 #include "rsstream_host.h"
+#include "stream_rows_host.h"
 #include "vtts_internal.h"
 
 using vtts::check_blob;
@@ -151,14 +152,11 @@ constexpr int64_t MAX_S = 0x7fffffff;
 
 struct vtts_rsstream {
     rh::Ratio ratio = {};
-    int minv = 0, span_floats = 0, rows = 0, max_chunk = 0;
+    int minv = 0, span_floats = 0;
     size_t table_bytes = 0;
     rh::Layout lay;
     const float* blob = nullptr;
-    std::vector<int64_t> R, F;
-    std::vector<unsigned char> closed, parity;
-    std::vector<unsigned> seen;  // the push that last named a slot
-    unsigned pushes = 0;
+    vtts_stream_rows::Cursors cur;
     vtts::DynLdsOnce lds[4];
 };
 
@@ -177,16 +175,8 @@ VTTS_API int vtts_rsstream_create(const vtts_audio_cfg* cfg, int device, int row
     h->minv = d.minv;
     h->span_floats = d.span_floats;
     h->table_bytes = d.table.size() * sizeof(float);
-    h->rows = rows;
-    h->max_chunk = max_chunk;
     h->lay = rh::layout(h->ratio, rows);
-    try {
-        h->R.assign(rows, 0);
-        h->F.assign(rows, 0);
-        h->closed.assign(rows, 0);
-        h->parity.assign(rows, 0);
-        h->seen.assign(rows, 0);
-    } catch (const std::bad_alloc&) {
+    if (!h->cur.init(rows, max_chunk)) {
         delete h;
         return failf(VTTS_ERR_NOMEM, "host allocation failed");
     }
@@ -225,18 +215,17 @@ VTTS_API int vtts_rsstream_bind_packed(vtts_rsstream* h, void* dev_blob, size_t 
 
 VTTS_API int vtts_rsstream_reset(vtts_rsstream* h, int row) {
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
-    if (row < 0 || row >= h->rows) return failf(VTTS_ERR_INVALID, "reset: row %d is outside 0 .. %d", row, h->rows - 1);
-    h->R[row] = h->F[row] = 0;
-    h->closed[row] = 0;
+    if (!h->cur.has(row)) return failf(VTTS_ERR_INVALID, "reset: row %d is outside 0 .. %d", row, h->cur.rows - 1);
+    h->cur.reset(row);
     return VTTS_OK;
 }
 
 VTTS_API int vtts_rsstream_cursor(const vtts_rsstream* h, int row, int64_t* received, int64_t* emitted, int* closed) {
     if (!h) return failf(VTTS_ERR_INVALID, "null argument");
-    if (row < 0 || row >= h->rows) return failf(VTTS_ERR_INVALID, "cursor: row %d is outside 0 .. %d", row, h->rows - 1);
-    if (received) *received = h->R[row];
-    if (emitted) *emitted = h->F[row];
-    if (closed) *closed = h->closed[row];
+    if (!h->cur.has(row)) return failf(VTTS_ERR_INVALID, "cursor: row %d is outside 0 .. %d", row, h->cur.rows - 1);
+    if (received) *received = h->cur.R[row];
+    if (emitted) *emitted = h->cur.F[row];
+    if (closed) *closed = h->cur.closed[row];
     return VTTS_OK;
 }
 
@@ -257,34 +246,24 @@ VTTS_API int vtts_rsstream_push(vtts_rsstream* h, void* state_dev, const void* c
     if (dtype != VTTS_AUDIO_F32 && dtype != VTTS_AUDIO_PCM16) return failf(VTTS_ERR_INVALID, "push: dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", dtype);
     if (out_dtype != VTTS_AUDIO_F32 && out_dtype != VTTS_AUDIO_PCM16)
         return failf(VTTS_ERR_INVALID, "push: out_dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", out_dtype);
-    if (n < 1 || n > h->rows) return failf(VTTS_ERR_INVALID, "push: n must be in 1 .. rows = %d (got %d)", h->rows, n);
+    vtts_stream_rows::Cursors& cu = h->cur;
+    if (n < 1 || n > cu.rows) return failf(VTTS_ERR_INVALID, "push: n must be in 1 .. rows = %d (got %d)", cu.rows, n);
     if (c_stride < 0) return failf(VTTS_ERR_INVALID, "push: c_stride must not be negative (got %lld)", (long long)c_stride);
     if (reinterpret_cast<uintptr_t>(state_dev) % 16) return failf(VTTS_ERR_INVALID, "push: the state must be 16-byte aligned");
     const rh::Ratio& rt = h->ratio;
     if (!rt.identity && !h->blob) return failf(VTTS_ERR_STATE, "push() before bind_packed()");
 
-    // ---- every refusal before any bookkeeping changes
-    if (++h->pushes == 0) {  // (the counter wrapped: forget every earlier mark)
-        h->seen.assign(h->seen.size(), 0u);
-        h->pushes = 1;
-    }
-    const unsigned mark = h->pushes;
-    for (int i = 0; i < n; ++i) {
-        const int r = rows_host[i];
-        if (r < 0 || r >= h->rows) return failf(VTTS_ERR_INVALID, "push: rows[%d] = %d is outside 0 .. %d", i, r, h->rows - 1);
-        if (h->seen[r] == mark) return failf(VTTS_ERR_INVALID, "push: row %d is named twice", r);
-        h->seen[r] = mark;
-        if (h->closed[r]) return failf(VTTS_ERR_STATE, "push: row %d ended with its last push; reset() it first", r);
-        const int64_t cnt = counts_host[i];
-        if (cnt < 0 || cnt > h->max_chunk) return failf(VTTS_ERR_INVALID, "push: counts[%d] = %lld is outside 0 .. max_chunk = %d", i, (long long)cnt, h->max_chunk);
-        if (c_stride && cnt > c_stride) return failf(VTTS_ERR_INVALID, "push: counts[%d] = %lld is above c_stride = %lld", i, (long long)cnt, (long long)c_stride);
-        if (h->R[r] + cnt > MAX_S) return failf(VTTS_ERR_SHAPE, "push: row %d would pass 2^31 - 1 samples", r);
+    // ---- every refusal before any bookkeeping changes; a row may reach MAX_S = 2^31 - 1 samples
+    // the contract's bounds, row by row: F is the function of R the kernel derives, and the next history fits its buffer
+    auto history_bound = [&](int i, int r, int64_t cnt, char (&why)[160]) {
         const int last = last_host && last_host[i] ? 1 : 0;
-        const int64_t Rn = h->R[r] + cnt, Fn = rh::emit_rule(rt, h->R[r], h->F[r], cnt, last);
-        // the contract's bounds: F is the function of R the kernel derives, and the next history fits its buffer
-        if (h->F[r] != rh::emitted_of(rt, h->R[r]) || (!rt.identity && !last && Rn - rh::hist_base(rt, Fn) > rt.kp4 - 1))
-            return failf(VTTS_ERR_STATE, "push: row %d's cursors break the history bound (R %lld, F %lld)", r, (long long)h->R[r], (long long)h->F[r]);
-    }
+        const int64_t Rn = cu.R[r] + cnt, Fn = rh::emit_rule(rt, cu.R[r], cu.F[r], cnt, last);
+        if (cu.F[r] == rh::emitted_of(rt, cu.R[r]) && (rt.identity || last || Rn - rh::hist_base(rt, Fn) <= rt.kp4 - 1)) return (int)VTTS_OK;
+        snprintf(why, sizeof why, "push: row %d's cursors break the history bound (R %lld, F %lld)", r, (long long)cu.R[r], (long long)cu.F[r]);
+        return (int)VTTS_ERR_STATE;
+    };
+    char why[160];
+    if (int rc = cu.check_push(n, rows_host, counts_host, c_stride, 0, history_bound, why)) return failf(rc, "%s", why);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pin = dtype == VTTS_AUDIO_PCM16, pout = out_dtype == VTTS_AUDIO_PCM16;
@@ -307,12 +286,12 @@ VTTS_API int vtts_rsstream_push(vtts_rsstream* h, void* state_dev, const void* c
         int64_t out_off = 0, tiles = 1;
         for (int b = 0; b < nr; ++b) {
             const int r = rows_host[r0 + b], cnt = counts_host[r0 + b], last = last_host && last_host[r0 + b] ? 1 : 0;
-            const int64_t emit = rh::emit_rule(rt, h->R[r], h->F[r], cnt, last) - h->F[r];  // < max_emit(): fits int32 by max_chunk and MAX_R
+            const int64_t emit = rh::emit_rule(rt, cu.R[r], cu.F[r], cnt, last) - cu.F[r];  // < max_emit(): fits int32 by max_chunk and MAX_R
             RsRow& q = rows.r[b];
             q.out_off = out_off;
             q.in_off = in_off;
-            q.R = (int)h->R[r];
-            q.cnt_flags = cnt << 2 | (int)h->parity[r] << 1 | last;
+            q.R = (int)cu.R[r];
+            q.cnt_flags = cnt << 2 | (int)cu.parity[r] << 1 | last;
             q.slot = r;
             in_off += cnt;
             out_off += emit;
@@ -328,15 +307,7 @@ VTTS_API int vtts_rsstream_push(vtts_rsstream* h, void* state_dev, const void* c
         else
             e = pout ? launch_stream<float, short>(a, rows, grid, lds, s, h->lds[1]) : launch_stream<float, float>(a, rows, grid, lds, s, h->lds[0]);
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "resampler kernel launch failed: %s", hipGetErrorString(e));
-        for (int b = 0; b < nr; ++b) {  // the launch's rows have moved
-            const int r = rows_host[r0 + b], cnt = counts_host[r0 + b], last = last_host && last_host[r0 + b] ? 1 : 0;
-            h->F[r] += out_counts_host[r0 + b];
-            h->R[r] += cnt;
-            if (last)
-                h->closed[r] = 1;
-            else
-                h->parity[r] ^= 1;
-        }
+        cu.advance(nr, rows_host + r0, counts_host + r0, last_host ? last_host + r0 : nullptr, out_counts_host + r0);  // the launch's rows have moved
     }
     return VTTS_OK;
 }

@@ -28,6 +28,7 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_stoi.h"
+#include "sample_convert.h"
 #include "vtts_internal.h"
 
 // include/vtts_stoi.h states single rounded fp32 products (p = fl32(x w)) that the keep mask is compared on with ==: no a * b + c of this
@@ -35,6 +36,7 @@
 #pragma clang fp contract(off)
 
 using vtts::failf;
+using vtts_sample::to_float;
 
 namespace {
 
@@ -83,9 +85,6 @@ struct StoiArgs {               // every pointer at the launch's first row
     float* estoi_series;
     double clip;                // 1 + 10^(15 / 20)
 };
-
-__device__ __forceinline__ float to_float(float v) { return v; }
-__device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
 
 __host__ __device__ __forceinline__ long long num_frames(long long S) { return S > FRAME ? (S - FRAME + HOP - 1) / HOP : 0; }
 

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 
 #define VTTS_API extern "C" __attribute__((visibility("default")))
@@ -38,6 +39,25 @@ inline int upload_blob(void* dev_blob, const void* host, size_t bytes, hipStream
     hipError_t e = hipMemcpyAsync(dev_blob, host, bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return failf(VTTS_ERR_HIP, "copying %s failed: %s", what, hipGetErrorString(e));
+    return VTTS_OK;
+}
+
+// The one rule for a batch of waveform rows (the limiter's and the loudness meter's calls): fp32 or PCM16, N >= 1, a pitch that leaves `margin`
+// samples (the stage's tile) below 2^31, every length within the pitch.  *longest = the longest row.  Host arithmetic only.
+inline int check_rows(const char* what, const void* wav, int dtype, int N, int64_t S_stride, const int32_t* lengths, int margin, int64_t* longest) {
+    if (!wav) return failf(VTTS_ERR_INVALID, "null argument");
+    if (dtype != VTTS_AUDIO_F32 && dtype != VTTS_AUDIO_PCM16) return failf(VTTS_ERR_INVALID, "%s: dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", what, dtype);
+    if (N <= 0) return failf(VTTS_ERR_INVALID, "%s: N must be positive (got %d)", what, N);
+    if (S_stride < 0 || S_stride > 0x7fffffff - margin)
+        return failf(VTTS_ERR_SHAPE, "%s: S_stride must be in 0 .. 2^31 - 1 - %d (got %lld)", what, margin, (long long)S_stride);
+    int64_t m = 0;
+    for (int b = 0; b < N; ++b) {
+        const int64_t len = lengths ? lengths[b] : S_stride;
+        if (len < 0 || len > S_stride)
+            return failf(VTTS_ERR_SHAPE, "%s: lengths[%d] = %lld is outside 0 .. S_stride = %lld", what, b, (long long)len, (long long)S_stride);
+        if (len > m) m = len;
+    }
+    *longest = m;
     return VTTS_OK;
 }
 
