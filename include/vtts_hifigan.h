@@ -185,6 +185,10 @@ int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const float* x_de
  *                 the split-operand one exists; VTTS_F32 has none), VTTS_ERR_INVALID elsewhere;
  *             1 = three fused-pair launches as a forward issues them: the first two store into scratch, the third carries
  *                 slope_out / acc_add / div into y_dev; no stage-4 tail is attached
+ *             2 = VTTS_F32 / VTTS_BF16X3 only: the six convolutions one by one, as a forward issues them where no fused kernel is taken
+ *                 (c1 into scratch; c2 with the pair's input as residual, into scratch for pairs 0 and 1 and into y_dev for pair 2; the last
+ *                 launch carries acc_add / div): the fp32 MFMA convolution where it covers the shape (L a multiple of 4), the generic
+ *                 kernel elsewhere and under "kernels" = 1; VTTS_ERR_INVALID on a VTTS_BF16 handle
  *   rows_dev  NULL, or [B] int32 on the device: utterance b's valid rows of the L allocated (clamped into [0, L] by the kernels, as the frame
  *             counts of forward_ragged): the rest reads as zero padding and is not written
  *   acc_add   1 = y_dev's content is added first; div = the MRF divisor (1 = none); slope_out = the consumer's LeakyReLU (1 = none)
@@ -192,7 +196,7 @@ int vtts_hifigan_run_pair(vtts_hifigan* h, const char* key_c1, const float* x_de
  * VTTS_BF16: arrays are fp32 channels-last [B, L, C]; x_dev and the initial y_dev are rounded to bf16 into buffers of the hook's own and the
  * result is converted back (rows no kernel writes come back as the rounded values that went in); slope_out in (0, 1]; the call synchronises.
  * VTTS_F32 / VTTS_BF16X3: arrays are [B, C, L] channel-major, y_dev is used directly, slope_out must be 1 (these engines' consumers activate on
- * load) and div != 1 needs acc_add; enqueued on `stream` (route 1 waits for the device when it frees its scratch).
+ * load) and div != 1 needs acc_add; enqueued on `stream` (routes 1 and 2 wait for the device when they free their scratch).
  * The hook allocates and frees its own scratch; options "tiles", "zigzag" and "kernels" act as in a forward.
  */
 int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, int route, const float* x_dev, const int32_t* rows_dev, int B, int L,

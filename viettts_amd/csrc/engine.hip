@@ -1593,7 +1593,8 @@ VTTS_API int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, in
     if (!h->blob) return failf(VTTS_ERR_STATE, "run_resblock() before pack()/bind_packed()");
     if (B <= 0 || L <= 0) return failf(VTTS_ERR_INVALID, "B and L must be positive");
     if (B > 65535) return failf(VTTS_ERR_INVALID, "at most 65535 utterances per launch (got %d)", B);
-    if (route != 0 && route != 1) return failf(VTTS_ERR_INVALID, "route must be 0 (the whole-ResBlock kernel) or 1 (three pair launches), got %d", route);
+    if (route != 0 && route != 1 && !(route == 2 && h->dtype == VTTS_F32))
+        return failf(VTTS_ERR_INVALID, "route must be 0 (the whole-ResBlock kernel), 1 (three pair launches) or, on an fp32 / bf16x3 handle, 2 (six convolution launches), got %d", route);
     if ((acc_add != 0 && acc_add != 1) || !(div > 0.0f) || !std::isfinite(div))
         return failf(VTTS_ERR_INVALID, "run_resblock(): acc_add must be 0 or 1 and div a positive number (got %d, %g)", acc_add, div);
     const Layer* rb = nullptr;  // rb[0..5] = c1_0, c2_0, c1_1, c2_1, c1_2, c2_2
@@ -1616,6 +1617,25 @@ VTTS_API int vtts_hifigan_run_resblock(vtts_hifigan* h, const char* key_c1_0, in
             if (!resblock_x3_runnable(h, rb, L))
                 return failf(VTTS_ERR_INVALID, "'%s': no whole-ResBlock kernel for this ResBlock on this handle (bf16x3, C = 32 / 64 / 128)", key_c1_0);
             return run_resblock_x3(h, rb, x_dev, B, L, y_dev, mode, div, st);
+        }
+        if (route == 2) {
+            // the six convolutions one by one, as mrf_f32's ROUTE_CONVS branch: c1 -> T; c2 (+ cur) -> C, the last one -> y_dev with the mode
+            DevBuf tbuf, cbuf;
+            HIP_TRY(hipMalloc(&tbuf.p, n * sizeof(float)));
+            HIP_TRY(hipMalloc(&cbuf.p, n * sizeof(float)));
+            float *tT = static_cast<float*>(tbuf.p), *tC = static_cast<float*>(cbuf.p);
+            const long CL = (long)C * L;
+            const float* cur = x_dev;
+            for (int z = 0; z < 3; ++z) {
+                int rc;
+                if ((rc = run_layer(h, rb[2 * z], Act{cur, CL, L, 1}, B, L, 0.1f, nullptr, tT, ACC_STORE, 1.f, 0, nullptr, st))) return rc;
+                const bool last = z == 2;
+                if ((rc = run_layer(h, rb[2 * z + 1], Act{tT, CL, L, 1}, B, L, 0.1f, cur, last ? y_dev : tC, last ? mode : ACC_STORE, last ? div : 1.f,
+                                    0, nullptr, st)))
+                    return rc;
+                cur = tC;
+            }
+            return VTTS_OK;
         }
         bool x3 = h->x3 && h->opt_kernels == 0, fp = h->opt_kernels == 0;  // the split-operand pair kernel, else the fp32 one, as route_f32 picks them
         for (int z = 0; z < 3; ++z) {

@@ -177,7 +177,8 @@ class Generator(NativeHandle):
     def run_resblock(self, key_c1_0: str, x: torch.Tensor, route: int = 0, rows=None, slope_out: float = 1.0, acc_add: bool = False,
                      div: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One ResBlock1 named by its ``convs1_0`` key, launched as the engine launches it (test hook): ``route`` 0 = the whole-ResBlock
-        kernel, 1 = three fused-pair launches; then ``v = rb(x) (+ out)``, ``v / div``, ``leaky_relu(v, slope_out)``.
+        kernel, 1 = three fused-pair launches, 2 (fp32 / bf16x3 handles only) = the six convolutions one by one, under the options
+        ``tiles`` and ``kernels``; then ``v = rb(x) (+ out)``, ``v / div``, ``leaky_relu(v, slope_out)``.
         bf16 handles: ``x`` fp32 ``[B, L, C]`` channels-last (``x`` and ``out`` rounded to bf16 on the way in); fp32 / bf16x3 handles:
         ``[B, C, L]``, ``slope_out`` must be 1.  ``rows``: per-utterance valid row counts (int sequence or int32 device tensor) or None.
         ``out`` is in-out (checked as in ``__call__``): rows no kernel writes keep what went in; ``acc_add`` needs it."""
