@@ -62,6 +62,11 @@ STOI_MAX_SAMPLES = 1 << 24  # include/vtts_stoi.h: VTTS_STOI_MAX_SAMPLES
 STOI_FRAMES_PER_BLOCK = 8  # include/vtts_stoi.h: VTTS_STOI_FRAMES_PER_BLOCK
 STOI_FRAME, STOI_HOP, STOI_BANDS, STOI_SEG = 256, 128, 15, 30  # include/vtts_stoi.h: VTTS_STOI_FRAME / _HOP / _BANDS / _SEG
 
+SPECTRAL_MAX_SAMPLES = 1 << 24  # include/vtts_spectral.h: VTTS_SPECTRAL_MAX_SAMPLES
+SPECTRAL_N_FFT = (256, 512, 1024, 2048)  # include/vtts_spectral.h: the transform lengths create() accepts
+SPECTRAL_MAX_FRAMES_PER_BLOCK, SPECTRAL_MAX_FRAMES_PER_BLOCK_2048 = 8, 4  # include/vtts_spectral.h: VTTS_SPECTRAL_MAX_FRAMES_PER_BLOCK[_2048]
+SPECTRAL_LDS_BUDGET = 81920  # include/vtts_spectral.h: VTTS_SPECTRAL_LDS_BUDGET
+
 LIMITER_TILE = 4096  # include/vtts_limiter.h: VTTS_LIMITER_TILE
 LIMITER_RUN = 16  # include/vtts_limiter.h: VTTS_LIMITER_RUN
 LIMITER_PHASE_TAPS = 52  # include/vtts_limiter.h: VTTS_LIMITER_PHASE_TAPS
@@ -72,6 +77,7 @@ MEL_ROWS_PER_LAUNCH = 256  # viettts_amd/csrc/mel.hip
 PITCH_ROWS_PER_LAUNCH = 256  # viettts_amd/csrc/pitch.hip
 STOI_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stoi.hip
 LOUDNESS_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/loudness.hip
+SPECTRAL_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/spectral.hip; include/vtts_spectral.h: VTTS_SPECTRAL_ROWS_PER_LAUNCH
 DTW_PAIRS_PER_LAUNCH = 128  # viettts_amd/csrc/dtw.hip: PAIRS_PER_LAUNCH
 LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
 LIMSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_limstream.h: VTTS_LIMSTREAM_ROWS_PER_LAUNCH
@@ -93,6 +99,10 @@ class PitchCfg(C.Structure):
 
 class LoudnessCfg(C.Structure):
     _fields_ = [("sample_rate", C.c_int32)]
+
+
+class SpectralCfg(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("win", C.c_int32), ("hop", C.c_int32)]
 
 
 class LimiterCfg(C.Structure):
@@ -272,6 +282,21 @@ STOI_SIGS = {
 }
 
 
+# include/vtts_spectral.h, likewise
+SPECTRAL_SIGS = {
+    "vtts_spectral_create": (C.c_int, [C.POINTER(SpectralCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_spectral_destroy": (None, [vp]),
+    "vtts_spectral_window": (C.c_int, [vp, fp]),
+    "vtts_spectral_frames_per_block": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "vtts_spectral_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_spectral_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "vtts_spectral_pack": (C.c_int, [vp, vp, sz, vp]),
+    "vtts_spectral_bind_packed": (C.c_int, [vp, vp, sz]),
+    "vtts_spectral_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_spectral_forward": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+}
+
+
 # include/vtts_limiter.h, likewise
 LIMITER_SIGS = {
     "vtts_limiter_create": (C.c_int, [C.POINTER(LimiterCfg), C.c_int, C.POINTER(vp)]),
@@ -326,6 +351,7 @@ DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
 PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
+SPECTRAL_EXPORTS = tuple(SPECTRAL_SIGS)  # include/vtts_spectral.h
 LIMITER_EXPORTS = tuple(LIMITER_SIGS)  # include/vtts_limiter.h
 LIMSTREAM_EXPORTS = tuple(LIMSTREAM_SIGS)  # include/vtts_limstream.h
 RSSTREAM_EXPORTS = tuple(RSSTREAM_SIGS)  # include/vtts_rsstream.h
@@ -382,7 +408,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

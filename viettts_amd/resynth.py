@@ -2,7 +2,7 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi] [--mrstft]
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
@@ -96,6 +96,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--loudness", type=float, default=None, help="write the result at this BS.1770 integrated loudness in LUFS (viettts_amd.loudness); the figures printed are of the result before the gain")
     ap.add_argument("--limit", action="store_true", help="with --loudness: the full gain to the target and a look-ahead limiter under -1 dBTP (viettts_amd.limiter) in place of the sample-peak cap")
     ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of the result against the input at 10 kHz (viettts_amd.stoi); NaN below 30 analysis frames")
+    ap.add_argument("--mrstft", action="store_true", help="also print the multi-resolution STFT distance and the log-spectral distance of the result against the input (viettts_amd.spectral); needs 1025 samples")
     return ap
 
 
@@ -143,6 +144,10 @@ def main(argv=None) -> None:
         from .stoi import format_result, wav_stoi
 
         print(format_result(wav_stoi(y[:, :n].contiguous(), wav[:, :n].contiguous(), rate=model_rate)))
+    if a.mrstft:
+        from .spectral import format_result as format_mrstft, wav_mrstft
+
+        print(format_mrstft(wav_mrstft(y[:, :n].contiguous(), wav[:, :n].contiguous())))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Score a vocoder checkpoint with the objective HiFi-GAN optimises, on the GPU: wav -> log-mel (``MelFilter``) -> generator ->
 (y, y_hat) through the discriminators (``Discriminators``, include/vtts_disc.h), segment by segment.
 
-    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness] [--stoi]
+    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness] [--stoi] [--mrstft]
 
 prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
 MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono (any rate but the model's is converted
@@ -10,6 +10,8 @@ generator as ``mel2wave`` reads it (``assets/hifigan/config.json`` + a Haiku pic
 ``FileNotFoundError`` without them, before any input is touched.  Forward only: nothing is trained.
 ``--f0`` adds one line: F0 RMSE in cents, voicing error and gross error of ``y_hat`` against ``y`` (``viettts_amd.pitch``), averaged over the passes.
 ``--stoi`` adds one line: STOI and ESTOI of ``y_hat`` against ``y`` (``viettts_amd.stoi``), each pass's segments laid end to end as one row.
+``--mrstft`` adds one line: the multi-resolution STFT distance (spectral convergence + log-magnitude L1 at Parallel WaveGAN's three resolutions)
+and the log-spectral distance of ``y_hat`` against ``y`` (``viettts_amd.spectral``), per segment, averaged.
 """
 from __future__ import annotations
 
@@ -26,15 +28,19 @@ MEL_WEIGHT = 45.0
 F0_KEYS = ("f0_rmse_cents", "voicing_error", "gross_error")  # what score_segments adds with a tracker
 LOUDNESS_KEYS = ("lufs_y", "lufs_y_hat")  # ... and with a meter
 STOI_KEYS = ("stoi", "estoi")  # ... and with a stoi_meter
+SPECTRAL_KEYS = ("mrstft", "sc", "logmag", "lsd")  # ... and with spectral
 
 
-def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None, stoi_meter=None, rate=None) -> dict:
+def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None, stoi_meter=None, rate=None, spectral=None) -> dict:
     """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction.
     With ``tracker`` (a ``viettts_amd.pitch.PitchTracker``) the result also holds ``f0_rmse_cents``, ``voicing_error`` and ``gross_error`` of
     ``y_hat`` against ``y`` (``pitch.f0_metrics``); with ``meter`` (a ``viettts_amd.loudness.LoudnessMeter``) ``lufs_y`` and ``lufs_y_hat``: the
     BS.1770 integrated loudness of the pass's segments laid end to end (nan when no block passes the gates); with ``stoi_meter`` (a
     ``viettts_amd.stoi.StoiMeter``) ``stoi`` and ``estoi`` of ``y_hat`` against ``y``, likewise laid end to end as one row at ``rate`` (the
-    model's without it) and converted to 10 kHz on the device (nan when the row holds no 30-frame segment)."""
+    model's without it) and converted to 10 kHz on the device (nan when the row holds no 30-frame segment); with ``spectral`` (a
+    ``viettts_amd.spectral.MultiResolutionStft``) ``mrstft``, ``sc``, ``logmag`` and ``lsd`` of ``y_hat`` against ``y``: each segment is a row
+    of its own (it must hold the largest ``n_fft / 2 + 1`` samples), the figures are the means over the segments of the means over the
+    resolutions."""
     from .resynth import default_mel_filter, log_mel_l1
 
     mf = mel_filter or default_mel_filter(generator.device)
@@ -56,6 +62,11 @@ def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, 
 
         r = wav_stoi(y.reshape(1, -1), y_hat.reshape(1, -1), rate=int(rate or NAT_FLAGS.sample_rate), meter=stoi_meter)
         out.update(stoi=float(r.stoi[0]), estoi=float(r.estoi[0]))
+    if spectral is not None:  # per segment: a segment is its own utterance to the reflection padding
+        r = spectral(y, y_hat)
+        k = float(len(r.per_resolution))
+        out.update(mrstft=float(r.mrstft.mean()), sc=float(sum(p.sc for p in r.per_resolution).mean() / k),
+                   logmag=float(sum(p.logmag for p in r.per_resolution).mean() / k), lsd=float(r.lsd.mean()))
     return out
 
 
@@ -72,6 +83,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of y_hat against y at 10 kHz (viettts_amd.stoi), each pass's segments laid end to end as "
                     "one row: the default --segment 8192 is 5120 samples or 38 frames at 10 kHz, and a pass whose row holds fewer than 30 frames "
                     "after its silent ones are dropped (one segment much shorter than 8192) gives NaN and is left out of the mean")
+    ap.add_argument("--mrstft", action="store_true", help="also print the multi-resolution STFT distance (spectral convergence + log-magnitude L1 at n_fft 1024, "
+                    "2048 and 512) and the log-spectral distance of y_hat against y (viettts_amd.spectral), per segment: --segment must be at least 1025")
     return ap
 
 
@@ -120,10 +133,15 @@ def main(argv=None) -> None:
         from .stoi import default_stoi_meter
 
         stoi_meter = default_stoi_meter(dev)
+    spectral = None
+    if a.mrstft:
+        from .spectral import default_mrstft
+
+        spectral = default_mrstft(dev)
     tot, n, f0_tot, f0_n = {}, 0, {}, {}
     for i in range(0, len(segs), a.batch):
         y = torch.from_numpy(np.stack(segs[i : i + a.batch])).to(dev)
-        r = score_segments(y, gen, disc, tracker=trk, meter=meter, stoi_meter=stoi_meter)
+        r = score_segments(y, gen, disc, tracker=trk, meter=meter, stoi_meter=stoi_meter, spectral=spectral)
         f0 = {k: r.pop(k) for k in F0_KEYS + LOUDNESS_KEYS + STOI_KEYS if k in r}
         for k, v in r.items():
             tot[k] = tot.get(k, 0.0) + v * y.shape[0]
@@ -134,6 +152,9 @@ def main(argv=None) -> None:
     m = {k: v / n for k, v in tot.items()}
     print(f"{n} segments of {a.segment} samples: adversarial {m['adv']:.4f}  feature matching {m['fm']:.4f}  log-mel L1 {m['mel']:.4f}  "
           f"adv + fm + {MEL_WEIGHT:g} * mel = {m['total']:.4f}  (discriminator loss {m['disc']:.4f})")
+    if spectral is not None:
+        print(f"spectral distance of y_hat against y, mean over the segments: multi-resolution STFT {m['mrstft']:.4f}  (SC {m['sc']:.4f} + log-mag L1 "
+              f"{m['logmag']:.4f})  LSD {m['lsd']:.2f} dB")
     if trk is not None:
         f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in F0_KEYS}
         print(f"F0 of y_hat against y, mean over the passes: RMSE {f['f0_rmse_cents']:.1f} cents  voicing error {100 * f['voicing_error']:.2f} %  "
