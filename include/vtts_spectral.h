@@ -2,7 +2,8 @@
  * vtts_spectral.h — C ABI of the batched spectral distances at ONE short-time resolution: spectral convergence and log-magnitude L1 (the two
  * parts of the multi-resolution STFT distance of Yamamoto, Song, Kim: Parallel WaveGAN, 2020) and log-spectral distance of a signal under
  * test y against the reference signal x it is sample-aligned with, and, optionally, both magnitude spectrograms: the forward magnitude STFT
- * at any of four transform lengths.  No inverse transform, no phase.  The reference project has no such stage.
+ * at any of four transform lengths.  Magnitudes only: the complex spectrum, the inverse transform and the phase are vtts_stft.h's.  The reference
+ * project has no such stage.
  *
  * One handle = one resolution {n_fft, win, hop}: n_fft in {256, 512, 1024, 2048}, 1 <= hop <= win <= n_fft; anything else is
  * VTTS_ERR_INVALID at create().  With H = n_fft / 2 and NB = H + 1 bins, for row b of x[N, S_stride] and y[N, S_stride] with S = lengths[b]

@@ -67,6 +67,10 @@ SPECTRAL_N_FFT = (256, 512, 1024, 2048)  # include/vtts_spectral.h: the transfor
 SPECTRAL_MAX_FRAMES_PER_BLOCK, SPECTRAL_MAX_FRAMES_PER_BLOCK_2048 = 8, 4  # include/vtts_spectral.h: VTTS_SPECTRAL_MAX_FRAMES_PER_BLOCK[_2048]
 SPECTRAL_LDS_BUDGET = 81920  # include/vtts_spectral.h: VTTS_SPECTRAL_LDS_BUDGET
 
+VTTS_STFT_CENTER, VTTS_STFT_MEL = 0, 1  # include/vtts_stft.h: the framings
+STFT_MAX_SAMPLES = 1 << 24  # include/vtts_stft.h: VTTS_STFT_MAX_SAMPLES
+STFT_NOLA_FLOOR = 1e-11  # include/vtts_stft.h: VTTS_STFT_NOLA_FLOOR
+
 LIMITER_TILE = 4096  # include/vtts_limiter.h: VTTS_LIMITER_TILE
 LIMITER_RUN = 16  # include/vtts_limiter.h: VTTS_LIMITER_RUN
 LIMITER_PHASE_TAPS = 52  # include/vtts_limiter.h: VTTS_LIMITER_PHASE_TAPS
@@ -78,6 +82,7 @@ PITCH_ROWS_PER_LAUNCH = 256  # viettts_amd/csrc/pitch.hip
 STOI_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stoi.hip
 LOUDNESS_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/loudness.hip
 SPECTRAL_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/spectral.hip; include/vtts_spectral.h: VTTS_SPECTRAL_ROWS_PER_LAUNCH
+STFT_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stft.hip; include/vtts_stft.h: VTTS_STFT_ROWS_PER_LAUNCH
 DTW_PAIRS_PER_LAUNCH = 128  # viettts_amd/csrc/dtw.hip: PAIRS_PER_LAUNCH
 LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
 LIMSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_limstream.h: VTTS_LIMSTREAM_ROWS_PER_LAUNCH
@@ -103,6 +108,10 @@ class LoudnessCfg(C.Structure):
 
 class SpectralCfg(C.Structure):
     _fields_ = [("n_fft", C.c_int32), ("win", C.c_int32), ("hop", C.c_int32)]
+
+
+class StftCfg(C.Structure):
+    _fields_ = [("n_fft", C.c_int32), ("win", C.c_int32), ("hop", C.c_int32), ("framing", C.c_int32)]
 
 
 class LimiterCfg(C.Structure):
@@ -297,6 +306,24 @@ SPECTRAL_SIGS = {
 }
 
 
+# include/vtts_stft.h, likewise
+STFT_SIGS = {
+    "vtts_stft_create": (C.c_int, [C.POINTER(StftCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_stft_destroy": (None, [vp]),
+    "vtts_stft_window": (C.c_int, [vp, fp]),
+    "vtts_stft_blocking": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtts_stft_num_frames": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_stft_num_samples": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "vtts_stft_min_envelope": (C.c_int, [vp, i64, C.POINTER(C.c_double)]),
+    "vtts_stft_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "vtts_stft_pack": (C.c_int, [vp, vp, sz, vp]),
+    "vtts_stft_bind_packed": (C.c_int, [vp, vp, sz]),
+    "vtts_stft_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, i64, vp]),
+    "vtts_stft_inverse": (C.c_int, [vp, vp, C.c_int, i64, C.POINTER(C.c_int32), vp, C.c_int, i64, vp]),
+    "vtts_stft_project": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, vp, vp, i64, C.c_float, vp]),
+}
+
+
 # include/vtts_limiter.h, likewise
 LIMITER_SIGS = {
     "vtts_limiter_create": (C.c_int, [C.POINTER(LimiterCfg), C.c_int, C.POINTER(vp)]),
@@ -352,6 +379,7 @@ PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
 SPECTRAL_EXPORTS = tuple(SPECTRAL_SIGS)  # include/vtts_spectral.h
+STFT_EXPORTS = tuple(STFT_SIGS)  # include/vtts_stft.h
 LIMITER_EXPORTS = tuple(LIMITER_SIGS)  # include/vtts_limiter.h
 LIMSTREAM_EXPORTS = tuple(LIMSTREAM_SIGS)  # include/vtts_limstream.h
 RSSTREAM_EXPORTS = tuple(RSSTREAM_SIGS)  # include/vtts_rsstream.h
@@ -408,7 +436,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **STFT_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -3,6 +3,7 @@ standard check of a vocoder checkpoint, and the mel-domain distance between two 
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
     python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi] [--mrstft]
+    python -m viettts_amd.resynth --input in.wav --output out.wav --vocoder griffinlim      # no checkpoint at all: viettts_amd.stft
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
@@ -97,16 +98,33 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--limit", action="store_true", help="with --loudness: the full gain to the target and a look-ahead limiter under -1 dBTP (viettts_amd.limiter) in place of the sample-peak cap")
     ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of the result against the input at 10 kHz (viettts_amd.stoi); NaN below 30 analysis frames")
     ap.add_argument("--mrstft", action="store_true", help="also print the multi-resolution STFT distance and the log-spectral distance of the result against the input (viettts_amd.spectral); needs 1025 samples")
+    ap.add_argument("--vocoder", default="hifigan", choices=("hifigan", "griffinlim"), help="griffinlim: log-mel -> wav by Griffin-Lim on the GPU (viettts_amd.stft): "
+                    "no checkpoint is opened; --dtype does not apply")
     return ap
 
 
-def main(argv=None) -> None:
-    from .hifigan.mel2wave import _generator
+class _Device:
+    """What main() needs of a generator when there is none: the device."""
 
-    a = build_parser().parse_args(argv)
+    def __init__(self, device):
+        self.device = device
+
+
+def main(argv=None) -> None:
+    ap = build_parser()
+    a = ap.parse_args(argv)
     if a.limit and a.loudness is None:
         raise SystemExit("--limit needs --loudness")
-    gen = _generator(a.dtype)  # FileNotFoundError without config / checkpoint, before the input is touched
+    if a.vocoder == "griffinlim":
+        if a.dtype != "f32":
+            ap.error("--vocoder griffinlim with --dtype: the engine's precision belongs to the HiFi-GAN generator")
+        if not torch.cuda.is_available():
+            raise RuntimeError("viettts_amd.resynth needs an MI355X visible to PyTorch-ROCm; there is no CPU path")
+        gen = _Device(torch.device("cuda", torch.cuda.current_device()))
+    else:
+        from .hifigan.mel2wave import _generator
+
+        gen = _generator(a.dtype)  # FileNotFoundError without config / checkpoint, before the input is touched
     sr, pcm = wavio.read_wav(a.input)
     model_rate = NAT_FLAGS.sample_rate
     y = _on_device(pcm.astype(np.int16)[None, :], gen.device)
@@ -114,7 +132,12 @@ def main(argv=None) -> None:
         from .audio import resampler
 
         y = resampler(sr, model_rate, gen.device)(y)
-    wav = resynthesize(y, gen)
+    if a.vocoder == "griffinlim":
+        from .stft import mel2wave_griffinlim
+
+        wav = mel2wave_griffinlim(wav2mel(y, device=gen.device))
+    else:
+        wav = resynthesize(y, gen)
     n = 256 * (y.shape[1] // 256)
     written = wav
     if a.loudness is not None and a.limit:

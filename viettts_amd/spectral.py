@@ -9,8 +9,8 @@ forward magnitude STFT at any of four transform lengths (include/vtts_spectral.h
 
     python -m viettts_amd.spectral --ref A.wav --test B.wav
 
-Framing is ``torch.stft(center=True, pad_mode="reflect")`` with a periodic Hann window centred in ``n_fft``.  The forward direction only:
-no inverse transform, no phase, no gradients.  Unaligned pairs and stereo are out of scope.  The reference has no such stage; nothing here is
+Framing is ``torch.stft(center=True, pad_mode="reflect")`` with a periodic Hann window centred in ``n_fft``.  Magnitudes only, no gradients: the
+complex spectrum, the inverse transform and Griffin-Lim are ``viettts_amd.stft`` (include/vtts_stft.h).  Unaligned pairs and stereo are out of scope.  The reference has no such stage; nothing here is
 re-exported under ``vietTTS/``.  No CPU fallback: the kernels are the only implementation.
 """
 from __future__ import annotations

@@ -64,6 +64,8 @@ def build_parser() -> ArgumentParser:
     p.add_argument("--gain-db", default=None, type=float, help="(extension) with --stream --ceiling-dbtp: a fixed gain in dB ahead of the limiter")
     p.add_argument("--output-rate", default=None, type=int, help="(extension) with --stream: convert the samples to this rate on the GPU, chunk by chunk "
                    "(viettts_amd.audio.ResamplerStream); the header carries it")
+    p.add_argument("--vocoder", default="hifigan", choices=("hifigan", "griffinlim"), help="(extension) griffinlim: mel -> wav by Griffin-Lim on the GPU "
+                   "(viettts_amd.stft) with the NAT checkpoints only; the HiFi-GAN checkpoint is not opened")
     return p
 
 
@@ -135,6 +137,8 @@ def main(argv=None) -> int:
             parser.error(f"--output-rate with --sample-rate {args.sample_rate}: the streamed samples are the models' {FLAGS.sample_rate} Hz and --output-rate "
                          "converts them; leave --sample-rate alone")
     if args.stream:  # argument errors before anything touches a device
+        if args.vocoder == "griffinlim":
+            parser.error("--stream with --vocoder griffinlim: Griffin-Lim iterates over the whole clip; there is no streamed inverse transform")
         if args.resample:
             parser.error("--stream with --resample: --resample converts a whole clip; a stream converts chunk by chunk with --output-rate R")
         if args.low_latency:
@@ -146,7 +150,6 @@ def main(argv=None) -> int:
         if args.mel_file is None and args.text is None:
             raise SystemExit("--text (or --mel-file) is required")
         return _stream(args)
-    from .hifigan.mel2wave import mel2wave
     from .wavio import write_wav, write_wav_pcm16
 
     if args.mel_file is not None:
@@ -163,7 +166,14 @@ def main(argv=None) -> int:
         text = nat_normalize_text(args.text)
         print("Normalized text input:", text)
         mel = text2mel(text, args.lexicon_file, args.silence_duration)
-    wave = mel2wave(mel)
+    if args.vocoder == "griffinlim":
+        from .stft import mel2wave_griffinlim
+
+        wave = np.squeeze(mel2wave_griffinlim(np.asarray(mel, dtype=np.float32)).cpu().numpy())
+    else:
+        from .hifigan.mel2wave import mel2wave
+
+        wave = mel2wave(mel)
     if args.loudness is not None and args.limit:
         from .limiter import default_limiter
 
