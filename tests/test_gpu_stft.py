@@ -184,8 +184,8 @@ def test_forward_against_the_float64_oracle(cfg, dev):
 
 @pytest.mark.parametrize("res", [SO.RESOLUTIONS[n] for n in SO.N_FFTS] + [(1024, 1024, 256)], ids=str)
 def test_forward_magnitude_is_the_spectral_meters_bit_for_bit(res, dev):
-    """The two copies of the forward transform (spectral.hip's and stockham.h's) held together: sqrt(max(re^2 + im^2, 1e-7)) of this output in
-    separately rounded fp32 operations is SpectralMeter(mags=True)."""
+    """The two kernels that run the shared front (csrc/stft_front.h: stft_forward_k and spectral_frames_k) and the meter's floor held together:
+    sqrt(max(re^2 + im^2, 1e-7)) of this output in separately rounded fp32 operations is SpectralMeter(mags=True)."""
     from viettts_amd.spectral import SpectralMeter
 
     cfg = res + ("center",)

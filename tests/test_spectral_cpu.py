@@ -82,6 +82,30 @@ def test_header_exports_and_constants(lib):
     assert "spectral.hip" in build.SOURCES and any(str(h).endswith("vtts_spectral.h") for h in build.HEADERS)
 
 
+def test_the_transform_family_is_stated_once():
+    """The butterflies, the Stockham pass and the wave helpers have one definition each among the native sources, and the files whose bits rest
+    on single roundings take them in after their pragma (a header's inline functions are compiled in the including file's contraction mode)."""
+    from viettts_amd.csrc import build
+
+    texts = {p.name: p.read_text() for p in sorted(build.CSRC.iterdir()) if p.suffix in (".hip", ".h")}
+    homes = {r"\bvoid dft4\(": "stockham.h", r"\bvoid wave_sync\(\)": "wave_common.h", r"\bdouble wave_sum\(": "wave_common.h",
+             r"\bvoid pass\(": "stockham.h", r"\bvoid radix\(": "stockham.h", r"\bvoid fft512_888\(": "stockham.h",
+             r"\bfloat2 cmul\(": "stockham.h", r"\bvoid stage_reflected\(": "stft_front.h", r"g = 2 \* \(S - 1\) - g": "stft_front.h",
+             r"ldexpf\(": "sample_convert.h", r"std::cos\(2\.0 \* pi \* m / H\)": "stft_host.h", r"n_fft must be 256, 512, 1024 or 2048 \(got": "stft_host.h"}
+    for pattern, home in homes.items():
+        assert [n for n, t in texts.items() if re.search(pattern, t)] == [home], pattern
+    pragma = "#pragma clang fp contract(off)"
+    for name, header in (("spectral.hip", "stft_front.h"), ("stft.hip", "stft_front.h"), ("stft.hip", "stockham.h"), ("stoi.hip", "stockham.h")):
+        t = texts[name]
+        assert t.count(pragma) == 1 and t.index(pragma) < t.index(f'#include "{header}"'), (name, header)
+    assert "#pragma clang fp" not in texts["mel.hip"] and '#include "stockham.h"' in texts["mel.hip"]  # its FMAs are part of its bits
+    assert "-ffp-contract=off" in build.FILE_FLAGS["pitch.hip"] and '#include "wave_common.h"' in texts["pitch.hip"]
+    for header in ("wave_common.h", "stockham.h", "stft_front.h", "stft_host.h"):
+        assert header in build.HEADERS, header
+    included = {h for t in texts.values() for h in re.findall(r'#include "([a-z_0-9]+\.h)"', t)}
+    assert included <= set(build.HEADERS), included - set(build.HEADERS)  # every header feeds the rebuild digest
+
+
 def test_create_refuses_what_the_header_excludes(lib):
     h = C.c_void_p(0)
     for bad in ((128, 64, 16), (4096, 1024, 256), (1000, 600, 120), (1024, 600, 0), (1024, 600, -1), (1024, 100, 120), (1024, 1025, 120), (512, 600, 120)):

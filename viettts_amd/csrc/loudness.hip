@@ -32,11 +32,13 @@
 #include "loudness_design.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
+#include "wave_common.h"
 
 using vtts::check_rows;
 using vtts::failf;
 using vtts_sample::from_float;
 using vtts_sample::to_float;
+using vtts_wave::wave_sum;
 namespace ld = vtts_loudness_design;
 
 namespace {
@@ -97,12 +99,6 @@ struct ApplyArgs {
 __device__ __forceinline__ void matvec(const float* m, const float (&s)[4], float (&r)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = fmaf(m[4 * i + 3], s[3], fmaf(m[4 * i + 2], s[2], fmaf(m[4 * i + 1], s[1], m[4 * i] * s[0])));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // FULL = false: stop after the scan and leave the segment's end state (from a zero incoming state) in a.state; the row's last segment is

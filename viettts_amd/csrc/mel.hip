@@ -5,14 +5,9 @@
 //   1. stage: the (8 + 3) * 256 samples the eight frames cover, once, into LDS (16-byte loads; PCM16 scaled by 2^-15 on the way),
 //      mirrored at the ROW'S OWN ends.  The 4x overlap of the frames is served from LDS: every sample is read from HBM once.
 //   2. FFT: a real 1024-point transform = a 512-point complex FFT of z[n] = x[2n] + i x[2n+1] and a split step.
-//      512 = 8 x 8 x 8: 64 lanes x 8 points, three radix-8 passes in registers, two exchanges through LDS
-//          n = 64 a + 8 b + c,  k = k0 + 8 k1 + 64 k2
-//          X[k] = sum_c W8^(c k2) W64^(c k1) W512^(c k0)  sum_b W8^(b k1) W64^(b k0)  sum_a W8^(a k0) z[n]
-//      pass 1: lane = 8 b + c, registers a -> k0, times W512^(lane k0);   pass 2: lane = 8 k0 + c, registers b -> k1, times W512^(8 c k1);
-//      pass 3: lane = 8 k0 + k1, registers c -> k2.  Window and twiddles come from tables computed in double on the host and rounded
-//      once; there is no sin / cos in the kernel.
-//      LDS rows of the exchanges are padded (72 complex per k0, and 9 per k1 in the second) so that every ds_write_b64 / ds_read_b64 of
-//      a 32-lane half touches 32 distinct bank pairs (guide §LDS: stride-64 and stride-8 columns would be 4- and 8-way otherwise).
+//      512 = 8 x 8 x 8: 64 lanes x 8 points, three radix-8 passes in registers, two exchanges through padded LDS rows (stockham.h:
+//      fft512_888, shared with stoi.hip; the first pass's twiddles wait in registers here).  Window and twiddles come from tables computed
+//      in double on the host and rounded once; there is no sin / cos in the kernel.
 //      A wave touches only its own exchange buffer and the LDS keeps one wave's accesses in order, so the exchanges are separated
 //      by a compiler-only wave fence (wave_sync), not by workgroup barriers.
 //   3. split step: lane pairs bin k with bin 512 - k, X[k] = E + W1024^k O, X[512 - k] = conj(E - W1024^k O); magnitudes
@@ -33,12 +28,14 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_mel.h"
 #include "sample_convert.h"
+#include "stockham.h"  // under this file's default contraction: the a * b + c of its complex products are FMAs here, as they always were
 #include "vtts_internal.h"
 
 using vtts::check_blob;
 using vtts::failf;
 using vtts::upload_blob;
 using vtts_sample::to_float;
+using namespace vtts_stockham;
 
 namespace {
 
@@ -47,8 +44,6 @@ constexpr int PADL = (NFFT - HOP) / 2;                    // 384 reflected sampl
 constexpr int FPB = VTTS_MEL_FRAMES_PER_BLOCK;            // frames (= waves) per workgroup
 constexpr int THREADS = 64 * FPB;
 constexpr int SPAN = (FPB + 3) * HOP;                     // samples the FPB frames cover
-constexpr int XROW = 72;                                  // complex entries per k0 row of the exchange buffer (64 + 8 pad)
-constexpr int XBUF = 8 * XROW;                            // complex entries of one wave's exchange buffer (>= 512)
 constexpr int MAX_MELS = 128;
 constexpr int ROWS_PER_LAUNCH = 256;
 constexpr int MAX_NNZ = 2 * NBINS;                        // triangles overlap their neighbours only: two bands per bin
@@ -78,42 +73,6 @@ struct MelArgs {
     float floor_log;   // (float)log(1e-5)
 };
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // -i a
-
-// A[k] = sum_j a_j (-i)^(j k)
-__device__ __forceinline__ void dft4(float2 a0, float2 a1, float2 a2, float2 a3, float2& A0, float2& A1, float2& A2, float2& A3) {
-    const float2 s0 = cadd(a0, a2), d0 = csub(a0, a2), s1 = cadd(a1, a3), d1 = mul_mi(csub(a1, a3));
-    A0 = cadd(s0, s1);
-    A1 = cadd(d0, d1);
-    A2 = csub(s0, s1);
-    A3 = csub(d0, d1);
-}
-// in place: v[k] = sum_a v[a] exp(-2 pi i a k / 8)
-__device__ __forceinline__ void radix8(float2 (&v)[8]) {
-    float2 e0, e1, e2, e3, o0, o1, o2, o3;
-    dft4(v[0], v[2], v[4], v[6], e0, e1, e2, e3);
-    dft4(v[1], v[3], v[5], v[7], o0, o1, o2, o3);
-    const float c = 0.70710678118654752440f;
-    o1 = make_float2(c * (o1.x + o1.y), c * (o1.y - o1.x));   // times W8   = (c, -c)
-    o2 = mul_mi(o2);                                          // times W8^2 = -i
-    o3 = make_float2(c * (o3.y - o3.x), -c * (o3.x + o3.y));  // times W8^3 = (-c, -c)
-    v[0] = cadd(e0, o0), v[4] = csub(e0, o0);
-    v[1] = cadd(e1, o1), v[5] = csub(e1, o1);
-    v[2] = cadd(e2, o2), v[6] = csub(e2, o2);
-    v[3] = cadd(e3, o3), v[7] = csub(e3, o3);
-}
-
-// Orders a wave's LDS writes before its later LDS reads of other lanes' data.  No instruction: the hardware keeps one wave's LDS
-// accesses in order; this only keeps the compiler from moving them across.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <typename T>
 __global__ __launch_bounds__(THREADS) void mel_fused_k(const MelArgs a, const MelRows rows) {
     extern __shared__ float4 lds4[];
@@ -138,7 +97,6 @@ __global__ __launch_bounds__(THREADS) void mel_fused_k(const MelArgs a, const Me
     const float2* win2 = reinterpret_cast<const float2*>(a.blob + OFF_WIN);
     const float2* tw512 = reinterpret_cast<const float2*>(a.blob + OFF_TW512);
     const float2* tw1024 = reinterpret_cast<const float2*>(a.blob + OFF_TW1024);
-    const int hi = lane >> 3, lo = lane & 7;
     float2 win[8], tw1[7];
 #pragma unroll
     for (int q = 0; q < 8; ++q) win[q] = win2[64 * q + lane];
@@ -183,28 +141,7 @@ __global__ __launch_bounds__(THREADS) void mel_fused_k(const MelArgs a, const Me
             v[q] = make_float2(x.x * win[q].x, x.y * win[q].y);
         }
     }
-    radix8(v);
-#pragma unroll
-    for (int k0 = 1; k0 < 8; ++k0) v[k0] = cmul(v[k0], tw1[k0 - 1]);
-#pragma unroll
-    for (int k0 = 0; k0 < 8; ++k0) xb[k0 * XROW + lane] = v[k0];
-    wave_sync();
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = xb[hi * XROW + q * 8 + lo];
-    wave_sync();
-    radix8(v);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; ++k1) v[k1] = cmul(v[k1], tw512[8 * lo * k1]);
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1) xb[hi * XROW + k1 * 9 + lo] = v[k1];
-    wave_sync();
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = xb[hi * XROW + lo * 9 + q];
-    wave_sync();
-    radix8(v);
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) xb[hi + 8 * lo + 64 * k2] = v[k2];  // Z[k0 + 8 k1 + 64 k2], natural order
-    wave_sync();
+    fft512_888<8>(v, xb, tw512, lane, [&](int k0) { return tw1[k0 - 1]; });
 
     // ---- 3. split step and magnitudes; the magnitudes overwrite the wave's exchange buffer once every lane has read its bins
     float2 zk[5], zn[5];

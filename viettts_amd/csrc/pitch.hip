@@ -35,6 +35,7 @@
 #include "../../include/vtts_pitch.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
+#include "wave_common.h"
 
 // The contract's operations are single fp32 operations: nothing in this file may be fused into an FMA.  The pragma covers this file's own
 // operators; __fsub_rn / __fmul_rn / __fadd_rn / __fdiv_rn are plain operators of a header that precedes it, which hipcc contracts all the
@@ -43,6 +44,7 @@
 
 using vtts::failf;
 using vtts_sample::to_float;
+using vtts_wave::wave_sync;
 
 namespace {
 
@@ -78,14 +80,6 @@ struct PitchArgs {
     float threshold;
     float rate;        // (float)sample_rate
 };
-
-// Orders a wave's LDS writes before its later LDS reads of other lanes' data.  No instruction: the hardware keeps one wave's LDS
-// accesses in order; this only keeps the compiler from moving them across.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // one step of a chain: s + (a - y)^2, three rounded operations
 __device__ __forceinline__ float step(float s, float a, float y) {

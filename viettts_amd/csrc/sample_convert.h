@@ -7,6 +7,10 @@ namespace vtts_sample {
 
 __device__ __forceinline__ float to_float(float v) { return v; }
 __device__ __forceinline__ float to_float(short v) { return (float)v * (1.0f / 32768.0f); }
+// The same bits with an exponent add in place of the multiply, for the short-time stages (stft_front.h): their staging converts two samples
+// side by side, and the compiler pairs two such multiplies into a v_pk_mul_f32, which no kernel of this library may hold (build.py).
+__device__ __forceinline__ float to_float_exact_shift(float v) { return v; }
+__device__ __forceinline__ float to_float_exact_shift(short v) { return ldexpf((float)v, -15); }
 
 template <typename TO>
 __device__ __forceinline__ TO from_float(float v);

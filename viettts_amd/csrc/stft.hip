@@ -33,41 +33,29 @@
 // transform's bits are spectral.hip's, and a sample's sums must not depend on how the compiler schedules a workgroup's run).
 #pragma clang fp contract(off)
 
+#include "stft_front.h"
+#include "stft_host.h"
 #include "stockham.h"
 
-using vtts::check_blob;
 using vtts::failf;
-using vtts::upload_blob;
-using namespace vtts_stockham;
+using namespace vtts_stft_front;
+namespace sh = vtts_stft_host;
 
 namespace {
 
 constexpr int ROWS_PER_LAUNCH = 128;
-static_assert(ROWS_PER_LAUNCH == VTTS_STFT_ROWS_PER_LAUNCH, "the header states the split");
-constexpr int MAX_F = 8, MAX_F_2048 = 4;
+static_assert(ROWS_PER_LAUNCH == VTTS_STFT_ROWS_PER_LAUNCH && ROWS_PER_LAUNCH == sh::ROWS, "the header states the split");
+constexpr int MAX_F = sh::MAX_F;
+constexpr int SIGNALS = 1, REDUCE = 0;  // of sh::frames_lds_bytes: one staged signal, nothing to reduce
 
-constexpr int even(int n) { return (n + 1) & ~1; }
 constexpr int inv_waves(int n_fft) { return n_fft == 2048 ? 4 : 8; }
 constexpr int inv_per_thread(int n_fft) { return n_fft == 256 ? 2 : n_fft == 512 ? 4 : n_fft == 1024 ? 8 : 16; }
 constexpr int inv_run(int n_fft) { return 64 * inv_waves(n_fft) * inv_per_thread(n_fft); }
 
-size_t fwd_lds_bytes(int n_fft, int hop, int F) {
-    const int H = n_fft / 2;
-    return (size_t)8 * H + (size_t)8 * (H / 2 + 2) + (size_t)4 * even((F - 1) * hop + n_fft) + (size_t)8 * F * pad8(H);
-}
-int fwd_frames(int n_fft, int hop) {
-    int F = n_fft == 2048 ? MAX_F_2048 : MAX_F;
-    while (F > 1 && fwd_lds_bytes(n_fft, hop, F) > VTTS_SPECTRAL_LDS_BUDGET) --F;
-    return F;
-}
 size_t inv_lds_bytes(int n_fft) {
     const int H = n_fft / 2;
     return (size_t)8 * H + (size_t)8 * (H / 2 + 2) + (size_t)4 * n_fft + (size_t)8 * inv_waves(n_fft) * pad8(H);
 }
-
-struct StftRows {
-    int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
-};
 
 struct FwdArgs {             // every pointer at the launch's first row
     const void* x;
@@ -90,16 +78,11 @@ struct InvArgs {
     float scale;             // 1 / n_fft
 };
 
-// A sample as fp32.  PCM16 is scaled by 2^-15 with an exponent add (sample_convert.h's multiply gives the same bits; spectral.hip says why).
-__device__ __forceinline__ float sample(const float* x, long long g) { return x[g]; }
-__device__ __forceinline__ float sample(const short* x, long long g) { return ldexpf((float)x[g], -15); }
-
 __device__ __forceinline__ long long num_frames_dev(long long S, int P, int n_fft, int hop) { return (S + 2 * P - n_fft) / hop + 1; }
 
 template <int NFFT, typename TI, bool PROJ>
-__global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, const StftRows rows) {
+__global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, const sh::Rows rows) {
     constexpr int H = NFFT / 2, NB = H + 1, XB = pad8(H);
-    constexpr int J = (H / 2) / 64 + 1;  // bins k = lane + 64 j <= H / 2 of a lane
     extern __shared__ float2 lds2[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int F = a.F;
@@ -114,46 +97,19 @@ __global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, co
     const long long t0 = (long long)blockIdx.x * F;
     if (t0 >= T) return;  // block-uniform
 
-    // this lane's window values of the first pass: issued now, so that their latency hides behind the staging
-    using O1 = Own<H, 8>;
-    float2 wv[O1::PER][8];
-    {
-        const float2* win2 = reinterpret_cast<const float2*>(a.blob);
-#pragma unroll
-        for (int m = 0; m < O1::PER; ++m)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) wv[m][q] = O1::active(lane) ? win2[lane + 64 * m + q * O1::BF] : make_float2(0.0f, 0.0f);
-    }
-    {
-        const float2* t2 = reinterpret_cast<const float2*>(a.blob + NFFT);
-        for (int i = tid; i < H + H / 2 + 1; i += 64 * F) (i < H ? twH[i] : twN[i - H]) = t2[i];
-    }
+    Window<H> wv;
+    load_window<H>(wv, a.blob, lane);
+    stage_twiddles<H>(twH, twN, a.blob, tid, 64 * F);
     // ---- 1. stage: span[i] = padded sample hop t0 + i = row sample hop t0 - P + i, reflected at the row's ends
-    {
-        const TI* x = static_cast<const TI*>(a.x) + (long long)b * a.s_stride;
-        const long long g0 = t0 * a.hop - a.P;
-        for (int i = tid; i < a.span; i += 64 * F) {
-            long long g = g0 + i;
-            if (g < 0) g = -g;
-            if (g >= S) g = 2 * (S - 1) - g;
-            g = g < 0 ? 0 : g >= S ? S - 1 : g;  // frames past the row's last (never used) stay inside the row
-            span[i] = sample(x, g);
-        }
-    }
+    stage_reflected(span, static_cast<const TI*>(a.x) + (long long)b * a.s_stride, S, t0 * a.hop - a.P, a.span, tid, 64 * F);
     __syncthreads();
 
     // ---- 2./3. From here on a wave touches only its own exchange buffer.
     const long long t = t0 + wave;
     if (t >= T) return;
-    const float* fr = span + wave * a.hop;
-    transform<H, false>(xb, twH, lane, [&](int m, int q, int i) { return make_float2(fr[2 * i] * wv[m][q].x, fr[2 * i + 1] * wv[m][q].y); });
-    float2 zk[J], zn[J];
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int k = min(lane + 64 * j, H / 2);
-        zk[j] = xb[pad8(k)];
-        zn[j] = xb[pad8((H - k) & (H - 1))];
-    }
+    transform_frame<H>(xb, twH, lane, span + wave * a.hop, wv);
+    Bins<H> z;
+    gather_bins(z, xb, lane);
     const long long row = ((long long)b * a.t_stride + t) * NB;
     auto store = [&](int f, float2 c) {
         if constexpr (PROJ) {
@@ -167,22 +123,14 @@ __global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, co
             a.spec[row + f] = c;
         }
     };
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int k = lane + 64 * j;
-        if (k <= H / 2) {
-            const float2 e = make_float2(0.5f * (zk[j].x + zn[j].x), 0.5f * (zk[j].y - zn[j].y));
-            const float2 o = make_float2(0.5f * (zk[j].y + zn[j].y), -0.5f * (zk[j].x - zn[j].x));
-            const float2 w = cmul(twN[k], o);
-            const float2 p = cadd(e, w), m = csub(e, w);
-            store(k, p);
-            if (k != H / 2) store(H - k, conj(m));
-        }
-    }
+    split_bins(z, twN, lane, [&](int, int k, float2 p, float2 m) {
+        store(k, p);
+        if (k != H / 2) store(H - k, conj(m));
+    });
 }
 
 template <int NFFT, typename TO>
-__global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const InvArgs a, const StftRows rows) {
+__global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const InvArgs a, const sh::Rows rows) {
     constexpr int H = NFFT / 2, NB = H + 1, XB = pad8(H), W = inv_waves(NFFT), R = inv_per_thread(NFFT), NT = 64 * W, RUN = NT * R;
     constexpr int J = (H / 2) / 64 + 1;
     extern __shared__ float2 lds2[];
@@ -198,11 +146,8 @@ __global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const Inv
     const int g0 = blockIdx.x * RUN;  // < 2^24 + RUN
     if (g0 >= S) return;              // block-uniform
     const int T = (int)num_frames_dev(S, a.P, NFFT, a.hop);
-    {
-        const float2* t2 = reinterpret_cast<const float2*>(a.blob + NFFT);
-        for (int i = tid; i < H + H / 2 + 1; i += NT) (i < H ? twH[i] : twN[i - H]) = t2[i];
-        for (int i = tid; i < NFFT; i += NT) winl[i] = a.blob[i];
-    }
+    stage_twiddles<H>(twH, twN, a.blob, tid, NT);
+    for (int i = tid; i < NFFT; i += NT) winl[i] = a.blob[i];
     // the frames whose window [hop t + lead, hop t + lead + win) meets the run's padded samples [p0, p1]
     const int p0 = g0 + a.P, p1 = min(g0 + RUN, S) - 1 + a.P;
     const int below = p0 - (a.lead + a.win - 1);
@@ -266,7 +211,7 @@ __global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const Inv
 }
 
 template <int NFFT>
-hipError_t launch_fwd(bool pcm, bool proj, dim3 grid, int F, size_t lds, hipStream_t s, const FwdArgs& a, const StftRows& rows, vtts::DynLdsOnce* once) {
+hipError_t launch_fwd(bool pcm, bool proj, dim3 grid, int F, size_t lds, hipStream_t s, const FwdArgs& a, const sh::Rows& rows, vtts::DynLdsOnce* once) {
     const void* fn = pcm ? (proj ? reinterpret_cast<const void*>(&stft_forward_k<NFFT, short, true>) : reinterpret_cast<const void*>(&stft_forward_k<NFFT, short, false>))
                          : (proj ? reinterpret_cast<const void*>(&stft_forward_k<NFFT, float, true>) : reinterpret_cast<const void*>(&stft_forward_k<NFFT, float, false>));
     const hipError_t e = vtts::set_max_dynamic_lds(fn, VTTS_SPECTRAL_LDS_BUDGET, once[2 * pcm + proj]);
@@ -283,7 +228,7 @@ hipError_t launch_fwd(bool pcm, bool proj, dim3 grid, int F, size_t lds, hipStre
 }
 
 template <int NFFT>
-hipError_t launch_inv(bool pcm, dim3 grid, hipStream_t s, const InvArgs& a, const StftRows& rows, vtts::DynLdsOnce* once) {
+hipError_t launch_inv(bool pcm, dim3 grid, hipStream_t s, const InvArgs& a, const sh::Rows& rows, vtts::DynLdsOnce* once) {
     const void* fn = pcm ? reinterpret_cast<const void*>(&stft_inverse_k<NFFT, short>) : reinterpret_cast<const void*>(&stft_inverse_k<NFFT, float>);
     const hipError_t e = vtts::set_max_dynamic_lds(fn, VTTS_SPECTRAL_LDS_BUDGET, once[pcm]);
     if (e != hipSuccess) return e;
@@ -297,13 +242,11 @@ hipError_t launch_inv(bool pcm, dim3 grid, hipStream_t s, const InvArgs& a, cons
 
 }  // namespace
 
-struct vtts_stft {
+struct vtts_stft : sh::Tables {
     vtts_stft_cfg cfg;
     int device = 0;
     int F = 1;
     int P = 0, lead = 0;
-    std::vector<float> img;  // the packed blob's host image: window | twH | twN
-    const float* blob = nullptr;
     std::map<int64_t, double> envelope;  // min_envelope() of the lengths seen so far
     vtts::DynLdsOnce lds_fwd[4], lds_inv[2];
 };
@@ -368,11 +311,10 @@ int forward_or_project(vtts_stft* h, const char* what, bool proj, const void* wa
     const int64_t gmax = (num_frames(h, longest) + F - 1) / F;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pcm = dtype == VTTS_AUDIO_PCM16;
-    const size_t esz = pcm ? 2 : 4, lds = fwd_lds_bytes(n_fft, hop, F), nb = (size_t)n_fft / 2 + 1;
+    const size_t esz = pcm ? 2 : 4, lds = sh::frames_lds_bytes(n_fft, hop, F, SIGNALS, REDUCE), nb = (size_t)n_fft / 2 + 1;
     for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
         const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        StftRows rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+        const sh::Rows rows = sh::launch_rows(lengths, r0, nr, S_stride);
         FwdArgs a;
         a.x = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.blob = h->blob;
@@ -382,12 +324,9 @@ int forward_or_project(vtts_stft* h, const char* what, bool proj, const void* wa
         a.mag = proj ? mag_dev + (size_t)r0 * T_stride * nb : nullptr;
         a.tprev = proj ? static_cast<float2*>(tprev_dev) + (size_t)r0 * T_stride * nb : nullptr;
         a.alpha = proj ? momentum / (1.0f + momentum) : 0.0f;
-        a.hop = hop, a.F = F, a.span = even((F - 1) * hop + n_fft), a.P = h->P;
+        a.hop = hop, a.F = F, a.span = sh::even((F - 1) * hop + n_fft), a.P = h->P;
         const dim3 grid((unsigned)gmax, (unsigned)nr);
-        const hipError_t e = n_fft == 256    ? launch_fwd<256>(pcm, proj, grid, F, lds, s, a, rows, h->lds_fwd)
-                             : n_fft == 512  ? launch_fwd<512>(pcm, proj, grid, F, lds, s, a, rows, h->lds_fwd)
-                             : n_fft == 1024 ? launch_fwd<1024>(pcm, proj, grid, F, lds, s, a, rows, h->lds_fwd)
-                                             : launch_fwd<2048>(pcm, proj, grid, F, lds, s, a, rows, h->lds_fwd);
+        const hipError_t e = sh::by_nfft(n_fft, [&](auto n) { return launch_fwd<decltype(n)::value>(pcm, proj, grid, F, lds, s, a, rows, h->lds_fwd); });
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "stft %s kernel launch failed: %s", what, hipGetErrorString(e));
     }
     return VTTS_OK;
@@ -397,10 +336,7 @@ int forward_or_project(vtts_stft* h, const char* what, bool proj, const void* wa
 VTTS_API int vtts_stft_create(const vtts_stft_cfg* cfg, int device, vtts_stft** out) {
     if (!cfg || !out) return failf(VTTS_ERR_INVALID, "null argument");
     const vtts_stft_cfg& c = *cfg;
-    if (c.n_fft != 256 && c.n_fft != 512 && c.n_fft != 1024 && c.n_fft != 2048)
-        return failf(VTTS_ERR_INVALID, "n_fft must be 256, 512, 1024 or 2048 (got %d)", c.n_fft);
-    if (c.hop < 1 || c.win < c.hop || c.win > c.n_fft)
-        return failf(VTTS_ERR_INVALID, "need 1 <= hop <= win <= n_fft (got hop %d, win %d, n_fft %d)", c.hop, c.win, c.n_fft);
+    if (int rc = sh::check_resolution(c.n_fft, c.hop, c.win)) return rc;
     if (c.framing != VTTS_STFT_CENTER && c.framing != VTTS_STFT_MEL)
         return failf(VTTS_ERR_INVALID, "framing must be VTTS_STFT_CENTER or VTTS_STFT_MEL (got %d)", c.framing);
     if (c.framing == VTTS_STFT_MEL && (c.n_fft - c.hop) % 2)
@@ -409,36 +345,17 @@ VTTS_API int vtts_stft_create(const vtts_stft_cfg* cfg, int device, vtts_stft** 
     if (!h) return failf(VTTS_ERR_NOMEM, "host allocation failed");
     h->cfg = c;
     h->device = device;
-    h->F = fwd_frames(c.n_fft, c.hop);
+    h->F = sh::frames_per_block(c.n_fft, c.hop, SIGNALS, REDUCE);
     h->P = c.framing == VTTS_STFT_MEL ? (c.n_fft - c.hop) / 2 : c.n_fft / 2;
     h->lead = (c.n_fft - c.win) / 2;
-    // vtts_spectral.h's tables, by the same expressions
-    const int H = c.n_fft / 2;
-    h->img.assign((size_t)c.n_fft + 2 * H + 2 * (H / 2 + 2), 0.0f);
-    const double pi = 3.14159265358979323846;
-    float* win = h->img.data();
-    float* twH = win + c.n_fft;
-    float* twN = twH + 2 * H;
-    for (int r = 0; r < c.win; ++r) win[h->lead + r] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * r / c.win));
-    for (int m = 0; m < H; ++m) {
-        twH[2 * m] = (float)std::cos(2.0 * pi * m / H);
-        twH[2 * m + 1] = (float)-std::sin(2.0 * pi * m / H);
-    }
-    for (int k = 0; k <= H / 2; ++k) {
-        twN[2 * k] = (float)std::cos(2.0 * pi * k / c.n_fft);
-        twN[2 * k + 1] = (float)-std::sin(2.0 * pi * k / c.n_fft);
-    }
+    h->build(c.n_fft, c.win);
     *out = h;
     return VTTS_OK;
 }
 
 VTTS_API void vtts_stft_destroy(vtts_stft* h) { delete h; }
 
-VTTS_API int vtts_stft_window(const vtts_stft* h, float* host_out) {
-    if (!h || !host_out) return failf(VTTS_ERR_INVALID, "null argument");
-    memcpy(host_out, h->img.data(), (size_t)h->cfg.n_fft * sizeof(float));
-    return VTTS_OK;
-}
+VTTS_API int vtts_stft_window(const vtts_stft* h, float* host_out) { return sh::window(h, h ? h->cfg.n_fft : 0, host_out); }
 
 VTTS_API int vtts_stft_blocking(const vtts_stft* h, int* forward_frames, int* inverse_waves, int* inverse_run) {
     if (!h || !forward_frames || !inverse_waves || !inverse_run) return failf(VTTS_ERR_INVALID, "null argument");
@@ -473,27 +390,13 @@ VTTS_API int vtts_stft_min_envelope(const vtts_stft* h, int64_t n_samples, doubl
     return VTTS_OK;
 }
 
-VTTS_API int vtts_stft_packed_bytes(const vtts_stft* h, size_t* bytes) {
-    if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
-    *bytes = h->img.size() * sizeof(float);
-    return VTTS_OK;
-}
+VTTS_API int vtts_stft_packed_bytes(const vtts_stft* h, size_t* bytes) { return sh::packed_bytes(h, bytes); }
 
 VTTS_API int vtts_stft_pack(vtts_stft* h, void* dev_blob, size_t blob_bytes, void* stream) {
-    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
-    const size_t need = h->img.size() * sizeof(float);
-    if (int rc = check_blob(dev_blob, blob_bytes, need)) return rc;
-    if (int rc = upload_blob(dev_blob, h->img.data(), need, static_cast<hipStream_t>(stream), "the stft tables")) return rc;
-    h->blob = static_cast<const float*>(dev_blob);
-    return VTTS_OK;
+    return sh::pack(h, dev_blob, blob_bytes, stream, "the stft tables");
 }
 
-VTTS_API int vtts_stft_bind_packed(vtts_stft* h, void* dev_blob, size_t blob_bytes) {
-    if (!h) return failf(VTTS_ERR_INVALID, "null argument");
-    if (int rc = check_blob(dev_blob, blob_bytes, h->img.size() * sizeof(float))) return rc;
-    h->blob = static_cast<const float*>(dev_blob);
-    return VTTS_OK;
-}
+VTTS_API int vtts_stft_bind_packed(vtts_stft* h, void* dev_blob, size_t blob_bytes) { return sh::bind_packed(h, dev_blob, blob_bytes); }
 
 VTTS_API int vtts_stft_forward(vtts_stft* h, const void* wav_dev, int dtype, int N, int64_t S_stride, const int32_t* lengths, void* spec_dev,
                                int64_t T_stride, void* stream) {
@@ -531,8 +434,7 @@ VTTS_API int vtts_stft_inverse(vtts_stft* h, const void* spec_dev, int N, int64_
     const size_t esz = pcm ? 2 : 4, nb = (size_t)n_fft / 2 + 1;
     for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {
         const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        StftRows rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+        const sh::Rows rows = sh::launch_rows(lengths, r0, nr, S_stride);
         InvArgs a;
         a.spec = static_cast<const float2*>(spec_dev) + (size_t)r0 * T_stride * nb;
         a.blob = h->blob;
@@ -542,10 +444,7 @@ VTTS_API int vtts_stft_inverse(vtts_stft* h, const void* spec_dev, int N, int64_
         a.hop = h->cfg.hop, a.P = h->P, a.lead = h->lead, a.win = h->cfg.win;
         a.scale = 1.0f / (float)n_fft;
         const dim3 grid((unsigned)gmax, (unsigned)nr);
-        const hipError_t e = n_fft == 256    ? launch_inv<256>(pcm, grid, s, a, rows, h->lds_inv)
-                             : n_fft == 512  ? launch_inv<512>(pcm, grid, s, a, rows, h->lds_inv)
-                             : n_fft == 1024 ? launch_inv<1024>(pcm, grid, s, a, rows, h->lds_inv)
-                                             : launch_inv<2048>(pcm, grid, s, a, rows, h->lds_inv);
+        const hipError_t e = sh::by_nfft(n_fft, [&](auto n) { return launch_inv<decltype(n)::value>(pcm, grid, s, a, rows, h->lds_inv); });
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "stft inverse kernel launch failed: %s", hipGetErrorString(e));
     }
     return VTTS_OK;

@@ -8,13 +8,21 @@
 // write, separated by a compiler-only wave fence (the LDS keeps one wave's accesses in order).  Entry i of the buffer lives at pad8(i) = i + i / 8:
 // the radix-8 first pass writes out[8 j + q], which at stride 8 would put a half-wave's stores on 4 bank pairs and at stride 9 takes distinct ones.
 //
-// The forward instance performs the operations of spectral.hip's transform in the same order (that file keeps its own copy for now; a test holds
-// the two together bit for bit).  Include under `#pragma clang fp contract(off)`: every operation is rounded on its own.
+// spectral.hip and stft.hip run it under `#pragma clang fp contract(off)`, every operation rounded on its own: a header's inline functions
+// take the contraction mode of the file that includes them, so those files include this one AFTER their pragma.
+//
+// fft512_888 at the end is the other transform of the library, the fixed 512-point one of mel.hip and stoi.hip: twiddles AFTER the
+// butterflies, so its bits are not the Stockham schedule's.  The two share the butterflies and nothing else.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "wave_common.h"
+
 namespace vtts_stockham {
+
+using vtts_wave::wave_sum;
+using vtts_wave::wave_sync;
 
 __host__ __device__ constexpr int pad8(int i) { return i + (i >> 3); }  // where entry i of an exchange buffer lives
 
@@ -61,13 +69,6 @@ __device__ __forceinline__ void radix(float2 (&v)[8]) {
     v[1] = cadd(e1, o1), v[5] = csub(e1, o1);
     v[2] = cadd(e2, o2), v[6] = csub(e2, o2);
     v[3] = cadd(e3, o3), v[7] = csub(e3, o3);
-}
-
-// Orders a wave's LDS writes before its later LDS reads of other lanes' data: no instruction, it only holds the compiler.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Butterflies a lane owns in a pass of radix R over H points
@@ -139,6 +140,44 @@ __device__ __forceinline__ void transform(float2* xb, const float2* twH, int lan
         pass<H, 4, 64, INV>(xb, twH, lane, buf);
         pass<H, 4, 256, INV>(xb, twH, lane, buf);
     }
+}
+
+// ---- 512 = 8 x 8 x 8 in one wave: 64 lanes x 8 points, three radix-8 passes in registers, two exchanges through the wave's buffer xb[XBUF]
+//     n = 64 a + 8 b + c,  k = k0 + 8 k1 + 64 k2
+//     X[k] = sum_c W8^(c k2) W64^(c k1) W512^(c k0)  sum_b W8^(b k1) W64^(b k0)  sum_a W8^(a k0) z[n]
+// pass 1: lane = 8 b + c, registers a -> k0, times W512^(lane k0) = tw1(k0);   pass 2: lane = 8 k0 + c, registers b -> k1, times
+// W512^(8 c k1);   pass 3: lane = 8 k0 + k1, registers c -> k2.  On entry v[a] = z[64 a + lane]; on return xb[k] = X[k] in natural order for
+// k < 64 K2 (K2 = 8: all of them; a caller that needs the lower bins only stores fewer rows).  The rows of the exchanges are padded (72 complex
+// per k0, and 9 per k1 in the second) so that every ds_write_b64 / ds_read_b64 of a 32-lane half touches 32 distinct bank pairs: stride-64 and
+// stride-8 columns would be 4- and 8-way conflicts otherwise.  tw512[j] = exp(-2 pi i j / 512), in global memory or in LDS.
+constexpr int XROW = 72;        // complex entries per k0 row of the exchange buffer (64 + 8 pad)
+constexpr int XBUF = 8 * XROW;  // complex entries of one wave's exchange buffer (>= 512)
+
+template <int K2, typename Tw1>
+__device__ __forceinline__ void fft512_888(float2 (&v)[8], float2* xb, const float2* tw512, int lane, const Tw1& tw1) {
+    const int hi = lane >> 3, lo = lane & 7;
+    radix<false>(v);
+#pragma unroll
+    for (int k0 = 1; k0 < 8; ++k0) v[k0] = cmul(v[k0], tw1(k0));
+#pragma unroll
+    for (int k0 = 0; k0 < 8; ++k0) xb[k0 * XROW + lane] = v[k0];
+    wave_sync();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = xb[hi * XROW + q * 8 + lo];
+    wave_sync();
+    radix<false>(v);
+#pragma unroll
+    for (int k1 = 1; k1 < 8; ++k1) v[k1] = cmul(v[k1], tw512[8 * lo * k1]);
+#pragma unroll
+    for (int k1 = 0; k1 < 8; ++k1) xb[hi * XROW + k1 * 9 + lo] = v[k1];
+    wave_sync();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = xb[hi * XROW + lo * 9 + q];
+    wave_sync();
+    radix<false>(v);
+#pragma unroll
+    for (int k2 = 0; k2 < K2; ++k2) xb[hi + 8 * lo + 64 * k2] = v[k2];  // Z[k0 + 8 k1 + 64 k2], natural order
+    wave_sync();
 }
 
 }  // namespace vtts_stockham

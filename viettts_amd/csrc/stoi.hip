@@ -7,9 +7,9 @@
 //   stoi_keep_k      one workgroup per row: the largest e_k, the keep mask e_k > 1e-4 e_max, and an exclusive scan (ballot + popcount per wave,
 //                    the four waves' counts through LDS, a running base) into the kept list.
 //   stoi_spectra_k   workgroup = 8 analysis frames, one wave per frame, x then y.  A frame gathers its three kept candidate frames straight
-//                    from the row (the overlap-added signal is never written; both signals' loads are issued first), and runs the zero-padded 512-point transform as mel.hip lays
-//                    its own out: 64 lanes x 8 points, three radix-8 passes in registers, two exchanges through the wave's own padded LDS
-//                    buffer behind compiler-only wave fences.  x and y are NOT packed as the real and imaginary parts of one transform: that
+//                    from the row (the overlap-added signal is never written; both signals' loads are issued first), and runs the zero-padded 512-point transform that mel.hip
+//                    runs (stockham.h: fft512_888): 64 lanes x 8 points, three radix-8 passes in registers, two exchanges through the wave's
+//                    own padded LDS buffer behind compiler-only wave fences.  x and y are NOT packed as the real and imaginary parts of one transform: that
 //                    would tie y's absolute error to x's magnitude, and a resynthesis 40 dB below its input would lose 40 dB of precision.
 //                    Bins 7 .. 218 become 15 band magnitudes: 60 B per frame and signal.
 //   stoi_segments_k  workgroup = 16 consecutive segments from one staged tile of 45 frames' magnitudes; fp64.  One lane per (segment, band),
@@ -35,8 +35,11 @@
 // file may become an FMA.
 #pragma clang fp contract(off)
 
+#include "stockham.h"
+
 using vtts::failf;
 using vtts_sample::to_float;
+using namespace vtts_stockham;
 
 namespace {
 
@@ -44,8 +47,6 @@ constexpr int FRAME = VTTS_STOI_FRAME, HOP = VTTS_STOI_HOP, NFFT = 512, BANDS = 
 constexpr int FPB = VTTS_STOI_FRAMES_PER_BLOCK;
 constexpr int THREADS = 64 * FPB;
 constexpr int SPAN = (FPB + 1) * HOP;   // samples the FPB candidate frames of a workgroup cover
-constexpr int XROW = 72;                // complex entries per k0 row of the exchange buffer (64 + 8 pad: mel.hip)
-constexpr int XBUF = 8 * XROW;
 constexpr int ROWS_PER_LAUNCH = 128;
 constexpr int SEG_THREADS = 256, SEGS_PER_BLOCK = SEG_THREADS / 16;  // 16 lanes per segment in phase 1: 15 bands and an idle one
 constexpr int TILE_FRAMES = SEGS_PER_BLOCK + SEG - 1;                 // frames the segments of a workgroup cover
@@ -87,48 +88,6 @@ struct StoiArgs {               // every pointer at the launch's first row
 };
 
 __host__ __device__ __forceinline__ long long num_frames(long long S) { return S > FRAME ? (S - FRAME + HOP - 1) / HOP : 0; }
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // -i a
-
-// A[k] = sum_j a_j (-i)^(j k)
-__device__ __forceinline__ void dft4(float2 a0, float2 a1, float2 a2, float2 a3, float2& A0, float2& A1, float2& A2, float2& A3) {
-    const float2 s0 = cadd(a0, a2), d0 = csub(a0, a2), s1 = cadd(a1, a3), d1 = mul_mi(csub(a1, a3));
-    A0 = cadd(s0, s1);
-    A1 = cadd(d0, d1);
-    A2 = csub(s0, s1);
-    A3 = csub(d0, d1);
-}
-// in place: v[k] = sum_a v[a] exp(-2 pi i a k / 8)
-__device__ __forceinline__ void radix8(float2 (&v)[8]) {
-    float2 e0, e1, e2, e3, o0, o1, o2, o3;
-    dft4(v[0], v[2], v[4], v[6], e0, e1, e2, e3);
-    dft4(v[1], v[3], v[5], v[7], o0, o1, o2, o3);
-    const float c = 0.70710678118654752440f;
-    o1 = make_float2(c * (o1.x + o1.y), c * (o1.y - o1.x));   // times W8   = (c, -c)
-    o2 = mul_mi(o2);                                          // times W8^2 = -i
-    o3 = make_float2(c * (o3.y - o3.x), -c * (o3.x + o3.y));  // times W8^3 = (-c, -c)
-    v[0] = cadd(e0, o0), v[4] = csub(e0, o0);
-    v[1] = cadd(e1, o1), v[5] = csub(e1, o1);
-    v[2] = cadd(e2, o2), v[6] = csub(e2, o2);
-    v[3] = cadd(e3, o3), v[7] = csub(e3, o3);
-}
-
-// Orders a wave's LDS writes before its later LDS reads of other lanes' data: no instruction, it only holds the compiler (mel.hip).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the header's halvings h = 32 .. 1 (every lane ends with lane 0's bits: each step adds the same two numbers on both sides)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---- A. candidate frame energies of the clean row ----------------------------------------------------------------------------------
 template <typename TI>
@@ -228,7 +187,6 @@ __global__ __launch_bounds__(THREADS) void stoi_spectra_k(const StoiArgs a, cons
     const long long oc = (long long)kept[tt] * HOP, on = (long long)kept[tt + 1] * HOP;  // tt + 1 <= Kk - 1
     const long long op = tt > 0 ? (long long)kept[tt - 1] * HOP : -1;
     float2* xb = xbuf + wave * XBUF;
-    const int hi = lane >> 3, lo = lane & 7;
 
     // both signals' samples are requested before either transform runs: the second's latency hides behind the first's arithmetic
     float vin[2][4];
@@ -256,29 +214,7 @@ __global__ __launch_bounds__(THREADS) void stoi_spectra_k(const StoiArgs a, cons
 #pragma unroll
         for (int q = 4; q < 8; ++q) v[q] = make_float2(0.0f, 0.0f);  // the zero padding to 512
 
-        // 512 = 8 x 8 x 8, n = 64 a + 8 b + c, k = k0 + 8 k1 + 64 k2 (mel.hip)
-        radix8(v);
-#pragma unroll
-        for (int k0 = 1; k0 < 8; ++k0) v[k0] = cmul(v[k0], tw[lane * k0]);
-#pragma unroll
-        for (int k0 = 0; k0 < 8; ++k0) xb[k0 * XROW + lane] = v[k0];
-        wave_sync();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = xb[hi * XROW + q * 8 + lo];
-        wave_sync();
-        radix8(v);
-#pragma unroll
-        for (int k1 = 1; k1 < 8; ++k1) v[k1] = cmul(v[k1], tw[8 * lo * k1]);
-#pragma unroll
-        for (int k1 = 0; k1 < 8; ++k1) xb[hi * XROW + k1 * 9 + lo] = v[k1];
-        wave_sync();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = xb[hi * XROW + lo * 9 + q];
-        wave_sync();
-        radix8(v);
-#pragma unroll
-        for (int k2 = 0; k2 < 4; ++k2) xb[hi + 8 * lo + 64 * k2] = v[k2];  // Z[k0 + 8 k1 + 64 k2], natural order; bins below 256 only
-        wave_sync();
+        fft512_888<4>(v, xb, tw, lane, [&](int k0) { return tw[lane * k0]; });  // bins below 256 only
 
         float pw[4];
 #pragma unroll
