@@ -51,6 +51,10 @@ MEL_MIN_SAMPLES = 385  # include/vtts_mel.h: VTTS_MEL_MIN_SAMPLES
 DTW_MAX_FEAT = 128  # include/vtts_dtw.h: VTTS_DTW_MAX_FEAT
 DTW_MAX_FRAMES = 4096  # include/vtts_dtw.h: VTTS_DTW_MAX_FRAMES
 
+MCD_MAX_MELS, MCD_MAX_CEPS = 128, 64  # include/vtts_mcd.h: VTTS_MCD_MAX_MELS / _MAX_CEPS
+MCD_FRAMES_PER_BLOCK = 64  # include/vtts_mcd.h: VTTS_MCD_FRAMES_PER_BLOCK
+MCD_ALPHA = 6.141851463713754  # include/vtts_mcd.h: VTTS_MCD_ALPHA = 10 sqrt(2) / ln 10
+
 PITCH_FRAMES_PER_BLOCK = 8  # include/vtts_pitch.h: VTTS_PITCH_FRAMES_PER_BLOCK
 PITCH_MAX_LAG = 512  # include/vtts_pitch.h: VTTS_PITCH_MAX_LAG
 
@@ -84,6 +88,7 @@ LOUDNESS_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/loudness.hip
 SPECTRAL_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/spectral.hip; include/vtts_spectral.h: VTTS_SPECTRAL_ROWS_PER_LAUNCH
 STFT_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stft.hip; include/vtts_stft.h: VTTS_STFT_ROWS_PER_LAUNCH
 DTW_PAIRS_PER_LAUNCH = 128  # viettts_amd/csrc/dtw.hip: PAIRS_PER_LAUNCH
+MCD_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/mcd.hip; include/vtts_mcd.h: VTTS_MCD_ROWS_PER_LAUNCH (its dtw() splits by DTW_PAIRS_PER_LAUNCH)
 LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
 LIMSTREAM_ROWS_PER_LAUNCH = 128  # include/vtts_limstream.h: VTTS_LIMSTREAM_ROWS_PER_LAUNCH
 RSSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_rsstream.h: VTTS_RSSTREAM_MAX_CHUNK
@@ -96,6 +101,10 @@ class MelCfg(C.Structure):
 
 class DtwCfg(C.Structure):
     _fields_ = [("n_feat", C.c_int32), ("band", C.c_int32), ("max_frames", C.c_int32)]
+
+
+class McdCfg(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("n_ceps", C.c_int32), ("band", C.c_int32), ("max_frames", C.c_int32)]
 
 
 class PitchCfg(C.Structure):
@@ -257,6 +266,19 @@ DTW_SIGS = {
 }
 
 
+# include/vtts_mcd.h, likewise a table of its own
+MCD_SIGS = {
+    "vtts_mcd_create": (C.c_int, [C.POINTER(McdCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_mcd_destroy": (None, [vp]),
+    "vtts_mcd_basis": (C.c_int, [vp, fp]),
+    "vtts_mcd_cepstra": (C.c_int, [vp, vp, C.c_int, i64, C.POINTER(C.c_int32), vp, vp]),
+    "vtts_mcd_aligned_workspace_bytes": (C.c_int, [vp, C.c_int, i64, C.POINTER(sz)]),
+    "vtts_mcd_aligned": (C.c_int, [vp, vp, vp, C.c_int, i64, i64, C.POINTER(C.c_int32), vp, vp, i64, vp, sz, vp]),
+    "vtts_mcd_dtw_workspace_bytes": (C.c_int, [vp, C.c_int, i64, i64, C.POINTER(sz)]),
+    "vtts_mcd_dtw": (C.c_int, [vp, vp, vp, C.c_int, i64, i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp, sz, vp]),
+}
+
+
 # include/vtts_pitch.h, likewise a table of its own
 PITCH_SIGS = {
     "vtts_pitch_create": (C.c_int, [C.POINTER(PitchCfg), C.c_int, C.POINTER(vp)]),
@@ -375,6 +397,7 @@ MEL_EXPORTS = _exports("vtts_mel_")  # include/vtts_mel.h
 DISC_EXPORTS = _exports("vtts_disc_")  # include/vtts_disc.h
 AUDIO_EXPORTS = _exports("vtts_audio_")  # include/vtts_audio.h
 DTW_EXPORTS = tuple(DTW_SIGS)  # include/vtts_dtw.h
+MCD_EXPORTS = tuple(MCD_SIGS)  # include/vtts_mcd.h
 PITCH_EXPORTS = tuple(PITCH_SIGS)  # include/vtts_pitch.h
 LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
@@ -436,7 +459,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **STFT_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **MCD_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **STFT_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

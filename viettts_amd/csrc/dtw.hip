@@ -19,119 +19,42 @@
 //   3. dtw_backtrace_k one wave per pair.  The lanes fetch a window of code words (BT_ROWS rows up, BT_WORDS words left of the current
 //                      cell) into LDS, lane 0 walks while the path stays inside: one HBM round trip per >= 16 moves.
 // Barriers inside a workgroup are the only synchronisation; the kernels of one call are ordered by the stream.
+// The launch arguments, the band, the workspace layout, the host checks and the cost kernel's tile map (with the local metric as a parameter) are
+// dtw_common.h's, shared with mcd.hip (include/vtts_mcd.h: the L2 cost over mel cepstra), which runs kernels 2 and 3 through vtts::dtw_path_launch.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
-#include "../../include/vtts_dtw.h"
-#include "../../include/vtts_hifigan.h"
-#include "vtts_internal.h"
+#include "dtw_common.h"
 
 using vtts::failf;
+using vtts::band_range;
+using vtts::DtwArgs;
+using vtts::DtwPairs;
 
 namespace {
 
-constexpr int STRIP = VTTS_DTW_STRIP;
-constexpr int TILE = VTTS_DTW_TILE;
-constexpr int CPW = VTTS_DTW_CODES_PER_WORD;
+constexpr int PAIRS_PER_LAUNCH = 128;
+constexpr int STRIP = vtts::DTW_STRIP;
+constexpr int CPW = vtts::DTW_CPW;
 constexpr int BT_ROWS = VTTS_DTW_BT_ROWS;
 constexpr int BT_WORDS = VTTS_DTW_BT_WORDS;
-constexpr int MAXF = VTTS_DTW_MAX_FRAMES;
-constexpr int PAIRS_PER_LAUNCH = 128;
-constexpr int COST_THREADS = 256;
-constexpr int CELLS = TILE * TILE / COST_THREADS;  // chains per thread of the cost kernel: consecutive steps of one row
-constexpr int AHEAD = 16;                          // steps the wavefront fetches its costs ahead
+constexpr int MAXF = vtts::DTW_MAXF;
+constexpr int AHEAD = 16;  // steps the wavefront fetches its costs ahead
 
-static_assert(STRIP % TILE == 0, "a cost tile lies in one strip");
-static_assert(CELLS == 16 && COST_THREADS / TILE * CELLS == TILE, "the cost kernel's thread map");
 static_assert(BT_ROWS * BT_WORDS == 64, "one code word per lane of the backtrace's wave");
+static_assert(PAIRS_PER_LAUNCH == vtts::DTW_PAIRS_PER_LAUNCH, "DtwPairs (dtw_common.h) holds one launch's lengths");
 
-struct DtwPairs {
-    int la[PAIRS_PER_LAUNCH];
-    int lb[PAIRS_PER_LAUNCH];
+// vtts_dtw.h: local cost, one link of the chain and what is stored
+struct L1Metric {
+    static __device__ __forceinline__ float term(float acc, float a, float b) { return acc + fabsf(a - b); }
+    static __device__ __forceinline__ float finish(float acc) { return acc; }
 };
-
-struct DtwArgs {
-    const float* a;      // first pair of this launch
-    const float* b;
-    char* ws;            // first pair's workspace
-    float* total;
-    int* path_len;
-    int* span;
-    long long ta_stride, tb_stride;
-    long long pair_bytes;   // workspace bytes per pair
-    long long cost_floats;  // of which the cost matrix; the code words follow
-    int steps;              // skewed columns per strip (vtts_dtw.h: steps)
-    int code_words;         // code words per row
-    int D, band;
-};
-
-__host__ __device__ inline long long floor_div(long long a, long long b) {  // b > 0
-    long long q = a / b;
-    return (a % b != 0 && a < 0) ? q - 1 : q;
-}
-
-// Row i's allowed columns [jlo, jhi] (vtts_dtw.h: band), exactly: j (la - 1) within R of i (lb - 1).
-__device__ __forceinline__ void band_range(int i, int la, int lb, int band, int& jlo, int& jhi) {
-    jlo = 0;
-    jhi = lb - 1;
-    if (band > 0 && la > 1) {
-        const long long m = la - 1, c = (long long)i * (lb - 1), R = (long long)band * (la > lb ? la - 1 : lb - 1);
-        const long long lo = -floor_div(-(c - R), m), hi = floor_div(c + R, m);  // ceil, floor
-        if (lo > jlo) jlo = (int)(lo < lb ? lo : lb);
-        if (hi < jhi) jhi = (int)hi;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(COST_THREADS) void dtw_cost_k(DtwArgs g, DtwPairs p) {
+__global__ __launch_bounds__(vtts::DTW_COST_THREADS) void dtw_cost_k(DtwArgs g, DtwPairs p) {
     extern __shared__ float lds[];
-    const int n = blockIdx.z, la = p.la[n], lb = p.lb[n];
-    const int i0 = blockIdx.y * TILE, s0 = blockIdx.x * TILE;
-    if (i0 >= la) return;
-    const int strip = i0 / STRIP, l0 = i0 % STRIP;
-    const int jmin = s0 - (l0 + TILE - 1), jmax = s0 + TILE - 1 - l0;  // columns the tile's cells have
-    if (jmax < 0 || jmin >= lb) return;
-    const int ilast = (i0 + TILE - 1 < la ? i0 + TILE - 1 : la - 1);
-    {
-        int lo, hi, lo2, hi2;
-        band_range(i0, la, lb, g.band, lo, hi);
-        band_range(ilast, la, lb, g.band, lo2, hi2);
-        if (hi2 < jmin || lo > jmax) return;  // jlo and jhi grow with i: no row of the tile has an allowed column in it
-    }
-    const int D = g.D, P = D | 1;
-    float* A = lds;             // [TILE][P]
-    float* B = lds + TILE * P;  // [2 TILE - 1][P]
-    const float* a = g.a + (size_t)n * g.ta_stride * D;
-    const float* b = g.b + (size_t)n * g.tb_stride * D;
-    for (int idx = threadIdx.x; idx < TILE * D; idx += COST_THREADS) {
-        const int r = idx / D, d = idx - r * D, i = i0 + r;
-        A[r * P + d] = i < la ? a[(size_t)i * D + d] : 0.0f;
-    }
-    for (int idx = threadIdx.x; idx < (2 * TILE - 1) * D; idx += COST_THREADS) {
-        const int r = idx / D, d = idx - r * D, j = jmin + r;
-        B[r * P + d] = (j >= 0 && j < lb) ? b[(size_t)j * D + d] : 0.0f;
-    }
-    __syncthreads();
-    const int r = threadIdx.x & (TILE - 1), k0 = (threadIdx.x / TILE) * CELLS;  // row of the tile; first of the thread's steps
-    const float* ar = A + r * P;
-    const float* br = B + (k0 - r + TILE - 1) * P;  // column s0 + k0 - (l0 + r), as a row of B
-    float acc[CELLS];
-#pragma unroll
-    for (int k = 0; k < CELLS; ++k) acc[k] = 0.0f;
-    for (int d = 0; d < D; ++d) {
-        const float av = ar[d];
-#pragma unroll
-        for (int k = 0; k < CELLS; ++k) acc[k] = acc[k] + fabsf(av - br[k * P + d]);
-    }
-    if (i0 + r >= la) return;
-    float* cost = reinterpret_cast<float*>(g.ws + (size_t)n * g.pair_bytes);
-    const int l = l0 + r;
-#pragma unroll
-    for (int k = 0; k < CELLS; ++k) {
-        const int s = s0 + k0 + k, j = s - l;
-        if (j >= 0 && j < lb) cost[((size_t)strip * g.steps + s) * STRIP + l] = acc[k];
-    }
+    vtts::dtw_cost_tile<L1Metric>(g, p, lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -288,36 +211,16 @@ __global__ __launch_bounds__(64) void dtw_backtrace_k(DtwArgs g, DtwPairs p) {
 
 }  // namespace
 
+void vtts::dtw_path_launch(const DtwArgs& g, const DtwPairs& pairs, int np, hipStream_t s) {
+    hipLaunchKernelGGL(dtw_wavefront_k, dim3(np), dim3(STRIP), 0, s, g, pairs);
+    hipLaunchKernelGGL(dtw_backtrace_k, dim3(np), dim3(64), 0, s, g, pairs);
+}
+
 struct vtts_dtw {
     vtts_dtw_cfg cfg;
     int device;
     vtts::DynLdsOnce lds_cost;
 };
-
-namespace {
-
-struct Layout {
-    long long steps, code_words, cost_floats, pair_bytes;
-};
-
-Layout layout(int64_t ta, int64_t tb) {
-    Layout L;
-    const long long strips = (ta + STRIP - 1) / STRIP;
-    L.steps = (tb + STRIP - 1 + TILE - 1) / TILE * TILE;
-    L.cost_floats = strips * L.steps * STRIP;
-    L.code_words = (tb + CPW - 1) / CPW;
-    L.pair_bytes = (4 * (L.cost_floats + ta * L.code_words) + 255) / 256 * 256;
-    return L;
-}
-
-int check_shape(const vtts_dtw* h, int N, int64_t ta, int64_t tb) {
-    if (N <= 0) return failf(VTTS_ERR_INVALID, "N must be positive (got %d)", N);
-    if (ta < 1 || tb < 1 || ta > h->cfg.max_frames || tb > h->cfg.max_frames)
-        return failf(VTTS_ERR_INVALID, "Ta_stride and Tb_stride must be in 1 .. max_frames = %d (got %lld, %lld)", h->cfg.max_frames, (long long)ta, (long long)tb);
-    return VTTS_OK;
-}
-
-}  // namespace
 
 VTTS_API int vtts_dtw_create(const vtts_dtw_cfg* cfg, int device, vtts_dtw** out) {
     if (!cfg || !out) return failf(VTTS_ERR_INVALID, "null argument");
@@ -336,8 +239,8 @@ VTTS_API void vtts_dtw_destroy(vtts_dtw* h) { delete h; }
 
 VTTS_API int vtts_dtw_workspace_bytes(const vtts_dtw* h, int N, int64_t Ta_stride, int64_t Tb_stride, size_t* bytes) {
     if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
-    if (int rc = check_shape(h, N, Ta_stride, Tb_stride)) return rc;
-    *bytes = (size_t)N * (size_t)layout(Ta_stride, Tb_stride).pair_bytes;
+    if (int rc = vtts::dtw_check_shape(h->cfg.max_frames, N, Ta_stride, Tb_stride)) return rc;
+    *bytes = (size_t)N * (size_t)vtts::dtw_layout(Ta_stride, Tb_stride).pair_bytes;
     return VTTS_OK;
 }
 
@@ -345,52 +248,16 @@ VTTS_API int vtts_dtw_forward(vtts_dtw* h, const float* a_dev, const float* b_de
                               const int32_t* lb, float* total_dev, int32_t* path_len_dev, int32_t* span_dev, void* workspace, size_t workspace_bytes,
                               void* stream) {
     if (!h || !a_dev || !b_dev || !la || !lb || !total_dev || !path_len_dev || !span_dev) return failf(VTTS_ERR_INVALID, "null argument");
-    if (int rc = check_shape(h, N, Ta_stride, Tb_stride)) return rc;
-    for (int n = 0; n < N; ++n)
-        if (la[n] < 1 || la[n] > Ta_stride || lb[n] < 1 || lb[n] > Tb_stride)
-            return failf(VTTS_ERR_INVALID, "pair %d: la = %d, lb = %d are outside 1 .. Ta_stride = %lld, 1 .. Tb_stride = %lld", n, la[n], lb[n],
-                         (long long)Ta_stride, (long long)Tb_stride);
-    const Layout L = layout(Ta_stride, Tb_stride);
-    const size_t need = (size_t)N * (size_t)L.pair_bytes;
-    if (!workspace || workspace_bytes < need) return failf(VTTS_ERR_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) % 256) return failf(VTTS_ERR_INVALID, "workspace must be 256-byte aligned");
-
+    DtwArgs call;
+    if (int rc = vtts::dtw_check_call(h->cfg.max_frames, h->cfg.n_feat, h->cfg.band, N, Ta_stride, Tb_stride, la, lb, workspace, workspace_bytes, &call)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int D = h->cfg.n_feat;
-    const size_t lds = (size_t)(3 * TILE - 1) * (D | 1) * sizeof(float);
+    const size_t lds = vtts::dtw_cost_lds_bytes(call.D);
     hipError_t e = vtts::set_max_dynamic_lds(reinterpret_cast<const void*>(&dtw_cost_k), (int)lds, h->lds_cost);
     if (e != hipSuccess) return failf(VTTS_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    DtwArgs g;
-    g.ta_stride = Ta_stride;
-    g.tb_stride = Tb_stride;
-    g.pair_bytes = L.pair_bytes;
-    g.cost_floats = L.cost_floats;
-    g.steps = (int)L.steps;
-    g.code_words = (int)L.code_words;
-    g.D = D;
-    g.band = h->cfg.band;
-    for (int n0 = 0; n0 < N; n0 += PAIRS_PER_LAUNCH) {  // the lengths travel as kernel arguments
-        const int np = N - n0 < PAIRS_PER_LAUNCH ? N - n0 : PAIRS_PER_LAUNCH;
-        DtwPairs pairs;
-        int la_max = 1, lb_max = 1;
-        for (int k = 0; k < PAIRS_PER_LAUNCH; ++k) {
-            pairs.la[k] = k < np ? la[n0 + k] : 1;
-            pairs.lb[k] = k < np ? lb[n0 + k] : 1;
-            if (pairs.la[k] > la_max) la_max = pairs.la[k];
-            if (pairs.lb[k] > lb_max) lb_max = pairs.lb[k];
-        }
-        g.a = a_dev + (size_t)n0 * Ta_stride * D;
-        g.b = b_dev + (size_t)n0 * Tb_stride * D;
-        g.ws = static_cast<char*>(workspace) + (size_t)n0 * L.pair_bytes;
-        g.total = total_dev + n0;
-        g.path_len = path_len_dev + n0;
-        g.span = span_dev + (size_t)n0 * Ta_stride * 2;
-        const int row_tiles = (la_max + TILE - 1) / TILE;
-        const int rows_in_strip = la_max < STRIP ? la_max : STRIP;
-        const int step_tiles = (lb_max + rows_in_strip - 1 + TILE - 1) / TILE;
-        hipLaunchKernelGGL(dtw_cost_k, dim3(step_tiles, row_tiles, np), dim3(COST_THREADS), lds, s, g, pairs);
-        hipLaunchKernelGGL(dtw_wavefront_k, dim3(np), dim3(STRIP), 0, s, g, pairs);
-        hipLaunchKernelGGL(dtw_backtrace_k, dim3(np), dim3(64), 0, s, g, pairs);
+    for (int n0 = 0; n0 < N; n0 += PAIRS_PER_LAUNCH) {
+        const vtts::DtwSlice sl = vtts::dtw_slice(call, a_dev, b_dev, la, lb, total_dev, path_len_dev, span_dev, workspace, N, n0);
+        hipLaunchKernelGGL(dtw_cost_k, sl.cost_grid, dim3(vtts::DTW_COST_THREADS), lds, s, sl.g, sl.pairs);
+        vtts::dtw_path_launch(sl.g, sl.pairs, sl.np, s);
         e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "dtw kernel launch failed: %s", hipGetErrorString(e));
     }

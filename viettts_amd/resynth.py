@@ -2,7 +2,7 @@
 standard check of a vocoder checkpoint, and the mel-domain distance between two waveforms (the quantity HiFi-GAN's mel loss is
 computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter`` writes the ``[N, T, 80]`` layout the generator reads.
 
-    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi] [--mrstft]
+    python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi] [--mrstft] [--mcd]
     python -m viettts_amd.resynth --input in.wav --output out.wav --vocoder griffinlim      # no checkpoint at all: viettts_amd.stft
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
@@ -98,6 +98,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--limit", action="store_true", help="with --loudness: the full gain to the target and a look-ahead limiter under -1 dBTP (viettts_amd.limiter) in place of the sample-peak cap")
     ap.add_argument("--stoi", action="store_true", help="also print STOI and ESTOI of the result against the input at 10 kHz (viettts_amd.stoi); NaN below 30 analysis frames")
     ap.add_argument("--mrstft", action="store_true", help="also print the multi-resolution STFT distance and the log-spectral distance of the result against the input (viettts_amd.spectral); needs 1025 samples")
+    ap.add_argument("--mcd", action="store_true", help="also print the mel-cepstral distortion in dB of the result against the input, frame by frame (viettts_amd.mcd: 13 log-mel cepstra, c0 left out)")
     ap.add_argument("--vocoder", default="hifigan", choices=("hifigan", "griffinlim"), help="griffinlim: log-mel -> wav by Griffin-Lim on the GPU (viettts_amd.stft): "
                     "no checkpoint is opened; --dtype does not apply")
     return ap
@@ -171,6 +172,10 @@ def main(argv=None) -> None:
         from .spectral import format_result as format_mrstft, wav_mrstft
 
         print(format_mrstft(wav_mrstft(y[:, :n].contiguous(), wav[:, :n].contiguous())))
+    if a.mcd:
+        from .mcd import wav_mcd
+
+        print(f"MCD {float(wav_mcd(y[:, :n].contiguous(), wav[:, :n].contiguous())[0]):.3f} dB of the result against the input ({n // 256} frames, 13 log-mel cepstra)")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Score a vocoder checkpoint with the objective HiFi-GAN optimises, on the GPU: wav -> log-mel (``MelFilter``) -> generator ->
 (y, y_hat) through the discriminators (``Discriminators``, include/vtts_disc.h), segment by segment.
 
-    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness] [--stoi] [--mrstft]
+    python -m viettts_amd.vocoder_eval --wav a.wav b.wav --generator hk_hifi.pickle --discriminator do_02500000 [--segment 8192] [--f0] [--loudness] [--stoi] [--mrstft] [--mcd]
 
 prints, averaged over the segments, the adversarial term (generator_loss of MPD + MSD), the feature-matching term (feature_loss of
 MPD + MSD), the log-mel L1 and their HiFi-GAN sum ``adv + fm + 45 * mel``.  Reads PCM16 mono (any rate but the model's is converted
@@ -12,6 +12,7 @@ generator as ``mel2wave`` reads it (``assets/hifigan/config.json`` + a Haiku pic
 ``--stoi`` adds one line: STOI and ESTOI of ``y_hat`` against ``y`` (``viettts_amd.stoi``), each pass's segments laid end to end as one row.
 ``--mrstft`` adds one line: the multi-resolution STFT distance (spectral convergence + log-magnitude L1 at Parallel WaveGAN's three resolutions)
 and the log-spectral distance of ``y_hat`` against ``y`` (``viettts_amd.spectral``), per segment, averaged.
+``--mcd`` adds one line: the mel-cepstral distortion in dB of ``y_hat`` against ``y``, frame by frame (``viettts_amd.mcd``), per segment, averaged.
 """
 from __future__ import annotations
 
@@ -29,9 +30,10 @@ F0_KEYS = ("f0_rmse_cents", "voicing_error", "gross_error")  # what score_segmen
 LOUDNESS_KEYS = ("lufs_y", "lufs_y_hat")  # ... and with a meter
 STOI_KEYS = ("stoi", "estoi")  # ... and with a stoi_meter
 SPECTRAL_KEYS = ("mrstft", "sc", "logmag", "lsd")  # ... and with spectral
+MCD_KEYS = ("mcd",)  # ... and with mcd
 
 
-def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None, stoi_meter=None, rate=None, spectral=None) -> dict:
+def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, tracker=None, meter=None, stoi_meter=None, rate=None, spectral=None, mcd=None) -> dict:
     """``y [B, S]`` float32 on the device, S a multiple of 256: one generator pass, one 2 B-row discriminator pass, one reduction.
     With ``tracker`` (a ``viettts_amd.pitch.PitchTracker``) the result also holds ``f0_rmse_cents``, ``voicing_error`` and ``gross_error`` of
     ``y_hat`` against ``y`` (``pitch.f0_metrics``); with ``meter`` (a ``viettts_amd.loudness.LoudnessMeter``) ``lufs_y`` and ``lufs_y_hat``: the
@@ -40,7 +42,8 @@ def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, 
     model's without it) and converted to 10 kHz on the device (nan when the row holds no 30-frame segment); with ``spectral`` (a
     ``viettts_amd.spectral.MultiResolutionStft``) ``mrstft``, ``sc``, ``logmag`` and ``lsd`` of ``y_hat`` against ``y``: each segment is a row
     of its own (it must hold the largest ``n_fft / 2 + 1`` samples), the figures are the means over the segments of the means over the
-    resolutions."""
+    resolutions; with ``mcd`` (a ``viettts_amd.mcd.Mcd``) ``mcd``: the aligned mel-cepstral distortion in dB of ``y_hat`` against ``y``, the
+    mean over the segments."""
     from .resynth import default_mel_filter, log_mel_l1
 
     mf = mel_filter or default_mel_filter(generator.device)
@@ -67,6 +70,8 @@ def score_segments(y: torch.Tensor, generator, discriminators, mel_filter=None, 
         k = float(len(r.per_resolution))
         out.update(mrstft=float(r.mrstft.mean()), sc=float(sum(p.sc for p in r.per_resolution).mean() / k),
                    logmag=float(sum(p.logmag for p in r.per_resolution).mean() / k), lsd=float(r.lsd.mean()))
+    if mcd is not None:
+        out.update(mcd=float(mcd.aligned(mf(y_hat), mf(y)).mean()))
     return out
 
 
@@ -85,6 +90,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "after its silent ones are dropped (one segment much shorter than 8192) gives NaN and is left out of the mean")
     ap.add_argument("--mrstft", action="store_true", help="also print the multi-resolution STFT distance (spectral convergence + log-magnitude L1 at n_fft 1024, "
                     "2048 and 512) and the log-spectral distance of y_hat against y (viettts_amd.spectral), per segment: --segment must be at least 1025")
+    ap.add_argument("--mcd", action="store_true", help="also print the mel-cepstral distortion in dB of y_hat against y, frame by frame (viettts_amd.mcd: 13 log-mel "
+                    "cepstra, c0 left out), per segment")
     return ap
 
 
@@ -138,10 +145,15 @@ def main(argv=None) -> None:
         from .spectral import default_mrstft
 
         spectral = default_mrstft(dev)
+    mcd = None
+    if a.mcd:
+        from .mcd import default_mcd
+
+        mcd = default_mcd(dev)
     tot, n, f0_tot, f0_n = {}, 0, {}, {}
     for i in range(0, len(segs), a.batch):
         y = torch.from_numpy(np.stack(segs[i : i + a.batch])).to(dev)
-        r = score_segments(y, gen, disc, tracker=trk, meter=meter, stoi_meter=stoi_meter, spectral=spectral)
+        r = score_segments(y, gen, disc, tracker=trk, meter=meter, stoi_meter=stoi_meter, spectral=spectral, mcd=mcd)
         f0 = {k: r.pop(k) for k in F0_KEYS + LOUDNESS_KEYS + STOI_KEYS if k in r}
         for k, v in r.items():
             tot[k] = tot.get(k, 0.0) + v * y.shape[0]
@@ -155,6 +167,8 @@ def main(argv=None) -> None:
     if spectral is not None:
         print(f"spectral distance of y_hat against y, mean over the segments: multi-resolution STFT {m['mrstft']:.4f}  (SC {m['sc']:.4f} + log-mag L1 "
               f"{m['logmag']:.4f})  LSD {m['lsd']:.2f} dB")
+    if mcd is not None:
+        print(f"mel-cepstral distortion of y_hat against y, mean over the segments: MCD {m['mcd']:.3f} dB")
     if trk is not None:
         f = {k: f0_tot[k] / f0_n[k] if f0_n.get(k) else float("nan") for k in F0_KEYS}
         print(f"F0 of y_hat against y, mean over the passes: RMSE {f['f0_rmse_cents']:.1f} cents  voicing error {100 * f['voicing_error']:.2f} %  "
