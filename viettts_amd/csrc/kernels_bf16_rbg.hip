@@ -52,10 +52,13 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&&
 constexpr int XCD_MAP_MIN_TILES = 192;  // XCD-aware tile order from this many tiles per utterance slot on (resblock_pair_g_bf16_k)
 
 // BLK_: the MFMA block shape of the two convolution loops, 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (see g_mfma_blk below).
-// It is the LAST parameter: rocprofv3's kernel names are matched by their prefix up to KS (pair_g_kernel_name).
-template <int C_, int KS_, int N1_, int WM_, int WN_, int PA_, int MINWG_, int XC_ = C_, int BLK_ = 32>
+// RS_ (BLK_ = 16 only, see g_res_slots below): bit 0 = c2's last block requests the residual rows in its look-ahead slots past the pass's end,
+// bit 1 = c1's last block requests nothing in them.  0 = both passes re-read the last weight step there.
+// They are the LAST parameters: rocprofv3's kernel names are matched by their prefix up to KS (pair_g_kernel_name).
+template <int C_, int KS_, int N1_, int WM_, int WN_, int PA_, int MINWG_, int XC_ = C_, int BLK_ = 32, int RS_ = 0>
 struct GTile {
-    static constexpr int C = C_, KS = KS_, N1 = N1_, WM = WM_, WN = WN_, PA = PA_, MINWG = MINWG_, BLK = BLK_;
+    static constexpr int C = C_, KS = KS_, N1 = N1_, WM = WM_, WN = WN_, PA = PA_, MINWG = MINWG_, BLK = BLK_, RS = RS_;
+    static_assert(RS == 0 || BLK == 16, "the look-ahead slots past the end are the 16-block loop's");
     static constexpr int XC = XC_, NXC = C / XC;        // the X tile is staged XC input channels at a time (C = 256: 2 x 128)
     // BLK = 16: a wave's 64 x (N1 / WN) tile as MR16 x NR16 blocks of 16 x 16; the loop's unit is one k = 32 step over 4 column blocks
     static constexpr int MR16 = C / WM / 16, NR16 = N1 / WN / 16, NH = NR16 / 4;
@@ -500,9 +503,28 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
     // C = 64 has two k = 32 steps per tap: a block of UB = 4 steps (one turn of the weight ring) then spans two taps, and the k = 7 / 11 passes
     // (14 / 22 steps) end in a peeled half block that requests nothing further.
     const int rowbase16 = wn * (N1 / WN) + l15;
-    auto conv_phase16 = [&](const unsigned char* __restrict__ wconv, int dl, auto sprb_tag, auto nks_tag, int ks0, auto fresh_tag) {
+    // T::RS: the last LA16 steps of a pass have no weight step left to request, and their look-ahead slots (LA16 x MR16 = 12 loads per wave, into ring
+    // slots that are dead from there on) re-read the last one.  The pass's last block is peeled instead.  c2's (bit 0) requests the residual rows
+    // x[t][c] of epilogue 2 there, one uint4 per (mr, j) as add_rows would: a wave's own vector-memory instructions between its own MFMAs issue
+    // for free, those of epilogue 2 wait for holes in the co-resident workgroup's MFMA stream (profiles/res_slots_findings.md).  Row q of the
+    // RS_ROWS = MR16 x NR16 / 2 is (mr, j) = (q % MR16, q / MR16): the MR16 rows of a step share their time row.  Narrow tiles: all 8 ride, in the first
+    // two steps past the end.  Wide tiles (238 - 255 VGPRs without them): the 4 rows of the LAST step past the end ride and epilogue 2 requests the other 12
+    // behind the loop; with 8 or 12 in the loop, or the last 4 in the B double buffer's dead half of the last unit, hipcc spills 5 - 27 VGPRs
+    // (profiles/res_slots_findings.md, section 2).  c1's (bit 1) requests nothing there.
+    constexpr bool RS_C2 = B16 && (T::RS & 1) != 0, RS_C1 = B16 && (T::RS & 2) != 0;
+    constexpr int RS_PE0 = NH == 2 ? 2 : 0;  // the first step past the end whose slots carry rows
+    constexpr int RS_ROWS = MR16 * (NR16 / 2), RS_SLOTS = (T::LA16 - RS_PE0) * MR16, RS_RIDE = RS_ROWS < RS_SLOTS ? RS_ROWS : RS_SLOTS;
+    [[maybe_unused]] uint4 rv16[RS_C2 ? MR16 : 1][RS_C2 ? NR16 / 2 : 1];
+    [[maybe_unused]] auto res_req = [&](auto q_tag) {
+        constexpr int q = decltype(q_tag)::value, mr = q % MR16, j = q / MR16;
+        const int t = t0 + wn * (N1 / WN) + 16 * (lg & 1) + l15 + 32 * j;
+        const int tc = t < 0 ? 0 : (t < L ? t : L - 1);  // rows outside the utterance are never stored: any in-bounds address will do
+        rv16[RS_C2 ? mr : 0][RS_C2 ? j : 0] = *reinterpret_cast<const uint4*>(xg + (size_t)tc * C + wm * (C / T::WM) + mr * 16 + 8 * (lg >> 1));
+    };
+    auto conv_phase16 = [&](const unsigned char* __restrict__ wconv, int dl, auto sprb_tag, auto nks_tag, int ks0, auto fresh_tag, auto res_tag) {
         constexpr int SPRB = decltype(sprb_tag)::value, PB = SPRB * 16, NKS = decltype(nks_tag)::value;  // NKS: this pass's k = 32 steps per tap
         constexpr bool FRESH = decltype(fresh_tag)::value;
+        constexpr int RES = decltype(res_tag)::value;  // the slots past the end: 0 = re-read the last step, 1 = request nothing, 2 = the residual rows
         constexpr int NSTEPS = KS * NKS, LA = T::LA16, RA = T::RA16, UB = 4, APU = MR16 / NH;  // APU: A fragments loaded per unit
         constexpr int REM = NSTEPS % UB;  // steps of the peeled last block
         static_assert((NKS % UB == 0 || UB % NKS == 0) && UB % RA == 0 && (UB * NH) % 2 == 0, "ring slot / B parity must be compile-time in the block loop");
@@ -555,9 +577,11 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         load_b(ta0, xs0, 0, 0, std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_group_barrier(0x020, MR16 * LA, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        auto block = [&](int s0, auto nu_tag) {  // NU steps: UB of one tap or of UB / NKS taps, or the peeled REM (nothing left to request but its own B fragments)
+        // END (RES != 0): the steps from s0 to the pass's end in the blocks peeled at it (the last UB, or UB + REM in two blocks), 0 inside the loop
+        auto block = [&](int s0, auto nu_tag, auto end_tag) {  // NU steps: UB of one tap or of UB / NKS taps, or the peeled REM (nothing left to request but its own B fragments)
             constexpr int NU = decltype(nu_tag)::value, NT = NKS >= UB ? 1 : (NU + NKS - 1) / NKS;  // NT: the taps its steps span
-            constexpr bool PEEL = NU < UB;
+            constexpr int END = decltype(end_tag)::value;
+            constexpr bool PEEL = NU < UB, ATEND = END > 0, FINAL = ATEND && NU == END;  // FINAL: no block follows
             const int tap = s0 / NKS, ksb = s0 - tap * NKS;  // NKS < UB: ksb = 0
             unsigned ta[NT], xs[NT], tn, xn;
 #pragma unroll
@@ -571,18 +595,24 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                 constexpr int ti = NKS >= UB ? 0 : i / NKS, ki = i - ti * NKS;          // step i: tap + ti, k-step ksb + ki
                 constexpr int tj = NKS >= UB ? 0 : (i + 1) / NKS, kj = i + 1 - tj * NKS;  // step i + 1
                 constexpr bool last = h + 1 == NH && i + 1 == NU;
-                if constexpr (!PEEL) load_a(s0 + i + LA, std::integral_constant<int, h>{}, std::integral_constant<int, (i + LA) % RA>{});
+                // ATEND: the look-ahead step s0 + i + LA lies PE steps past the pass's end; its unit's slots are rows Q0 .. Q0 + APU - 1
+                constexpr bool past = ATEND && i + LA >= END;
+                constexpr int PE = past ? i + LA - END : 0, Q0 = PE >= RS_PE0 ? ((PE - RS_PE0) * NH + h) * APU : RS_ROWS;
+                constexpr int NRES = RES == 2 && past ? (Q0 + APU <= RS_RIDE ? APU : (Q0 < RS_RIDE ? RS_RIDE - Q0 : 0)) : 0;
+                if constexpr (past) {
+                    static_for(std::make_integer_sequence<int, NRES>{}, [&](auto r) { res_req(std::integral_constant<int, Q0 + decltype(r)::value>{}); });
+                } else if constexpr (!PEEL) load_a(s0 + i + LA, std::integral_constant<int, h>{}, std::integral_constant<int, (i + LA) % RA>{});
                 constexpr auto par = std::integral_constant<int, (u + 1) & 1>{};
                 if constexpr (h + 1 < NH) load_b(ta[ti], xs[ti], ksb + ki, h + 1, par);
                 else if constexpr (i + 1 < NU) load_b(ta[tj], xs[tj], ksb + kj, 0, par);
-                else if constexpr (!PEEL) load_b(tn, xn, ksn, 0, par);
+                else if constexpr (!PEEL && !FINAL) load_b(tn, xn, ksn, 0, par);
                 // column block outermost: the unit's last fragment read is first needed 12 MFMAs into the next unit
 #pragma unroll
                 for (int nr = 0; nr < 4; ++nr)
 #pragma unroll
                     for (int mr = 0; mr < MR16; ++mr)
                         acc16[mr][4 * h + nr] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i % RA][mr], bf[u & 1][nr], acc16[mr][4 * h + nr], 0, 0, 0);
-                pin_unit(std::integral_constant<int, PEEL && last ? 0 : 4>{}, std::integral_constant<int, PEEL ? 0 : APU>{});
+                pin_unit(std::integral_constant<int, (PEEL || FINAL) && last ? 0 : 4>{}, std::integral_constant<int, past ? NRES : PEEL ? 0 : APU>{});
             });
         };
         // The bias block as the first step's C operand (as in the 32-block loop) needs that step's block peeled, and the peeled copy — ring full, bias
@@ -594,9 +624,21 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 #pragma unroll
                 for (int nr = 0; nr < NR16; ++nr) acc16[mr][nr] = bblk16[mr];
         }
+        constexpr auto in_loop = std::integral_constant<int, 0>{};
+        if constexpr (RES == 0) {
 #pragma nounroll
-        for (int s0 = 0; s0 < NSTEPS - REM; s0 += UB) block(s0, std::integral_constant<int, UB>{});
-        if constexpr (REM != 0) block(NSTEPS - REM, std::integral_constant<int, REM>{});
+            for (int s0 = 0; s0 < NSTEPS - REM; s0 += UB) block(s0, std::integral_constant<int, UB>{}, in_loop);
+            if constexpr (REM != 0) block(NSTEPS - REM, std::integral_constant<int, REM>{}, in_loop);
+        } else {
+            static_assert(NSTEPS >= 2 * UB + REM, "a loop in front of the peeled end");
+#pragma nounroll
+            for (int s0 = 0; s0 < NSTEPS - REM - UB; s0 += UB) block(s0, std::integral_constant<int, UB>{}, in_loop);
+            block(NSTEPS - REM - UB, std::integral_constant<int, UB>{}, std::integral_constant<int, UB + REM>{});
+            if constexpr (REM != 0) block(NSTEPS - REM, std::integral_constant<int, REM>{}, std::integral_constant<int, REM>{});
+            // the peeled end is one basic block with the epilogue behind it: keep the scheduler from pulling the epilogue's VALU work (the rows'
+            // conversion to fp32 doubles their registers) up between the MFMAs
+            __builtin_amdgcn_sched_barrier(0);
+        }
     };
 
     // ---------------- phase 1: xt = c1(lrelu(x)); column n <-> xt time t0 - H2 + n; tap j reads X row n + j*dil ----------------
@@ -608,8 +650,8 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
             __syncthreads();
         }
         if constexpr (B16) {
-            if (xc == 0) conv_phase16(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, T::KSX32>{}, 0, std::true_type{});
-            else conv_phase16(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, T::KSX32>{}, xc * T::KSX32, std::false_type{});
+            if (xc == 0) conv_phase16(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, T::KSX32>{}, 0, std::true_type{}, std::integral_constant<int, RS_C1 ? 1 : 0>{});
+            else conv_phase16(static_cast<const unsigned char*>(a.wp), dil, std::integral_constant<int, SPR1>{}, std::integral_constant<int, T::KSX32>{}, xc * T::KSX32, std::false_type{}, std::integral_constant<int, RS_C1 ? 1 : 0>{});
         } else if constexpr (T::WREG)
             conv_phase_wreg(dil, std::integral_constant<int, SPR1>{});
         else if (xc == 0)
@@ -685,7 +727,7 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
 
     // ---------------- phase 2: c2 over the xt tile (rate 1): column n <-> time t0 + n, tap j reads xt row n + j ----------------
     if constexpr (B16)
-        conv_phase16(static_cast<const unsigned char*>(a.wp) + T::CONV_BYTES, 1, std::integral_constant<int, SPR2>{}, std::integral_constant<int, T::KS32>{}, 0, std::true_type{});
+        conv_phase16(static_cast<const unsigned char*>(a.wp) + T::CONV_BYTES, 1, std::integral_constant<int, SPR2>{}, std::integral_constant<int, T::KS32>{}, 0, std::true_type{}, std::integral_constant<int, RS_C2 ? 2 : 0>{});
     else if constexpr (T::WREG)
         conv_phase_wreg(1, std::integral_constant<int, SPR2>{});
     else
@@ -699,9 +741,14 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
         const float rdv = mrf_recip(dv);
         unsigned short* __restrict__ yg = static_cast<unsigned short*>(a.y) + (size_t)b * Lp * C;
         // rows of a [B][L][C] tensor in the swapped accumulator layout: all requests first, one wait
-        auto add_rows = [&](const unsigned short* __restrict__ src) {
+        // rode_tag (T::RS bit 0, the residual rows only): the rows are in rv16, requested from inside c2's last block
+        auto add_rows = [&](const unsigned short* __restrict__ src, auto rode_tag) {
             if constexpr (B16) {
-                uint4 rv[MR16][NR16 / 2];
+                constexpr bool RODE = decltype(rode_tag)::value;
+                uint4 rv[RODE ? 1 : MR16][RODE ? 1 : NR16 / 2];
+                if constexpr (RODE) {  // the rows that did not ride
+                    static_for(std::make_integer_sequence<int, RS_ROWS - RS_RIDE>{}, [&](auto r) { res_req(std::integral_constant<int, RS_RIDE + decltype(r)::value>{}); });
+                } else {
 #pragma unroll
                 for (int mr = 0; mr < MR16; ++mr)
 #pragma unroll
@@ -710,11 +757,18 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                         const int tc = t < 0 ? 0 : (t < L ? t : L - 1);  // rows outside the utterance are never stored: any in-bounds address will do
                         rv[mr][j] = *reinterpret_cast<const uint4*>(src + (size_t)tc * C + wm * (C / T::WM) + mr * 16 + 8 * (lg >> 1));
                     }
+                }
+#if VTTS_TIMELINE
+                VTTS_TL(a, wg_lin, 10);
+                __builtin_amdgcn_s_waitcnt(0x0f70);
+                VTTS_TL(a, wg_lin, 11);
+#endif
 #pragma unroll
-                for (int mr = 0; mr < MR16; ++mr)
-#pragma unroll
-                    for (int j = 0; j < NR16 / 2; ++j) {
-                        uint4 r = rv[mr][j];
+                for (int q = 0; q < RS_ROWS; ++q) {
+                        const int mr = RODE ? q % MR16 : q / (NR16 / 2), j = RODE ? q / MR16 : q % (NR16 / 2);  // RODE: in the order requested
+                        uint4 r;
+                        if constexpr (RODE) r = rv16[mr][j];
+                        else r = rv[mr][j];
                         swap_pair16(r.x, r.z);  // un-swap the chunk into the accumulator layout
                         swap_pair16(r.y, r.w);
                         f32x4& ap = acc16[mr][2 * j];
@@ -776,9 +830,9 @@ __global__ __launch_bounds__(T::THREADS, (T::MINWG * T::THREADS + 255) / 256) vo
                         acc[mr][nr][r0 + 6] = vadd_raw(bf16_lo(r.w), acc[mr][nr][r0 + 6]); acc[mr][nr][r0 + 7] = vadd_raw(bf16_hi(r.w), acc[mr][nr][r0 + 7]);
                     }
         } else {
-            add_rows(xg);                                                   // x = xt + x        (model.py:50)
+            add_rows(xg, std::integral_constant<bool, RS_C2>{});            // x = xt + x        (model.py:50)
         }
-        if (a.acc_add != 0) add_rows(yg);                                   // xs += rb(x)       (model.py:118-120)
+        if (a.acc_add != 0) add_rows(yg, std::false_type{});                // xs += rb(x)       (model.py:118-120)
         VTTS_TL(a, wg_lin, 12);
         if constexpr (T::UP) {
             __syncthreads();  // every wave is done reading the xt tile: it becomes the fused upsampler's input tile
@@ -988,20 +1042,40 @@ constexpr int g_mfma_blk(int C, int KS) {
          : C == 64  ? (KS == 3 ? 32 : KS == 7 ? 16 : 16)
                     : 32;
 }
-template <int KS> using G128 = GTile<128, KS, KS == 3 ? VTTS_G128K3_N1 : 256, 2, 2, 3, KS == 3 ? VTTS_G128K3_WG : 2, 128, g_mfma_blk(128, KS)>;
-template <int KS> using G64 = GTile<64, KS, VTTS_G64_N1, 1, 4, 3, VTTS_G64_WG, 64, g_mfma_blk(64, KS)>;
+// What the 16-block loops do with the look-ahead slots past a pass's end (GTile's RS_), per class: bit 0 = c2's carry the residual rows, bit 1 = c1's
+// stay empty.  A bit is set only where the class, measured per launch as g_mfma_blk's entries were, gains more than three times the parent's spread
+// (profiles/res_slots_findings.md).  The arithmetic is the same either way, so a class's wide and narrow tiles need not agree; they share the entry.
+#ifndef VTTS_RES_SLOTS  // kernel-development switch (A/B builds): 0 .. 3 forces every 16-block class to that value, -1 = the table
+#define VTTS_RES_SLOTS -1
+#endif
+constexpr int g_res_slots(int C, int KS, bool up = false) {  // up: the tile under GUp (the stage-ending launch), an entry of its own
+    if (g_mfma_blk(C, KS) != 16) return 0;
+    if (VTTS_RES_SLOTS >= 0) return VTTS_RES_SLOTS;
+    if (up) return C == 128 ? 3 : 0;
+    return C == 256 ? (KS == 3 ? 1 : 0)
+         : C == 128 ? (KS == 3 ? 3 : KS == 7 ? 3 : 0)
+         : C == 64  ? (KS == 7 ? 3 : 0)
+                    : 0;
+}
+template <int KS> using G128 = GTile<128, KS, KS == 3 ? VTTS_G128K3_N1 : 256, 2, 2, 3, KS == 3 ? VTTS_G128K3_WG : 2, 128, g_mfma_blk(128, KS), g_res_slots(128, KS)>;
+template <int KS> using G64 = GTile<64, KS, VTTS_G64_N1, 1, 4, 3, VTTS_G64_WG, 64, g_mfma_blk(64, KS), g_res_slots(64, KS)>;
 #ifndef VTTS_G32_PA
 #define VTTS_G32_PA 3
 #endif
 template <int KS> using G32 = GTile<32, KS, VTTS_G32_N1, 1, 4, VTTS_G32_PA, VTTS_G32_WG>;
-template <int KS> using G256 = GTile<256, KS, 128, 4, 1, 3, 2, 128, g_mfma_blk(256, KS)>;
+template <int KS> using G256 = GTile<256, KS, 128, 4, 1, 3, 2, 128, g_mfma_blk(256, KS), g_res_slots(256, KS)>;
 // narrow tiles for SMALL launches (batch-1 latency: a 512-frame utterance is 35 wide tiles at C = 256, 134 at C = 128 — a
 // fraction of the 512 workgroup slots): half the time steps per workgroup, twice the workgroups.  Same per-element
 // accumulation order (the k loop), so the samples are bit-identical to the wide tiles'.
-template <int KS> using G256S = GTile<256, KS, 64, 4, 1, 3, 2, 128, g_mfma_blk(256, KS)>;
-template <int KS> using G128S = GTile<128, KS, 128, 2, 2, 3, 2, 128, g_mfma_blk(128, KS)>;
-template <int KS> using G64S = GTile<64, KS, 256, 1, 4, 3, 2, 64, g_mfma_blk(64, KS)>;
+template <int KS> using G256S = GTile<256, KS, 64, 4, 1, 3, 2, 128, g_mfma_blk(256, KS), g_res_slots(256, KS)>;
+template <int KS> using G128S = GTile<128, KS, 128, 2, 2, 3, 2, 128, g_mfma_blk(128, KS), g_res_slots(128, KS)>;
+template <int KS> using G64S = GTile<64, KS, 256, 1, 4, 3, 2, 64, g_mfma_blk(64, KS), g_res_slots(64, KS)>;
 template <int KS> using G32S = GTile<32, KS, 256, 1, 4, 3, 2>;
+// the k = 11 tiles under GUp
+using G128U = GTile<128, 11, 256, 2, 2, 3, 2, 128, g_mfma_blk(128, 11), g_res_slots(128, 11, true)>;
+using G128SU = GTile<128, 11, 128, 2, 2, 3, 2, 128, g_mfma_blk(128, 11), g_res_slots(128, 11, true)>;
+using G64U = GTile<64, 11, VTTS_G64_N1, 1, 4, 3, VTTS_G64_WG, 64, g_mfma_blk(64, 11), g_res_slots(64, 11, true)>;
+using G64SU = GTile<64, 11, 256, 1, 4, 3, 2, 64, g_mfma_blk(64, 11), g_res_slots(64, 11, true)>;
 constexpr long G_MIN_WGS = 384;  // below this many wide-tile workgroups (1.5 per CU slot pair) the narrow tile is launched
 template <class T>
 static hipError_t launch_g(const BConvArgs& a, hipStream_t s) {
@@ -1030,8 +1104,8 @@ hipError_t launch_pair_g_bf16(int C, int K, const BConvArgs& a, hipStream_t s) {
     auto narrow = [&](int nt2) { return a.tile_pref == 2 || (a.tile_pref != 1 && (long)((a.L + nt2 - 1) / nt2) * a.B < G_MIN_WGS); };
     if (a.up_y) {  // the next stage's transposed convolution rides on this launch (engine.hip: only where pair_up_bf16_supported); same width rule as the plain launch
         if (K != 11 || a.tail_wav) return hipErrorInvalidValue;
-        if (C == 128) return narrow(G128<11>::NT2) ? launch_g<GUp<G128S<11>>>(a, s) : launch_g<GUp<G128<11>>>(a, s);
-        if (C == 64) return narrow(G64<11>::NT2) ? launch_g<GUp<G64S<11>>>(a, s) : launch_g<GUp<G64<11>>>(a, s);
+        if (C == 128) return narrow(G128<11>::NT2) ? launch_g<GUp<G128SU>>(a, s) : launch_g<GUp<G128U>>(a, s);
+        if (C == 64) return narrow(G64<11>::NT2) ? launch_g<GUp<G64SU>>(a, s) : launch_g<GUp<G64U>>(a, s);
         return hipErrorInvalidValue;
     }
     switch (C) {
