@@ -74,6 +74,8 @@ SPECTRAL_LDS_BUDGET = 81920  # include/vtts_spectral.h: VTTS_SPECTRAL_LDS_BUDGET
 VTTS_STFT_CENTER, VTTS_STFT_MEL = 0, 1  # include/vtts_stft.h: the framings
 STFT_MAX_SAMPLES = 1 << 24  # include/vtts_stft.h: VTTS_STFT_MAX_SAMPLES
 STFT_NOLA_FLOOR = 1e-11  # include/vtts_stft.h: VTTS_STFT_NOLA_FLOOR
+DENOISE_MAX_SAMPLES = 1 << 24  # include/vtts_denoise.h: VTTS_DENOISE_MAX_SAMPLES
+DENOISE_NOLA_FLOOR = 1e-11  # include/vtts_denoise.h: VTTS_DENOISE_NOLA_FLOOR
 
 LIMITER_TILE = 4096  # include/vtts_limiter.h: VTTS_LIMITER_TILE
 LIMITER_RUN = 16  # include/vtts_limiter.h: VTTS_LIMITER_RUN
@@ -87,6 +89,7 @@ STOI_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stoi.hip
 LOUDNESS_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/loudness.hip
 SPECTRAL_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/spectral.hip; include/vtts_spectral.h: VTTS_SPECTRAL_ROWS_PER_LAUNCH
 STFT_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/stft.hip; include/vtts_stft.h: VTTS_STFT_ROWS_PER_LAUNCH
+DENOISE_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/denoise.hip; include/vtts_denoise.h: VTTS_DENOISE_ROWS_PER_LAUNCH
 DTW_PAIRS_PER_LAUNCH = 128  # viettts_amd/csrc/dtw.hip: PAIRS_PER_LAUNCH
 MCD_ROWS_PER_LAUNCH = 128  # viettts_amd/csrc/mcd.hip; include/vtts_mcd.h: VTTS_MCD_ROWS_PER_LAUNCH (its dtw() splits by DTW_PAIRS_PER_LAUNCH)
 LIMSTREAM_MAX_CHUNK = 1 << 20  # include/vtts_limstream.h: VTTS_LIMSTREAM_MAX_CHUNK
@@ -346,6 +349,18 @@ STFT_SIGS = {
 }
 
 
+# include/vtts_denoise.h, likewise (created from a StftCfg)
+DENOISE_SIGS = {
+    "vtts_denoise_create": (C.c_int, [C.POINTER(StftCfg), C.c_int, C.POINTER(vp)]),
+    "vtts_denoise_destroy": (None, [vp]),
+    "vtts_denoise_blocking": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vtts_denoise_packed_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "vtts_denoise_pack": (C.c_int, [vp, vp, sz, vp]),
+    "vtts_denoise_bind_packed": (C.c_int, [vp, vp, sz]),
+    "vtts_denoise_apply": (C.c_int, [vp, vp, C.c_int, C.c_int, i64, C.POINTER(C.c_int32), vp, C.c_float, vp, C.c_int, i64, vp]),
+}
+
+
 # include/vtts_limiter.h, likewise
 LIMITER_SIGS = {
     "vtts_limiter_create": (C.c_int, [C.POINTER(LimiterCfg), C.c_int, C.POINTER(vp)]),
@@ -403,6 +418,7 @@ LOUDNESS_EXPORTS = tuple(LOUDNESS_SIGS)  # include/vtts_loudness.h
 STOI_EXPORTS = tuple(STOI_SIGS)  # include/vtts_stoi.h
 SPECTRAL_EXPORTS = tuple(SPECTRAL_SIGS)  # include/vtts_spectral.h
 STFT_EXPORTS = tuple(STFT_SIGS)  # include/vtts_stft.h
+DENOISE_EXPORTS = tuple(DENOISE_SIGS)  # include/vtts_denoise.h
 LIMITER_EXPORTS = tuple(LIMITER_SIGS)  # include/vtts_limiter.h
 LIMSTREAM_EXPORTS = tuple(LIMSTREAM_SIGS)  # include/vtts_limstream.h
 RSSTREAM_EXPORTS = tuple(RSSTREAM_SIGS)  # include/vtts_rsstream.h
@@ -459,7 +475,7 @@ def load(path=None) -> C.CDLL:
         )
     _load_hip_runtime()
     lib = C.CDLL(str(p))
-    for name, (res, args) in {**SIGS, **DTW_SIGS, **MCD_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **STFT_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
+    for name, (res, args) in {**SIGS, **DTW_SIGS, **MCD_SIGS, **PITCH_SIGS, **LOUDNESS_SIGS, **STOI_SIGS, **SPECTRAL_SIGS, **STFT_SIGS, **DENOISE_SIGS, **LIMITER_SIGS, **LIMSTREAM_SIGS, **RSSTREAM_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

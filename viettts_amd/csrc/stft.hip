@@ -12,7 +12,8 @@
 //     2. after a workgroup barrier every thread adds the round's frames to its samples in ascending t (y += v w, e += w w, each rounded);
 //     3. a second barrier frees the buffers for the next round.
 //     At the end out = (y / e) / NFFT.  A sample's sums run over the same frames in the same order whichever workgroup owns it, so no result
-//     depends on RUN or W.  Reads of v for consecutive samples are consecutive LDS dwords (a pad dword pair after every 16).
+//     depends on RUN or W.  Reads of v for consecutive samples are consecutive LDS dwords (a pad dword pair after every 16).  The blocking, the
+//     inverse split step and the add-to-samples loop live in stft_back.h, shared with denoise.hip.
 //
 // Twiddles and window come from the packed blob (computed in double on the host, rounded once); there is no sin / cos and no atomic here.
 #include <hip/hip_runtime.h>
@@ -33,12 +34,14 @@
 // transform's bits are spectral.hip's, and a sample's sums must not depend on how the compiler schedules a workgroup's run).
 #pragma clang fp contract(off)
 
+#include "stft_back.h"
 #include "stft_front.h"
 #include "stft_host.h"
 #include "stockham.h"
 
 using vtts::failf;
 using namespace vtts_stft_front;
+using namespace vtts_stft_back;
 namespace sh = vtts_stft_host;
 
 namespace {
@@ -47,10 +50,6 @@ constexpr int ROWS_PER_LAUNCH = 128;
 static_assert(ROWS_PER_LAUNCH == VTTS_STFT_ROWS_PER_LAUNCH && ROWS_PER_LAUNCH == sh::ROWS, "the header states the split");
 constexpr int MAX_F = sh::MAX_F;
 constexpr int SIGNALS = 1, REDUCE = 0;  // of sh::frames_lds_bytes: one staged signal, nothing to reduce
-
-constexpr int inv_waves(int n_fft) { return n_fft == 2048 ? 4 : 8; }
-constexpr int inv_per_thread(int n_fft) { return n_fft == 256 ? 2 : n_fft == 512 ? 4 : n_fft == 1024 ? 8 : 16; }
-constexpr int inv_run(int n_fft) { return 64 * inv_waves(n_fft) * inv_per_thread(n_fft); }
 
 size_t inv_lds_bytes(int n_fft) {
     const int H = n_fft / 2;
@@ -150,9 +149,8 @@ __global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const Inv
     for (int i = tid; i < NFFT; i += NT) winl[i] = a.blob[i];
     // the frames whose window [hop t + lead, hop t + lead + win) meets the run's padded samples [p0, p1]
     const int p0 = g0 + a.P, p1 = min(g0 + RUN, S) - 1 + a.P;
-    const int below = p0 - (a.lead + a.win - 1);
-    const int t_lo = below <= 0 ? 0 : (below + a.hop - 1) / a.hop;
-    const int t_hi = min(T - 1, (p1 - a.lead) / a.hop);  // p1 >= P >= lead
+    int t_lo, t_hi;
+    covering_frames(p0, p1, T, a.hop, a.lead, a.win, t_lo, t_hi);  // p1 >= P >= lead
 
     float y[R], e[R];
 #pragma unroll
@@ -173,33 +171,13 @@ __global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const Inv
 #pragma unroll
             for (int j = 0; j < J; ++j) {
                 const int k = lane + 64 * j;
-                if (k <= H / 2) {
-                    if (k == 0) xk[j].y = 0.0f, xn[j].y = 0.0f;  // the imaginary parts of bins 0 and H are no part of the signal
-                    const float2 A = make_float2(xk[j].x + xn[j].x, xk[j].y - xn[j].y);
-                    const float2 D = make_float2(xk[j].x - xn[j].x, xk[j].y + xn[j].y);
-                    const float2 B = cmul(conj(twN[k]), D);
-                    xb[pad8(k)] = make_float2(A.x - B.y, A.y + B.x);
-                    if (k != 0 && k != H / 2) xb[pad8(H - k)] = make_float2(A.x + B.y, B.x - A.y);
-                }
+                if (k <= H / 2) put_bin_pair<H>(xb, twN, k, xk[j], xn[j]);
             }
             wave_sync();
             transform<H, true>(xb, twH, lane, FromBuffer{xb});
         }
         __syncthreads();
-        const int n = min(W, t_hi - tb + 1);
-        for (int u = 0; u < n; ++u) {
-            const float* v = reinterpret_cast<const float*>(xall + u * XB);
-            const int base = p0 + tid - a.hop * (tb + u);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int o = base + NT * r;
-                if (o >= a.lead && o < a.lead + a.win) {
-                    const float w = winl[o];
-                    y[r] += v[2 * pad8(o >> 1) + (o & 1)] * w;
-                    e[r] += w * w;
-                }
-            }
-        }
+        add_round<R, NT, XB>(y, e, xall, winl, p0, tid, a.hop, tb, min(W, t_hi - tb + 1), a.lead, a.win);
         __syncthreads();
     }
     TO* out = static_cast<TO*>(a.out) + (long long)b * a.s_stride;

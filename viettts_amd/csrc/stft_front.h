@@ -1,4 +1,5 @@
-// The front of the forward short-time transform, stated once for spectral.hip's meter and stft.hip's forward and projection kernels: a
+// The front of the forward short-time transform, stated once for spectral.hip's meter and stft.hip's forward and projection kernels (denoise.hip's
+// fused pass runs its transform_frame-like first pass straight from global memory, and its gather_bins and split_bins): a
 // workgroup of F waves stages the samples its F consecutive frames cover, reflected at the row's own ends; each wave then runs its windowed
 // frame, as H = NFFT / 2 complex points z[n] = v[2n] + i v[2n+1], through stockham.h's forward transform in its own exchange buffer and
 // splits the result into bins 0 .. H, a lane pairing bin k with bin H - k.  What becomes of the bins is the caller's.
@@ -36,16 +37,17 @@ __device__ __forceinline__ void stage_twiddles(float2* twH, float2* twN, const f
     for (int i = tid; i < H + H / 2 + 1; i += nthreads) (i < H ? twH[i] : twN[i - H]) = t2[i];
 }
 
+// row sample g of a row of S samples, reflected at the row's ends
+__device__ __forceinline__ long long reflect_index(long long g, long long S) {
+    if (g < 0) g = -g;
+    if (g >= S) g = 2 * (S - 1) - g;
+    return g < 0 ? 0 : g >= S ? S - 1 : g;  // frames past the row's last (never used) stay inside the row
+}
+
 // dst[i] = row sample g0 + i, i < n, reflected at the row's ends (S samples), PCM16 scaled by 2^-15 on the way; by the whole workgroup
 template <typename TI>
 __device__ __forceinline__ void stage_reflected(float* dst, const TI* x, long long S, long long g0, int n, int tid, int nthreads) {
-    for (int i = tid; i < n; i += nthreads) {
-        long long g = g0 + i;
-        if (g < 0) g = -g;
-        if (g >= S) g = 2 * (S - 1) - g;
-        g = g < 0 ? 0 : g >= S ? S - 1 : g;  // frames past the row's last (never used) stay inside the row
-        dst[i] = vtts_sample::to_float_exact_shift(x[g]);
-    }
+    for (int i = tid; i < n; i += nthreads) dst[i] = vtts_sample::to_float_exact_shift(x[reflect_index(g0 + i, S)]);
 }
 
 // the transform of the frame that starts at fr[0], times the window; Z lies in xb in natural order

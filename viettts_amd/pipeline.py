@@ -84,7 +84,7 @@ def _copy_stream(device: torch.device):
 def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, acoustic_model, generator, silence_duration: float = -1.0,
                          dropout_seed: Optional[int] = 0, rank: int = 0, world: int = 1, gen_batch: int = 0,
                          timing: Optional[dict] = None, out_dtype: str = "f32", out_rate: Optional[int] = None,
-                         loudness: Optional[float] = None, limit: bool = False) -> Dict[int, np.ndarray]:
+                         loudness: Optional[float] = None, limit: bool = False, denoise: Optional[float] = None) -> Dict[int, np.ndarray]:
     """Waveforms (float32, 16 kHz samples) of THIS rank's sentences, keyed by sentence index.  ``out_dtype="pcm16"`` returns int16
     arrays equal to ``wavio.float_to_pcm16`` of the default's, and ``out_rate`` samples at that rate: each pass is then converted
     (``viettts_amd.audio.Resampler``) and packed on the device, and only the packed samples are read back.  ``loudness`` (a target in LUFS;
@@ -112,6 +112,10 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
         raise ValueError(f"out_dtype must be 'f32' or 'pcm16', got {out_dtype!r}")
     if limit and loudness is None:
         raise ValueError("limit=True needs a loudness target")
+    if denoise is not None:
+        from .denoise import check_strength
+
+        denoise = check_strength(denoise)
     convert = out_dtype != "f32" or (out_rate is not None and int(out_rate) != t2m.FLAGS.sample_rate)
     mine = shard_utterances([len(t) for t in token_lists], world)[rank]
     if not mine:
@@ -184,6 +188,10 @@ def synthesize_sentences(token_lists: Sequence[Sequence[int]], duration_model, a
                 batch = torch.nn.functional.pad(batch, (0, 0, 0, Ts - batch.shape[1]))
             batch = batch.contiguous()
             w = generator.forward_ragged(batch, fr) if ragged else generator(batch)
+            if denoise is not None:  # the generator's own bias out of its output, ahead of every other stage
+                from .denoise import generator_denoiser
+
+                w = generator_denoiser(generator)(w, lengths=[generator.hop * f for f in fr], strength=denoise)
             if loudness is not None and limit:  # the gain to the target, and the limiter under -1 dBTP, on the device
                 from .limiter import default_limiter
 

@@ -4,6 +4,8 @@ computed on).  The mel stays in HBM between the two kernels' worlds: ``MelFilter
 
     python -m viettts_amd.resynth --input in.wav --output out.wav [--dtype f32|bf16|bf16x3] [--output-rate 48000] [--f0] [--loudness -23 [--limit]] [--stoi] [--mrstft] [--mcd]
     python -m viettts_amd.resynth --input in.wav --output out.wav --vocoder griffinlim      # no checkpoint at all: viettts_amd.stft
+    python -m viettts_amd.resynth --input in.wav --output out.wav --denoise 0.01            # the vocoder's own bias out of the result: viettts_amd.denoise
+    python -m viettts_amd.resynth --input in.wav --output out.wav --denoise 1.0 --noise-from 0:0.5   # the input's room tone out of the input
 
 reads PCM16 mono at any rate (anything but the model's 16 kHz is converted on the GPU first: ``viettts_amd.audio.Resampler``), writes
 at the model's rate or, converted again, at ``--output-rate``; uses the same ``assets/hifigan/config.json`` and ``hk_hifi.pickle`` as ``mel2wave`` and raises
@@ -101,6 +103,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mcd", action="store_true", help="also print the mel-cepstral distortion in dB of the result against the input, frame by frame (viettts_amd.mcd: 13 log-mel cepstra, c0 left out)")
     ap.add_argument("--vocoder", default="hifigan", choices=("hifigan", "griffinlim"), help="griffinlim: log-mel -> wav by Griffin-Lim on the GPU (viettts_amd.stft): "
                     "no checkpoint is opened; --dtype does not apply")
+    ap.add_argument("--denoise", type=float, default=None, metavar="S", help="subtract S x a bias spectrum (viettts_amd.denoise): the vocoder's own, from its output "
+                    "for an empty mel, out of the result; or with --noise-from the input's room tone out of the input, ahead of the mel front end")
+    ap.add_argument("--noise-from", default=None, metavar="A:B", help="with --denoise: seconds A..B of the input hold room tone only, the bias is their mean magnitude spectrum")
     return ap
 
 
@@ -116,6 +121,25 @@ def main(argv=None) -> None:
     a = ap.parse_args(argv)
     if a.limit and a.loudness is None:
         raise SystemExit("--limit needs --loudness")
+    span = None
+    if a.noise_from is not None and a.denoise is None:
+        ap.error("--noise-from belongs to --denoise S")
+    if a.denoise is not None:  # argument errors before anything touches a device
+        from .denoise import check_strength, noise_span, parse_noise_from
+
+        try:
+            check_strength(a.denoise)
+            span = None if a.noise_from is None else parse_noise_from(a.noise_from)
+        except ValueError as e:
+            ap.error(str(e).replace("strength", "--denoise"))
+        if span is None and a.vocoder == "griffinlim":
+            ap.error("--vocoder griffinlim with --denoise and no --noise-from: there is no vocoder to take a bias from")
+        if span is not None:
+            try:
+                sr0, pcm0 = wavio.read_wav(a.input)  # (host work: the stretch has to lie inside the input)
+                noise_span(span, len(pcm0), sr0)
+            except ValueError as e:
+                ap.error(str(e))
     if a.vocoder == "griffinlim":
         if a.dtype != "f32":
             ap.error("--vocoder griffinlim with --dtype: the engine's precision belongs to the HiFi-GAN generator")
@@ -133,12 +157,24 @@ def main(argv=None) -> None:
         from .audio import resampler
 
         y = resampler(sr, model_rate, gen.device)(y)
+    if span is not None:  # the input's room tone out of the input
+        from .denoise import DEFAULT_CFG, Denoiser
+
+        dn = Denoiser(DEFAULT_CFG, device=gen.device)
+        lo, hi = (int(round(t * model_rate)) for t in span)
+        dn.bias_from_noise(y[:, lo:min(hi, y.shape[1])].contiguous())
+        y = dn(y, strength=a.denoise, out_dtype="pcm16" if y.dtype == torch.int16 else "f32")
+        dn.close()
     if a.vocoder == "griffinlim":
         from .stft import mel2wave_griffinlim
 
         wav = mel2wave_griffinlim(wav2mel(y, device=gen.device))
     else:
         wav = resynthesize(y, gen)
+        if a.denoise is not None and span is None:  # the vocoder's own bias out of its output
+            from .denoise import generator_denoiser
+
+            wav = generator_denoiser(gen)(wav, lengths=[256 * (y.shape[1] // 256)], strength=a.denoise)
     n = 256 * (y.shape[1] // 256)
     written = wav
     if a.loudness is not None and a.limit:

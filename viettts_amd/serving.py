@@ -129,7 +129,10 @@ class SpeechPool:
 
     def __init__(self, duration_model, acoustic_model, generator, slots: int, Lmax: int, Fmax: int, chunk_frames: int = 32,
                  first_chunk_frames: Optional[int] = None, out_dtype: str = "pcm16", limit: bool = False, gain_db: float = 0.0,
-                 ceiling_dbtp: float = -1.0, out_rate: Optional[int] = None):
+                 ceiling_dbtp: float = -1.0, out_rate: Optional[int] = None, denoise: Optional[float] = None):
+        if denoise is not None:
+            raise ValueError("SpeechPool with denoise: a streamed denoiser needs per-row overlap-add state between chunks, which viettts_amd.denoise "
+                             "does not keep; denoise whole sentences with synthesize_sentences(..., denoise=S)")
         _check_dtype(out_dtype)
         self.dm, self.am, self.gen, self.out_dtype = duration_model, acoustic_model, generator, out_dtype
         self.planner = RoundPlanner(slots, chunk_frames, first_chunk_frames)

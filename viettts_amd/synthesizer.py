@@ -11,7 +11,9 @@ mel->waveform path can be driven on its own (the text path runs the NAT duration
 writes the output chunk by chunk while the acoustic decoder is still running (``viettts_amd.streaming``): the WAV header first — the sample count
 is known before the first decoder frame — then PCM16 per chunk of ``--chunk-frames`` mel frames, flushed; ``--output -`` writes the raw PCM16 to
 stdout (the two printed lines go to stderr then); ``--stream --output-rate R`` converts the streamed samples to R chunk by chunk
-(``viettts_amd.audio.ResamplerStream``), the header carrying R and the converted count.
+(``viettts_amd.audio.ResamplerStream``), the header carrying R and the converted count; ``--denoise S`` subtracts S times the vocoder's own bias
+spectrum (its output for an empty mel) from the clip directly behind the generator (``viettts_amd.denoise``), not with ``--stream`` and not with
+``--vocoder griffinlim``.
 
     python -m viettts_amd.synthesizer --text "..." --output clip.wav --lexicon-file assets/infore/lexicon.txt
 """
@@ -66,6 +68,8 @@ def build_parser() -> ArgumentParser:
                    "(viettts_amd.audio.ResamplerStream); the header carries it")
     p.add_argument("--vocoder", default="hifigan", choices=("hifigan", "griffinlim"), help="(extension) griffinlim: mel -> wav by Griffin-Lim on the GPU "
                    "(viettts_amd.stft) with the NAT checkpoints only; the HiFi-GAN checkpoint is not opened")
+    p.add_argument("--denoise", default=None, type=float, metavar="S", help="(extension) subtract S x the vocoder's own bias spectrum (its output for an empty "
+                   "mel) from the clip, directly behind the generator (viettts_amd.denoise); the published scripts' --denoising-strength")
     return p
 
 
@@ -136,6 +140,13 @@ def main(argv=None) -> int:
         if args.sample_rate != FLAGS.sample_rate:
             parser.error(f"--output-rate with --sample-rate {args.sample_rate}: the streamed samples are the models' {FLAGS.sample_rate} Hz and --output-rate "
                          "converts them; leave --sample-rate alone")
+    if args.denoise is not None:  # argument errors before anything touches a device
+        if not (args.denoise >= 0.0 and args.denoise != float("inf")):
+            parser.error("--denoise must be finite and not negative")
+        if args.stream:
+            parser.error("--stream with --denoise: a streamed denoiser needs per-row overlap-add state between chunks; there is none yet")
+        if args.vocoder == "griffinlim":
+            parser.error("--vocoder griffinlim with --denoise: there is no vocoder to take a bias from")
     if args.stream:  # argument errors before anything touches a device
         if args.vocoder == "griffinlim":
             parser.error("--stream with --vocoder griffinlim: Griffin-Lim iterates over the whole clip; there is no streamed inverse transform")
@@ -174,6 +185,11 @@ def main(argv=None) -> int:
         from .hifigan.mel2wave import mel2wave
 
         wave = mel2wave(mel)
+        if args.denoise is not None:
+            from .denoise import generator_denoiser
+            from .hifigan.mel2wave import _generator
+
+            wave = np.squeeze(generator_denoiser(_generator())(np.asarray(wave, dtype=np.float32).reshape(1, -1), strength=args.denoise).cpu().numpy())
     if args.loudness is not None and args.limit:
         from .limiter import default_limiter
 
