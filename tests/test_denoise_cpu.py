@@ -45,7 +45,7 @@ def test_header_exports_and_constants(lib):
     assert float(k["VTTS_DENOISE_NOLA_FLOOR"]) == _lib.DENOISE_NOLA_FLOOR == float(ks["VTTS_STFT_NOLA_FLOOR"])
     text = (REPO / "viettts_amd" / "csrc" / "denoise.hip").read_text()
     assert re.findall(r"^constexpr int (ROWS_PER_LAUNCH) = (\d+);", text, flags=re.M) == [("ROWS_PER_LAUNCH", str(_lib.DENOISE_ROWS_PER_LAUNCH))]
-    assert len(re.findall(r"\+= ROWS_PER_LAUNCH\)", text)) == 1
+    assert len(re.findall(r"for_each_launch(?:_off)?<ROWS_PER_LAUNCH>\(", text)) == 1 and len(re.findall(r"\+= ROWS_PER_LAUNCH\)", text)) == 0
     assert "#pragma clang fp contract(off)" in text and text.index("#pragma clang fp contract(off)") < text.index('#include "stockham.h"')
     assert not re.search(r"atomic(Add|Max|Min|CAS|Exch)|__hip_atomic", text) and not re.search(r"\b(sinf?|cosf?|sincosf?)\s*\(", text)
     for word in ("contract", "blocking", "LDS", "bit for bit"):  # the header states the contract, the blocking and the LDS formula

@@ -252,7 +252,8 @@ def test_rows_behind_the_launch_split(mcds):
     PD = _split_constant("dtw_common.h", r"^constexpr int DTW_PAIRS_PER_LAUNCH = (\d+);")
     assert P == _lib.MCD_ROWS_PER_LAUNCH == KM["VTTS_MCD_ROWS_PER_LAUNCH"] and PD == _lib.DTW_PAIRS_PER_LAUNCH
     src = (CSRC / "mcd.hip").read_text()
-    assert len(re.findall(r"\+= ROWS_PER_LAUNCH\)", src)) == 2 and len(re.findall(r"\+= vtts::DTW_PAIRS_PER_LAUNCH\)", src)) == 1
+    assert len(re.findall(r"for_each_launch(?:_off)?<ROWS_PER_LAUNCH>\(", src)) == 2 and len(re.findall(r"\+= vtts::DTW_PAIRS_PER_LAUNCH\)", src)) == 1
+    assert len(re.findall(r"\+= ROWS_PER_LAUNCH\)", src)) == 0  # launch_rows.h's loop, and no hand-written one
     M, Kc, St = 8, 4, F + 6
     m = mcds(M, Kc)
     table = _table(M, Kc)

@@ -76,7 +76,8 @@ def test_header_exports_and_constants(lib):
     assert k["VTTS_SPECTRAL_LDS_BUDGET"] == _lib.SPECTRAL_LDS_BUDGET == 80 * 1024  # two workgroups in a CU's 160 KB
     text = (REPO / "viettts_amd" / "csrc" / "spectral.hip").read_text()
     found = re.findall(r"^constexpr int (ROWS_PER_LAUNCH) = (\d+);", text, flags=re.M)
-    assert found == [("ROWS_PER_LAUNCH", str(_lib.SPECTRAL_ROWS_PER_LAUNCH))] and len(re.findall(r"\+= ROWS_PER_LAUNCH\)", text)) >= 1
+    assert found == [("ROWS_PER_LAUNCH", str(_lib.SPECTRAL_ROWS_PER_LAUNCH))] and len(re.findall(r"for_each_launch(?:_off)?<ROWS_PER_LAUNCH>\(", text)) >= 1
+    assert len(re.findall(r"\+= ROWS_PER_LAUNCH\)", text)) == 0  # launch_rows.h's loop, and no hand-written one
     from viettts_amd.csrc import build
 
     assert "spectral.hip" in build.SOURCES and any(str(h).endswith("vtts_spectral.h") for h in build.HEADERS)

@@ -30,6 +30,7 @@
 #include "../../include/vtts_hifigan.h"
 #include "audio_common.h"
 #include "audio_design.h"
+#include "launch_rows.h"
 #include "vtts_internal.h"
 
 using vtts::check_blob;
@@ -48,10 +49,7 @@ constexpr int OPB = VTTS_AUDIO_OUT_PER_BLOCK;
 constexpr int THREADS = 256;
 constexpr int ROWS_PER_LAUNCH = 128;
 
-struct AudioRows {
-    long long off[ROWS_PER_LAUNCH];  // first output element of each row of this launch, from a.out
-    int len[ROWS_PER_LAUNCH];        // input samples of each row of this launch
-};
+using AudioRows = vtts_rows::OffLens<ROWS_PER_LAUNCH>;  // input samples and first output element (from a.out) of each row of this launch
 
 struct AudioArgs {
     const void* in;      // first row of this launch
@@ -232,13 +230,9 @@ VTTS_API int vtts_audio_forward(vtts_audio* h, const void* in_dev, int in_dtype,
     a.identity = d.identity ? 1 : 0;
     const size_t lds = d.identity ? 0 : (size_t)d.span_floats * sizeof(float);
     const unsigned tiles = (unsigned)((plan.cover + OPB - 1) / OPB);
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths and offsets travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        AudioRows rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) {
-            rows.len[b] = b < nr ? plan.len[r0 + b] : 0;
-            rows.off[b] = b < nr ? plan.off[r0 + b] : 0;
-        }
+    // the rows' lengths and offsets travel as kernel arguments: plan_rows() has checked them, a row of len samples writes out_samples(d, len)
+    const auto count = [&](int len) { return (long long)ad::out_samples(d, len); };
+    return vtts_rows::for_each_launch_off<ROWS_PER_LAUNCH>(N, lengths, S_stride, O_stride, count, [&](int r0, int nr, const AudioRows& rows) -> int {
         a.in = static_cast<const char*>(in_dev) + (size_t)r0 * S_stride * esz;
         const dim3 grid(tiles, (unsigned)nr);
         hipError_t e;
@@ -247,6 +241,6 @@ VTTS_API int vtts_audio_forward(vtts_audio* h, const void* in_dev, int in_dtype,
         else
             e = pout ? launch<float, short>(a, rows, grid, lds, s, h->lds[1]) : launch<float, float>(a, rows, grid, lds, s, h->lds[0]);
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "audio kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

@@ -20,7 +20,7 @@ ROOT = CSRC.parents[1]
 LIBDIR = CSRC.parent / "lib"
 OBJDIR = CSRC / "build"
 SOURCES = ["engine.hip", "kernels_generic.hip", "kernels_f32_mfma.hip", "kernels_f32_pair.hip", "kernels_x3.hip", "kernels_x3_rb.hip", "kernels_bf16.hip", "kernels_bf16_rbg.hip", "kernels_bf16_rbk.hip", "kernels_bf16_up.hip", "nat.hip", "nat_resident.hip", "mel.hip", "disc.hip", "audio.hip", "dtw.hip", "mcd.hip", "pitch.hip", "loudness.hip", "stoi.hip", "spectral.hip", "stft.hip", "denoise.hip", "limiter.hip", "limiter_stream.hip", "resample_stream.hip"]
-HEADERS = ["vtts_internal.h", "device_common.h", "bf16_common.h", "x3_common.h", "nat_model.h", "audio_design.h", "loudness_design.h", "limiter_common.h", "limstream_host.h", "audio_common.h", "rsstream_host.h", "sample_convert.h", "stream_rows_host.h", "stockham.h", "wave_common.h", "stft_front.h", "stft_back.h", "stft_host.h", "dtw_common.h", str(ROOT / "include" / "vtts_hifigan.h"), str(ROOT / "include" / "vtts_nat.h"), str(ROOT / "include" / "vtts_mel.h"), str(ROOT / "include" / "vtts_disc.h"), str(ROOT / "include" / "vtts_audio.h"), str(ROOT / "include" / "vtts_dtw.h"), str(ROOT / "include" / "vtts_mcd.h"), str(ROOT / "include" / "vtts_pitch.h"), str(ROOT / "include" / "vtts_loudness.h"), str(ROOT / "include" / "vtts_stoi.h"), str(ROOT / "include" / "vtts_spectral.h"), str(ROOT / "include" / "vtts_stft.h"), str(ROOT / "include" / "vtts_denoise.h"), str(ROOT / "include" / "vtts_limiter.h"), str(ROOT / "include" / "vtts_limstream.h"), str(ROOT / "include" / "vtts_rsstream.h")]
+HEADERS = ["vtts_internal.h", "device_common.h", "bf16_common.h", "x3_common.h", "nat_model.h", "audio_design.h", "loudness_design.h", "limiter_common.h", "limstream_host.h", "audio_common.h", "rsstream_host.h", "sample_convert.h", "stream_rows_host.h", "stockham.h", "wave_common.h", "stft_front.h", "stft_back.h", "stft_host.h", "dtw_common.h", "launch_rows.h", "mel_framing.h", str(ROOT / "include" / "vtts_hifigan.h"), str(ROOT / "include" / "vtts_nat.h"), str(ROOT / "include" / "vtts_mel.h"), str(ROOT / "include" / "vtts_disc.h"), str(ROOT / "include" / "vtts_audio.h"), str(ROOT / "include" / "vtts_dtw.h"), str(ROOT / "include" / "vtts_mcd.h"), str(ROOT / "include" / "vtts_pitch.h"), str(ROOT / "include" / "vtts_loudness.h"), str(ROOT / "include" / "vtts_stoi.h"), str(ROOT / "include" / "vtts_spectral.h"), str(ROOT / "include" / "vtts_stft.h"), str(ROOT / "include" / "vtts_denoise.h"), str(ROOT / "include" / "vtts_limiter.h"), str(ROOT / "include" / "vtts_limstream.h"), str(ROOT / "include" / "vtts_rsstream.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # No kernel of this library may contain packed-f32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32); hipcc's SLP vectoriser is
 # what forms them, so every device file is built with -fno-slp-vectorize.  Two reasons, both measured on MI355X:

@@ -21,6 +21,7 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_spectral.h"
 #include "../../include/vtts_stft.h"
+#include "launch_rows.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
 
@@ -40,7 +41,8 @@ namespace sh = vtts_stft_host;
 namespace {
 
 constexpr int ROWS_PER_LAUNCH = 128;
-static_assert(ROWS_PER_LAUNCH == VTTS_DENOISE_ROWS_PER_LAUNCH && ROWS_PER_LAUNCH == sh::ROWS, "the header states the split");
+static_assert(ROWS_PER_LAUNCH == VTTS_DENOISE_ROWS_PER_LAUNCH, "the header states the split");
+using Rows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // samples of each row of this launch
 static_assert(VTTS_DENOISE_MAX_SAMPLES == VTTS_STFT_MAX_SAMPLES, "the rows are vtts_stft.h's");
 
 // the header's table: tables, window, strength x bias, W exchange buffers
@@ -69,7 +71,7 @@ __device__ __forceinline__ float2 subtract(float2 c, float sb) {
 }
 
 template <int NFFT, typename TI, typename TO>
-__global__ __launch_bounds__(64 * inv_waves(NFFT)) void denoise_k(const Args a, const sh::Rows rows) {
+__global__ __launch_bounds__(64 * inv_waves(NFFT)) void denoise_k(const Args a, const Rows rows) {
     constexpr int H = NFFT / 2, XB = pad8(H), W = inv_waves(NFFT), R = inv_per_thread(NFFT), NT = 64 * W, RUN = NT * R;
     extern __shared__ float2 lds2[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(64 * inv_waves(NFFT)) void denoise_k(const Args a, 
 }
 
 template <int NFFT, typename TI, typename TO>
-hipError_t launch_one(dim3 grid, hipStream_t s, const Args& a, const sh::Rows& rows, vtts::DynLdsOnce& once) {
+hipError_t launch_one(dim3 grid, hipStream_t s, const Args& a, const Rows& rows, vtts::DynLdsOnce& once) {
     const hipError_t e = vtts::set_max_dynamic_lds(reinterpret_cast<const void*>(&denoise_k<NFFT, TI, TO>), VTTS_SPECTRAL_LDS_BUDGET, once);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((denoise_k<NFFT, TI, TO>), grid, dim3(64 * inv_waves(NFFT)), lds_bytes(NFFT), s, a, rows);
@@ -152,7 +154,7 @@ hipError_t launch_one(dim3 grid, hipStream_t s, const Args& a, const sh::Rows& r
 }
 
 template <int NFFT>
-hipError_t launch(bool pcm_in, bool pcm_out, dim3 grid, hipStream_t s, const Args& a, const sh::Rows& rows, vtts::DynLdsOnce* once) {
+hipError_t launch(bool pcm_in, bool pcm_out, dim3 grid, hipStream_t s, const Args& a, const Rows& rows, vtts::DynLdsOnce* once) {
     vtts::DynLdsOnce& o = once[2 * pcm_in + pcm_out];
     if (pcm_in) return pcm_out ? launch_one<NFFT, short, short>(grid, s, a, rows, o) : launch_one<NFFT, short, float>(grid, s, a, rows, o);
     return pcm_out ? launch_one<NFFT, float, short>(grid, s, a, rows, o) : launch_one<NFFT, float, float>(grid, s, a, rows, o);
@@ -249,9 +251,7 @@ VTTS_API int vtts_denoise_apply(vtts_denoise* h, const void* wav_dev, int in_dty
     const int n_fft = h->cfg.n_fft, run = inv_run(n_fft);
     const int64_t gmax = (longest + run - 1) / run;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        const sh::Rows rows = sh::launch_rows(lengths, r0, nr, S_stride);
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         Args a;
         a.x = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * isz;
         a.blob = h->blob;
@@ -264,6 +264,6 @@ VTTS_API int vtts_denoise_apply(vtts_denoise* h, const void* wav_dev, int in_dty
         const dim3 grid((unsigned)gmax, (unsigned)nr);
         const hipError_t e = sh::by_nfft(n_fft, [&](auto n) { return launch<decltype(n)::value>(pcm_in, pcm_out, grid, s, a, rows, h->lds_once); });
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "denoise kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

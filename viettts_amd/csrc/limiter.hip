@@ -25,6 +25,7 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_limiter.h"
+#include "launch_rows.h"
 #include "limiter_common.h"
 #include "vtts_internal.h"
 
@@ -38,14 +39,8 @@ constexpr int ROWS_PER_LAUNCH = 128;
 constexpr int SPAN = TILE + KP + 4;   // staged samples of a tile: x[t0 - LEAD .. t0 + TILE + 28]
 constexpr int MAX_APPLY_LDS = 2 * gain_buf_floats(MAX_W) * (int)sizeof(float);  // lim_apply_k's two gain buffers
 
-struct LimLens {
-    int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
-};
-
-struct LimRows {
-    long long off[ROWS_PER_LAUNCH];  // first output element of each row of this launch, from the call's out
-    int len[ROWS_PER_LAUNCH];
-};
+using LimLens = vtts_rows::Lens<ROWS_PER_LAUNCH>;     // samples of each row of this launch
+using LimRows = vtts_rows::OffLens<ROWS_PER_LAUNCH>;  // ... and each row's first output element, from the call's out
 
 struct EnvArgs {
     const void* wav;     // first row of this launch, as every pointer below
@@ -270,10 +265,7 @@ int run_envelope(vtts_limiter* h, const void* wav_dev, int dtype, int N, int64_t
     const size_t esz = pcm ? 2 : 4;
     const int64_t cover = envelope_dev ? S_stride : longest;
     const unsigned tiles = (unsigned)((cover + TILE - 1) / TILE);
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        LimLens rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const LimLens& rows) -> int {
         EnvArgs a;
         a.wav = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.s_stride = S_stride;
@@ -298,8 +290,8 @@ int run_envelope(vtts_limiter* h, const void* wav_dev, int dtype, int N, int64_t
         hipLaunchKernelGGL((lim_reduce_k<false>), dim3((unsigned)nr), dim3(64), 0, s, r, rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "limiter kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }
 
 template <typename TI, typename TO>
@@ -396,17 +388,7 @@ VTTS_API int vtts_limiter_apply(vtts_limiter* h, const void* wav_dev, int dtype,
     const size_t esz = pin ? 2 : 4;
     const int64_t cover = O_stride ? O_stride : longest;
     const unsigned tiles = (unsigned)((cover + TILE - 1) / TILE);
-    long long packed = 0;
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        LimRows rows;
-        LimLens lens;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) {
-            const int len = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
-            rows.len[b] = lens.len[b] = len;
-            rows.off[b] = O_stride ? (long long)(r0 + b) * O_stride : packed;
-            packed += len;
-        }
+    return vtts_rows::for_each_launch_off<ROWS_PER_LAUNCH>(N, lengths, S_stride, O_stride, [&](int r0, int nr, const LimRows& rows) -> int {
         ApplyArgs a;
         a.wav = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.out = out_dev;
@@ -436,9 +418,11 @@ VTTS_API int vtts_limiter_apply(vtts_limiter* h, const void* wav_dev, int dtype,
         r.result = min_gain_dev + r0;
         r.gains = nullptr;
         r.gains_used = nullptr;
+        LimLens lens;  // lim_reduce_k takes the lengths alone
+        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) lens.len[b] = rows.len[b];
         hipLaunchKernelGGL((lim_reduce_k<true>), dim3((unsigned)nr), dim3(64), 0, s, r, lens);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "limiter kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

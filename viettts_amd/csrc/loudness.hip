@@ -29,6 +29,7 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_loudness.h"
+#include "launch_rows.h"
 #include "loudness_design.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
@@ -53,14 +54,8 @@ constexpr int ROWS_PER_LAUNCH = 128;
 constexpr int APPLY_TILE = 4096;
 static_assert(THREADS == WAVES * 64 && THREADS * CHUNK == SEGMENT, "one lane per chunk");
 
-struct LoudLens {
-    int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
-};
-
-struct LoudRows {  // normalise
-    long long off[ROWS_PER_LAUNCH];  // first output element of each row of this launch, from the call's out
-    int len[ROWS_PER_LAUNCH];
-};
+using LoudLens = vtts_rows::Lens<ROWS_PER_LAUNCH>;     // samples of each row of this launch
+using LoudRows = vtts_rows::OffLens<ROWS_PER_LAUNCH>;  // normalise: and each row's first output element, from the call's out
 
 struct ScanArgs {
     const void* wav;      // first row of this launch
@@ -406,10 +401,7 @@ VTTS_API int vtts_loudness_measure(vtts_loudness* h, const void* wav_dev, int dt
     const size_t esz = pcm ? 2 : 4;
     char* ws = static_cast<char*>(workspace);
     const unsigned nseg = (unsigned)ld::num_segments(longest);
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        LoudLens rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const LoudLens& rows) -> int {
         ScanArgs a;
         a.wav = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.s_stride = S_stride;
@@ -449,8 +441,8 @@ VTTS_API int vtts_loudness_measure(vtts_loudness* h, const void* wav_dev, int dt
         hipLaunchKernelGGL(loud_gate_k, dim3((unsigned)nr), dim3(64), 0, s, g, rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "loudness kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }
 
 VTTS_API int vtts_loudness_normalize(vtts_loudness* h, const void* wav_dev, int dtype, int N, int64_t S_stride, const int32_t* lengths,
@@ -473,17 +465,8 @@ VTTS_API int vtts_loudness_normalize(vtts_loudness* h, const void* wav_dev, int 
     const size_t esz = pin ? 2 : 4;
     const int64_t cover = O_stride ? O_stride : longest;
     const unsigned tiles = (unsigned)((cover + APPLY_TILE - 1) / APPLY_TILE);
-    long long packed = 0;
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        LoudRows rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) {
-            const int len = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
-            rows.len[b] = len;
-            rows.off[b] = O_stride ? (long long)(r0 + b) * O_stride : packed;
-            packed += len;
-        }
-        if (tiles == 0) continue;
+    vtts_rows::for_each_launch_off<ROWS_PER_LAUNCH>(N, lengths, S_stride, O_stride, [&](int r0, int nr, const LoudRows& rows) -> int {
+        if (tiles == 0) return VTTS_OK;  // packed, and every row is empty
         ApplyArgs a;
         a.wav = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.out = out_dev;
@@ -502,7 +485,8 @@ VTTS_API int vtts_loudness_normalize(vtts_loudness* h, const void* wav_dev, int 
             else
                 hipLaunchKernelGGL((loud_apply_k<float, float>), grid, dim3(THREADS), 0, s, a, rows);
         }
-    }
+        return VTTS_OK;
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return failf(VTTS_ERR_HIP, "loudness kernel launch failed: %s", hipGetErrorString(e));
     return VTTS_OK;

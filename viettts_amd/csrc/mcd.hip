@@ -20,6 +20,7 @@
 
 #include "../../include/vtts_mcd.h"
 #include "dtw_common.h"
+#include "launch_rows.h"
 
 using vtts::DtwArgs;
 using vtts::DtwPairs;
@@ -37,9 +38,7 @@ static_assert(ROWS_PER_LAUNCH == VTTS_MCD_ROWS_PER_LAUNCH, "the header names the
 static_assert(FRAMES == 64, "a wave's lanes own the frames of a block");
 static_assert(VTTS_MCD_MAX_CEPS <= VTTS_DTW_MAX_FEAT, "the cepstra are the DTW's features");
 
-struct McdRows {
-    int len[ROWS_PER_LAUNCH];
-};
+using McdRows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // frames of each row of this launch
 
 struct McdArgs {
     const float* xa;     // first row of this launch
@@ -227,12 +226,6 @@ int check_batch(int N, int64_t T) {
 
 size_t aligned_bytes(int N, int64_t T) { return vtts::align_up(sizeof(double) * (size_t)N * (size_t)((T + FRAMES - 1) / FRAMES), 256); }
 
-McdRows slice_rows(const int32_t* lens, int n0, int np, int64_t full) {
-    McdRows r;
-    for (int k = 0; k < ROWS_PER_LAUNCH; ++k) r.len[k] = k < np ? (lens ? lens[n0 + k] : (int)full) : 0;
-    return r;
-}
-
 }  // namespace
 
 VTTS_API int vtts_mcd_create(const vtts_mcd_cfg* cfg, int device, vtts_mcd** out) {
@@ -282,15 +275,14 @@ VTTS_API int vtts_mcd_cepstra(vtts_mcd* h, const float* logmel_dev, int N, int64
     g.M = M;
     g.K = K;
     const int blocks = (int)((T_stride + FRAMES - 1) / FRAMES);
-    for (int n0 = 0; n0 < N; n0 += ROWS_PER_LAUNCH) {  // the lengths travel as kernel arguments
-        const int np = N - n0 < ROWS_PER_LAUNCH ? N - n0 : ROWS_PER_LAUNCH;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lens, T_stride, [&](int n0, int np, const McdRows& rows) -> int {
         g.xa = logmel_dev + (size_t)n0 * T_stride * M;
         g.ceps = ceps_dev + (size_t)n0 * T_stride * K;
-        hipLaunchKernelGGL(mcd_cepstra_k, dim3(blocks, np), dim3(THREADS), lds, s, g, slice_rows(lens, n0, np, T_stride));
+        hipLaunchKernelGGL(mcd_cepstra_k, dim3(blocks, np), dim3(THREADS), lds, s, g, rows);
         e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "mcd_cepstra_k launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }
 
 VTTS_API int vtts_mcd_aligned_workspace_bytes(const vtts_mcd* h, int N, int64_t T, size_t* bytes) {
@@ -330,19 +322,18 @@ VTTS_API int vtts_mcd_aligned(vtts_mcd* h, const float* logmel_a_dev, const floa
     g.blocks = (int)((T + FRAMES - 1) / FRAMES);
     g.M = M;
     g.K = K;
-    for (int n0 = 0; n0 < N; n0 += ROWS_PER_LAUNCH) {
-        const int np = N - n0 < ROWS_PER_LAUNCH ? N - n0 : ROWS_PER_LAUNCH;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lens, T, [&](int n0, int np, const McdRows& rows) -> int {
         g.xa = logmel_a_dev + (size_t)n0 * Ta_stride * M;
         g.xb = logmel_b_dev + (size_t)n0 * Tb_stride * M;
         g.frame = frame_dev ? frame_dev + (size_t)n0 * F_stride : nullptr;
         g.part = static_cast<double*>(workspace) + (size_t)n0 * g.blocks;
         g.sum = sum_dev + n0;
-        hipLaunchKernelGGL(mcd_aligned_k, dim3(g.blocks, np), dim3(THREADS), lds, s, g, slice_rows(lens, n0, np, T));
+        hipLaunchKernelGGL(mcd_aligned_k, dim3(g.blocks, np), dim3(THREADS), lds, s, g, rows);
         hipLaunchKernelGGL(mcd_rowsum_k, dim3((np + 63) / 64), dim3(64), 0, s, g, np);
         e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "mcd_aligned_k launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }
 
 VTTS_API int vtts_mcd_dtw_workspace_bytes(const vtts_mcd* h, int N, int64_t Ta_stride, int64_t Tb_stride, size_t* bytes) {

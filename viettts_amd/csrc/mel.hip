@@ -27,6 +27,8 @@
 
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_mel.h"
+#include "launch_rows.h"
+#include "mel_framing.h"
 #include "sample_convert.h"
 #include "stockham.h"  // under this file's default contraction: the a * b + c of its complex products are FMAs here, as they always were
 #include "vtts_internal.h"
@@ -36,11 +38,12 @@ using vtts::failf;
 using vtts::upload_blob;
 using vtts_sample::to_float;
 using namespace vtts_stockham;
+namespace mf = vtts_mel_framing;
 
 namespace {
 
-constexpr int NFFT = 1024, HOP = 256, NBINS = NFFT / 2 + 1, HALF = NFFT / 2;
-constexpr int PADL = (NFFT - HOP) / 2;                    // 384 reflected samples on each side
+constexpr int NFFT = mf::NFFT, HOP = mf::HOP, NBINS = NFFT / 2 + 1, HALF = NFFT / 2;
+constexpr int PADL = mf::PADL;                            // 384 reflected samples on each side
 constexpr int FPB = VTTS_MEL_FRAMES_PER_BLOCK;            // frames (= waves) per workgroup
 constexpr int THREADS = 64 * FPB;
 constexpr int SPAN = (FPB + 3) * HOP;                     // samples the FPB frames cover
@@ -58,9 +61,7 @@ constexpr int BLOB_FLOATS = OFF_SPW + MAX_NNZ + 2;
 
 constexpr size_t LDS_BYTES = (size_t)(SPAN + FPB * 2 * XBUF + MAX_NNZ) * sizeof(float);
 
-struct MelRows {
-    int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
-};
+using Rows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // samples of each row of this launch
 
 struct MelArgs {
     const void* wav;   // first row of this launch
@@ -74,7 +75,7 @@ struct MelArgs {
 };
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void mel_fused_k(const MelArgs a, const MelRows rows) {
+__global__ __launch_bounds__(THREADS) void mel_fused_k(const MelArgs a, const Rows rows) {
     extern __shared__ float4 lds4[];
     float* lds = reinterpret_cast<float*>(lds4);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -274,9 +275,8 @@ VTTS_API void vtts_mel_destroy(vtts_mel* h) { delete h; }
 
 VTTS_API int vtts_mel_num_frames(const vtts_mel* h, int64_t n_samples, int64_t* frames) {
     if (!h || !frames) return failf(VTTS_ERR_INVALID, "null argument");
-    if (n_samples < VTTS_MEL_MIN_SAMPLES)
-        return failf(VTTS_ERR_SHAPE, "a row needs at least %d samples for its reflection padding (got %lld)", VTTS_MEL_MIN_SAMPLES, (long long)n_samples);
-    *frames = (n_samples + 2 * PADL - NFFT) / HOP + 1;
+    if (int rc = mf::check_shortest(n_samples)) return rc;
+    *frames = mf::num_frames(n_samples);
     return VTTS_OK;
 }
 
@@ -312,8 +312,7 @@ VTTS_API int vtts_mel_bind_packed(vtts_mel* h, void* dev_blob, size_t blob_bytes
 VTTS_API int vtts_mel_workspace_bytes(const vtts_mel* h, int N, int64_t S, size_t* bytes) {
     if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
     if (N <= 0) return failf(VTTS_ERR_INVALID, "N must be positive (got %d)", N);
-    if (S < VTTS_MEL_MIN_SAMPLES)
-        return failf(VTTS_ERR_SHAPE, "a row needs at least %d samples for its reflection padding (got %lld)", VTTS_MEL_MIN_SAMPLES, (long long)S);
+    if (int rc = mf::check_shortest(S)) return rc;
     *bytes = 0;  // spectrum and magnitudes live in LDS; the row lengths travel as kernel arguments
     return VTTS_OK;
 }
@@ -325,18 +324,7 @@ VTTS_API int vtts_mel_forward(vtts_mel* h, const void* wav_dev, int dtype, int N
     if (dtype != VTTS_MEL_F32 && dtype != VTTS_MEL_PCM16) return failf(VTTS_ERR_INVALID, "dtype must be VTTS_MEL_F32 or VTTS_MEL_PCM16 (got %d)", dtype);
     if (!h->blob) return failf(VTTS_ERR_STATE, "forward() before pack()/bind_packed()");
     if (N <= 0) return failf(VTTS_ERR_INVALID, "N must be positive (got %d)", N);
-    if (S_stride < VTTS_MEL_MIN_SAMPLES)
-        return failf(VTTS_ERR_SHAPE, "a row needs at least %d samples for its reflection padding (got S_stride %lld)", VTTS_MEL_MIN_SAMPLES, (long long)S_stride);
-    if (S_stride > 0x7fffffff - 2 * NFFT) return failf(VTTS_ERR_SHAPE, "rows of 2^31 samples are not supported (got S_stride %lld)", (long long)S_stride);
-    int64_t t_max = 0;
-    for (int b = 0; b < N; ++b) {
-        const int64_t len = lengths ? lengths[b] : S_stride;
-        if (len < VTTS_MEL_MIN_SAMPLES || len > S_stride)
-            return failf(VTTS_ERR_SHAPE, "lengths[%d] = %lld is outside %d .. S_stride = %lld", b, (long long)len, VTTS_MEL_MIN_SAMPLES, (long long)S_stride);
-        const int64_t tb = (len + 2 * PADL - NFFT) / HOP + 1;
-        if (tb > t_max) t_max = tb;
-    }
-    if (T_stride < t_max) return failf(VTTS_ERR_SHAPE, "T_stride = %lld is below the longest row's %lld frames", (long long)T_stride, (long long)t_max);
+    if (int rc = mf::check_batch(N, S_stride, lengths, T_stride)) return rc;
     const int64_t tiles = (T_stride + FPB - 1) / FPB;
     if (tiles > 0x7fffffff) return failf(VTTS_ERR_SHAPE, "T_stride = %lld is too large", (long long)T_stride);
 
@@ -354,10 +342,7 @@ VTTS_API int vtts_mel_forward(vtts_mel* h, const void* wav_dev, int dtype, int N
     a.nnz = h->nnz;
     a.vec_ok = reinterpret_cast<uintptr_t>(wav_dev) % 16 == 0 && (S_stride * esz) % 16 == 0;
     a.floor_log = (float)std::log(1e-5);
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the row lengths travel as kernel arguments, 256 rows per launch
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        MelRows rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         a.wav = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.mel = mel_dev + (size_t)r0 * T_stride * h->cfg.n_mels;
         const dim3 grid((unsigned)tiles, (unsigned)nr);
@@ -367,6 +352,6 @@ VTTS_API int vtts_mel_forward(vtts_mel* h, const void* wav_dev, int dtype, int N
             hipLaunchKernelGGL(mel_fused_k<float>, grid, dim3(THREADS), LDS_BYTES, s, a, rows);
         e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "mel kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

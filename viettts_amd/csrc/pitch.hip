@@ -33,6 +33,8 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_mel.h"
 #include "../../include/vtts_pitch.h"
+#include "launch_rows.h"
+#include "mel_framing.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
 #include "wave_common.h"
@@ -45,6 +47,7 @@
 using vtts::failf;
 using vtts_sample::to_float;
 using vtts_wave::wave_sync;
+namespace mf = vtts_mel_framing;
 
 namespace {
 
@@ -60,13 +63,11 @@ constexpr int LAGBUF = 64 * MAX_LAG_BLOCKS;               // floats of one wave'
 constexpr int ROWS_PER_LAUNCH = 256;
 // the last word any lane reads from the image: shift 3, last frame, base + lane 63 + the last block's last step (tau_max = 512: base 0)
 static_assert(3 + (FPB - 1) * HOP + 63 + 64 * (MAX_LAG_BLOCKS - 1 + RUNS - 1) + 63 < IMG, "stream reads stay inside the staged image");
-static_assert(NFFT == 1024 && HOP == 256 && PADL == (NFFT - HOP) / 2 && W == 512 && W + MAX_LAG == NFFT, "the kernel is built for the mel framing");
+static_assert(NFFT == mf::NFFT && HOP == mf::HOP && PADL == mf::PADL && W == 512 && W + MAX_LAG == NFFT, "the kernel is built for the mel framing");
 static_assert(VTTS_PITCH_MIN_SAMPLES == VTTS_MEL_MIN_SAMPLES, "one rule for the shortest row");
 static_assert((size_t)(IMG + FPB * 2 * LAGBUF) * sizeof(float) <= 64 * 1024, "static LDS");
 
-struct PitchRows {
-    int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
-};
+using Rows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // samples of each row of this launch
 
 struct PitchArgs {
     const void* wav;   // first row of this launch
@@ -88,7 +89,7 @@ __device__ __forceinline__ float step(float s, float a, float y) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(THREADS) void pitch_yin_k(const PitchArgs a, const PitchRows rows) {
+__global__ __launch_bounds__(THREADS) void pitch_yin_k(const PitchArgs a, const Rows rows) {
     __shared__ float4 lds4[(IMG + FPB * 2 * LAGBUF) / 4];
     float* lds = reinterpret_cast<float*>(lds4);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -296,17 +297,15 @@ VTTS_API void vtts_pitch_destroy(vtts_pitch* h) { delete h; }
 
 VTTS_API int vtts_pitch_num_frames(const vtts_pitch* h, int64_t n_samples, int64_t* frames) {
     if (!h || !frames) return failf(VTTS_ERR_INVALID, "null argument");
-    if (n_samples < VTTS_PITCH_MIN_SAMPLES)
-        return failf(VTTS_ERR_SHAPE, "a row needs at least %d samples for its reflection padding (got %lld)", VTTS_PITCH_MIN_SAMPLES, (long long)n_samples);
-    *frames = (n_samples + 2 * PADL - NFFT) / HOP + 1;
+    if (int rc = mf::check_shortest(n_samples)) return rc;
+    *frames = mf::num_frames(n_samples);
     return VTTS_OK;
 }
 
 VTTS_API int vtts_pitch_workspace_bytes(const vtts_pitch* h, int N, int64_t S, size_t* bytes) {
     if (!h || !bytes) return failf(VTTS_ERR_INVALID, "null argument");
     if (N <= 0) return failf(VTTS_ERR_INVALID, "N must be positive (got %d)", N);
-    if (S < VTTS_PITCH_MIN_SAMPLES)
-        return failf(VTTS_ERR_SHAPE, "a row needs at least %d samples for its reflection padding (got %lld)", VTTS_PITCH_MIN_SAMPLES, (long long)S);
+    if (int rc = mf::check_shortest(S)) return rc;
     *bytes = 0;  // d, c and the running sum live in LDS; the row lengths travel as kernel arguments
     return VTTS_OK;
 }
@@ -317,18 +316,7 @@ VTTS_API int vtts_pitch_forward(vtts_pitch* h, const void* wav_dev, int dtype, i
     if (!h || !wav_dev || !f0_dev || !aperiodicity_dev || !candidate_dev) return failf(VTTS_ERR_INVALID, "null argument");
     if (dtype != VTTS_MEL_F32 && dtype != VTTS_MEL_PCM16) return failf(VTTS_ERR_INVALID, "dtype must be VTTS_MEL_F32 or VTTS_MEL_PCM16 (got %d)", dtype);
     if (N <= 0) return failf(VTTS_ERR_INVALID, "N must be positive (got %d)", N);
-    if (S_stride < VTTS_PITCH_MIN_SAMPLES)
-        return failf(VTTS_ERR_SHAPE, "a row needs at least %d samples for its reflection padding (got S_stride %lld)", VTTS_PITCH_MIN_SAMPLES, (long long)S_stride);
-    if (S_stride > 0x7fffffff - 2 * NFFT) return failf(VTTS_ERR_SHAPE, "rows of 2^31 samples are not supported (got S_stride %lld)", (long long)S_stride);
-    int64_t t_max = 0;
-    for (int b = 0; b < N; ++b) {
-        const int64_t len = lengths ? lengths[b] : S_stride;
-        if (len < VTTS_PITCH_MIN_SAMPLES || len > S_stride)
-            return failf(VTTS_ERR_SHAPE, "lengths[%d] = %lld is outside %d .. S_stride = %lld", b, (long long)len, VTTS_PITCH_MIN_SAMPLES, (long long)S_stride);
-        const int64_t tb = (len + 2 * PADL - NFFT) / HOP + 1;
-        if (tb > t_max) t_max = tb;
-    }
-    if (T_stride < t_max) return failf(VTTS_ERR_SHAPE, "T_stride = %lld is below the longest row's %lld frames", (long long)T_stride, (long long)t_max);
+    if (int rc = mf::check_batch(N, S_stride, lengths, T_stride)) return rc;
     const int64_t tiles = (T_stride + FPB - 1) / FPB;
     if (tiles > 0x7fffffff) return failf(VTTS_ERR_SHAPE, "T_stride = %lld is too large", (long long)T_stride);
 
@@ -343,10 +331,7 @@ VTTS_API int vtts_pitch_forward(vtts_pitch* h, const void* wav_dev, int dtype, i
     a.vec_ok = reinterpret_cast<uintptr_t>(wav_dev) % 16 == 0 && (S_stride * esz) % 16 == 0;
     a.threshold = h->cfg.threshold;
     a.rate = (float)h->cfg.sample_rate;
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the row lengths travel as kernel arguments, 256 rows per launch
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        PitchRows rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         a.wav = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.f0 = f0_dev + (size_t)r0 * T_stride;
         a.ap = aperiodicity_dev + (size_t)r0 * T_stride;
@@ -358,6 +343,6 @@ VTTS_API int vtts_pitch_forward(vtts_pitch* h, const void* wav_dev, int dtype, i
             hipLaunchKernelGGL(pitch_yin_k<float>, grid, dim3(THREADS), 0, s, a, rows);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "pitch kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

@@ -23,6 +23,7 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_spectral.h"
+#include "launch_rows.h"
 #include "vtts_internal.h"
 
 // x and y must come out of the same arithmetic whichever kernel instance (fp32 or PCM16 input) and whichever turn of the signal loop runs it:
@@ -39,7 +40,8 @@ namespace sh = vtts_stft_host;
 namespace {
 
 constexpr int ROWS_PER_LAUNCH = 128;
-static_assert(ROWS_PER_LAUNCH == VTTS_SPECTRAL_ROWS_PER_LAUNCH && ROWS_PER_LAUNCH == sh::ROWS, "the header states the split");
+static_assert(ROWS_PER_LAUNCH == VTTS_SPECTRAL_ROWS_PER_LAUNCH, "the header states the split");
+using Rows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // samples of each row of this launch
 constexpr int MAX_F = sh::MAX_F;
 constexpr float P_FLOOR = 1e-7f;
 constexpr int SIGNALS = 2, REDUCE = 32;  // of sh::frames_lds_bytes: x and y are staged, and a frame leaves four fp64 sums
@@ -61,7 +63,7 @@ struct SpecArgs {            // every pointer at the launch's first row
 };
 
 template <int NFFT, typename TI>
-__global__ __launch_bounds__(64 * MAX_F) void spectral_frames_k(const SpecArgs a, const sh::Rows rows) {
+__global__ __launch_bounds__(64 * MAX_F) void spectral_frames_k(const SpecArgs a, const Rows rows) {
     constexpr int H = NFFT / 2, NB = H + 1, XB = pad8(H), J = Bins<H>::J;
     extern __shared__ double lds8[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(64 * MAX_F) void spectral_frames_k(const SpecArgs a
 }
 
 template <int NB>
-__global__ __launch_bounds__(64) void spectral_finish_k(const SpecArgs a, const sh::Rows rows) {
+__global__ __launch_bounds__(64) void spectral_finish_k(const SpecArgs a, const Rows rows) {
     const int lane = threadIdx.x, b = blockIdx.x;
     const long long T = 1 + (long long)rows.len[b] / a.hop, G = (T + a.F - 1) / a.F;
     const double* p = a.part + (long long)b * a.g_stride * 4;
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(64) void spectral_finish_k(const SpecArgs a, const 
 }
 
 template <int NFFT>
-hipError_t launch(bool pcm, dim3 grid, int F, size_t lds, hipStream_t s, const SpecArgs& a, const sh::Rows& rows, vtts::DynLdsOnce& once) {
+hipError_t launch(bool pcm, dim3 grid, int F, size_t lds, hipStream_t s, const SpecArgs& a, const Rows& rows, vtts::DynLdsOnce& once) {
     const void* fn = pcm ? reinterpret_cast<const void*>(&spectral_frames_k<NFFT, short>) : reinterpret_cast<const void*>(&spectral_frames_k<NFFT, float>);
     const hipError_t e = vtts::set_max_dynamic_lds(fn, VTTS_SPECTRAL_LDS_BUDGET, once);
     if (e != hipSuccess) return e;
@@ -261,9 +263,7 @@ VTTS_API int vtts_spectral_forward(vtts_spectral* h, const void* ref_dev, const 
     const bool pcm = dtype == VTTS_AUDIO_PCM16;
     const size_t esz = pcm ? 2 : 4, lds = sh::frames_lds_bytes(n_fft, hop, F, SIGNALS, REDUCE);
     const size_t nb = (size_t)n_fft / 2 + 1;
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        const sh::Rows rows = sh::launch_rows(lengths, r0, nr, S_stride);
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         SpecArgs a;
         a.x = static_cast<const char*>(ref_dev) + (size_t)r0 * S_stride * esz;
         a.y = static_cast<const char*>(test_dev) + (size_t)r0 * S_stride * esz;
@@ -282,6 +282,6 @@ VTTS_API int vtts_spectral_forward(vtts_spectral* h, const void* ref_dev, const 
         vtts::DynLdsOnce& once = pcm ? h->lds_pcm : h->lds_f32;
         const hipError_t e = sh::by_nfft(n_fft, [&](auto n) { return launch<decltype(n)::value>(pcm, grid, F, lds, s, a, rows, once); });
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "spectral kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

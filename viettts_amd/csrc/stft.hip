@@ -27,6 +27,7 @@
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_spectral.h"
 #include "../../include/vtts_stft.h"
+#include "launch_rows.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
 
@@ -47,7 +48,8 @@ namespace sh = vtts_stft_host;
 namespace {
 
 constexpr int ROWS_PER_LAUNCH = 128;
-static_assert(ROWS_PER_LAUNCH == VTTS_STFT_ROWS_PER_LAUNCH && ROWS_PER_LAUNCH == sh::ROWS, "the header states the split");
+static_assert(ROWS_PER_LAUNCH == VTTS_STFT_ROWS_PER_LAUNCH, "the header states the split");
+using Rows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // samples of each row of this launch
 constexpr int MAX_F = sh::MAX_F;
 constexpr int SIGNALS = 1, REDUCE = 0;  // of sh::frames_lds_bytes: one staged signal, nothing to reduce
 
@@ -80,7 +82,7 @@ struct InvArgs {
 __device__ __forceinline__ long long num_frames_dev(long long S, int P, int n_fft, int hop) { return (S + 2 * P - n_fft) / hop + 1; }
 
 template <int NFFT, typename TI, bool PROJ>
-__global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, const sh::Rows rows) {
+__global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, const Rows rows) {
     constexpr int H = NFFT / 2, NB = H + 1, XB = pad8(H);
     extern __shared__ float2 lds2[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(64 * MAX_F) void stft_forward_k(const FwdArgs a, co
 }
 
 template <int NFFT, typename TO>
-__global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const InvArgs a, const sh::Rows rows) {
+__global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const InvArgs a, const Rows rows) {
     constexpr int H = NFFT / 2, NB = H + 1, XB = pad8(H), W = inv_waves(NFFT), R = inv_per_thread(NFFT), NT = 64 * W, RUN = NT * R;
     constexpr int J = (H / 2) / 64 + 1;
     extern __shared__ float2 lds2[];
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(64 * inv_waves(NFFT)) void stft_inverse_k(const Inv
 }
 
 template <int NFFT>
-hipError_t launch_fwd(bool pcm, bool proj, dim3 grid, int F, size_t lds, hipStream_t s, const FwdArgs& a, const sh::Rows& rows, vtts::DynLdsOnce* once) {
+hipError_t launch_fwd(bool pcm, bool proj, dim3 grid, int F, size_t lds, hipStream_t s, const FwdArgs& a, const Rows& rows, vtts::DynLdsOnce* once) {
     const void* fn = pcm ? (proj ? reinterpret_cast<const void*>(&stft_forward_k<NFFT, short, true>) : reinterpret_cast<const void*>(&stft_forward_k<NFFT, short, false>))
                          : (proj ? reinterpret_cast<const void*>(&stft_forward_k<NFFT, float, true>) : reinterpret_cast<const void*>(&stft_forward_k<NFFT, float, false>));
     const hipError_t e = vtts::set_max_dynamic_lds(fn, VTTS_SPECTRAL_LDS_BUDGET, once[2 * pcm + proj]);
@@ -206,7 +208,7 @@ hipError_t launch_fwd(bool pcm, bool proj, dim3 grid, int F, size_t lds, hipStre
 }
 
 template <int NFFT>
-hipError_t launch_inv(bool pcm, dim3 grid, hipStream_t s, const InvArgs& a, const sh::Rows& rows, vtts::DynLdsOnce* once) {
+hipError_t launch_inv(bool pcm, dim3 grid, hipStream_t s, const InvArgs& a, const Rows& rows, vtts::DynLdsOnce* once) {
     const void* fn = pcm ? reinterpret_cast<const void*>(&stft_inverse_k<NFFT, short>) : reinterpret_cast<const void*>(&stft_inverse_k<NFFT, float>);
     const hipError_t e = vtts::set_max_dynamic_lds(fn, VTTS_SPECTRAL_LDS_BUDGET, once[pcm]);
     if (e != hipSuccess) return e;
@@ -290,9 +292,7 @@ int forward_or_project(vtts_stft* h, const char* what, bool proj, const void* wa
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pcm = dtype == VTTS_AUDIO_PCM16;
     const size_t esz = pcm ? 2 : 4, lds = sh::frames_lds_bytes(n_fft, hop, F, SIGNALS, REDUCE), nb = (size_t)n_fft / 2 + 1;
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        const sh::Rows rows = sh::launch_rows(lengths, r0, nr, S_stride);
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         FwdArgs a;
         a.x = static_cast<const char*>(wav_dev) + (size_t)r0 * S_stride * esz;
         a.blob = h->blob;
@@ -306,8 +306,8 @@ int forward_or_project(vtts_stft* h, const char* what, bool proj, const void* wa
         const dim3 grid((unsigned)gmax, (unsigned)nr);
         const hipError_t e = sh::by_nfft(n_fft, [&](auto n) { return launch_fwd<decltype(n)::value>(pcm, proj, grid, F, lds, s, a, rows, h->lds_fwd); });
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "stft %s kernel launch failed: %s", what, hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }
 }  // namespace
 
@@ -410,9 +410,7 @@ VTTS_API int vtts_stft_inverse(vtts_stft* h, const void* spec_dev, int N, int64_
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pcm = dtype == VTTS_AUDIO_PCM16;
     const size_t esz = pcm ? 2 : 4, nb = (size_t)n_fft / 2 + 1;
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        const sh::Rows rows = sh::launch_rows(lengths, r0, nr, S_stride);
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         InvArgs a;
         a.spec = static_cast<const float2*>(spec_dev) + (size_t)r0 * T_stride * nb;
         a.blob = h->blob;
@@ -424,6 +422,6 @@ VTTS_API int vtts_stft_inverse(vtts_stft* h, const void* spec_dev, int N, int64_
         const dim3 grid((unsigned)gmax, (unsigned)nr);
         const hipError_t e = sh::by_nfft(n_fft, [&](auto n) { return launch_inv<decltype(n)::value>(pcm, grid, s, a, rows, h->lds_inv); });
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "stft inverse kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

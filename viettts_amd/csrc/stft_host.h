@@ -1,5 +1,5 @@
-// The host side that the short-time stages with a free resolution share (spectral.hip, stft.hip): what a resolution may be, the tables it
-// needs and their packed blob, the LDS of a workgroup of F frames, the rows of one launch and the choice of a kernel instance by n_fft.
+// The host side that the short-time stages with a free resolution share (spectral.hip, stft.hip, denoise.hip): what a resolution may be, the
+// tables it needs and their packed blob, the LDS of a workgroup of F frames and the choice of a kernel instance by n_fft (launch_rows.h: the rows).
 #pragma once
 
 #include <cmath>
@@ -16,16 +16,6 @@ namespace vtts_stft_host {
 
 using vtts::failf;
 using vtts_stockham::pad8;
-
-constexpr int ROWS = 128;  // rows of one launch: their lengths travel as kernel arguments
-struct Rows {
-    int len[ROWS];  // samples of each row of this launch
-};
-inline Rows launch_rows(const int32_t* lengths, int r0, int nr, int64_t S_stride) {
-    Rows rows;
-    for (int b = 0; b < ROWS; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
-    return rows;
-}
 
 constexpr int MAX_F = VTTS_SPECTRAL_MAX_FRAMES_PER_BLOCK;
 constexpr int even(int n) { return (n + 1) & ~1; }

@@ -28,6 +28,7 @@
 #include "../../include/vtts_audio.h"
 #include "../../include/vtts_hifigan.h"
 #include "../../include/vtts_stoi.h"
+#include "launch_rows.h"
 #include "sample_convert.h"
 #include "vtts_internal.h"
 
@@ -61,9 +62,7 @@ struct StoiTables {
     float tw[FRAME];    // exp(-2 pi i j / 512), j = 0 .. 127, as (re, im) pairs
 };
 
-struct StoiLens {
-    int len[ROWS_PER_LAUNCH];  // samples of each row of this launch
-};
+using Rows = vtts_rows::Lens<ROWS_PER_LAUNCH>;  // samples of each row of this launch
 
 struct StoiArgs {               // every pointer at the launch's first row
     const void* x;              // clean
@@ -91,7 +90,7 @@ __host__ __device__ __forceinline__ long long num_frames(long long S) { return S
 
 // ---- A. candidate frame energies of the clean row ----------------------------------------------------------------------------------
 template <typename TI>
-__global__ __launch_bounds__(THREADS) void stoi_energy_k(const StoiArgs a, const StoiTables t, const StoiLens rows) {
+__global__ __launch_bounds__(THREADS) void stoi_energy_k(const StoiArgs a, const StoiTables t, const Rows rows) {
     __shared__ float span[SPAN];
     __shared__ float win[FRAME];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(THREADS) void stoi_energy_k(const StoiArgs a, const
 }
 
 // ---- A. the keep mask and the kept list ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(KEEP_THREADS) void stoi_keep_k(const StoiArgs a, const StoiLens rows) {
+__global__ __launch_bounds__(KEEP_THREADS) void stoi_keep_k(const StoiArgs a, const Rows rows) {
     __shared__ double wmax[KEEP_THREADS / 64];
     __shared__ int wcnt[KEEP_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -447,10 +446,7 @@ VTTS_API int vtts_stoi_forward(vtts_stoi* h, const void* clean_dev, const void* 
     char* ws = static_cast<char*>(workspace);
     const long long t_stride = mags_dev ? T_stride : l.tmax;
     float* mags = mags_dev ? mags_dev : reinterpret_cast<float*>(ws + l.mags);
-    for (int r0 = 0; r0 < N; r0 += ROWS_PER_LAUNCH) {  // the rows' lengths travel as kernel arguments
-        const int nr = N - r0 < ROWS_PER_LAUNCH ? N - r0 : ROWS_PER_LAUNCH;
-        StoiLens rows;
-        for (int b = 0; b < ROWS_PER_LAUNCH; ++b) rows.len[b] = b < nr ? (lengths ? lengths[r0 + b] : (int)S_stride) : 0;
+    return vtts_rows::for_each_launch<ROWS_PER_LAUNCH>(N, lengths, S_stride, [&](int r0, int nr, const Rows& rows) -> int {
         StoiArgs a;
         a.x = static_cast<const char*>(clean_dev) + (size_t)r0 * S_stride * esz;
         a.y = static_cast<const char*>(processed_dev) + (size_t)r0 * S_stride * esz;
@@ -490,6 +486,6 @@ VTTS_API int vtts_stoi_forward(vtts_stoi* h, const void* clean_dev, const void* 
         hipLaunchKernelGGL(stoi_mean_k, dim3((unsigned)nr), dim3(64), 0, s, a);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return failf(VTTS_ERR_HIP, "stoi kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return VTTS_OK;
+        return VTTS_OK;
+    });
 }

@@ -43,7 +43,7 @@ inline int upload_blob(void* dev_blob, const void* host, size_t bytes, hipStream
 }
 
 // The one rule for a batch of waveform rows (the limiter's and the loudness meter's calls): fp32 or PCM16, N >= 1, a pitch that leaves `margin`
-// samples (the stage's tile) below 2^31, every length within the pitch.  *longest = the longest row.  Host arithmetic only.
+// samples (the stage's tile) below 2^31, every length within the pitch.  *longest = the longest row.  Host only; launch_rows.h cuts the call up.
 inline int check_rows(const char* what, const void* wav, int dtype, int N, int64_t S_stride, const int32_t* lengths, int margin, int64_t* longest) {
     if (!wav) return failf(VTTS_ERR_INVALID, "null argument");
     if (dtype != VTTS_AUDIO_F32 && dtype != VTTS_AUDIO_PCM16) return failf(VTTS_ERR_INVALID, "%s: dtype must be VTTS_AUDIO_F32 or VTTS_AUDIO_PCM16 (got %d)", what, dtype);
